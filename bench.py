@@ -16,9 +16,16 @@ collective; the only collective is one RCCL broadcast of the twiddle block at st
       broadcast on the device view, the rank count and the parity all-reduce on device tensors -- the path the 8-GPU run takes,
       executed on the one GPU at hand.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel, HIP
-events on the launch stream) and `cpu_baseline` (the oracle -- a C restatement of the reference's CPU
-path -- timed on this host's cores over a bounded sample; rank 0, N = 1 only).
+Prints ONE JSON line on rank 0: `metric`, `value` (ring-muls/s over the K timed steps), `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (milliseconds of one timed step) and the configuration.  A plain run does only that: set up, warm up, time the K steps.
+
+  python bench.py ... --full      everything else as well: the property gate (canonical outputs, icrt(crt(c)) == c), parity of a
+      sample against the oracle, `roofline` (dominant kernel, HIP events on the launch stream, over K more steps), the copy bandwidth,
+      the clock / power sampler, the figures replayed from profiles/, and `cpu_baseline` (the oracle -- a C restatement of the
+      reference's CPU path -- timed on this host's cores over a bounded sample; rank 0, N = 1 only).
+  python bench.py ... --dump-outputs DIR      after the timed steps, rank 0 writes DIR/c.npy: a fixed, seeded sample of the ring
+      elements the last timed step left in `a` (its own shard), float64 of shape (elements, words per element, 2) holding the low
+      and high 32 bits of every word.  Same arguments, same inputs: two builds compare output for output.
 """
 import argparse
 import json
@@ -187,6 +194,22 @@ def replayed_kernel_stats(workload, dom_kernel_names, here_hash):
         return None, None, "unreadable"
 
 
+def dump_outputs(outdir, a, batch, wpe, seed=0x5EED0003, budget=32 << 20):
+    """DIR/c.npy: the ring elements of a fixed, seeded sample (sorted indices; as many as fit `budget` bytes, at least one) of the
+    batch `a` holds, float64 of shape (elements, wpe, 2) = (low, high) 32 bits of every word -- exact for 64-bit words, which
+    float64 itself is not.  The element indices depend on the seed and the batch alone."""
+    import numpy as np
+    import torch
+
+    n = max(1, min(batch, budget // (wpe * 2 * 8)))
+    idx = np.sort(np.random.default_rng(seed).choice(batch, size=n, replace=False))
+    words = a.view(batch, wpe)[torch.from_numpy(idx).to(a.device)].cpu().numpy()
+    words = words.view(np.uint32).astype(np.uint64) if words.dtype == np.int32 else words.view(np.uint64)
+    c = np.stack([words & 0xFFFFFFFF, words >> 32], axis=-1).astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "c.npy"), c)
+
+
 def self_launch(args):
     """--gpus N > 1 outside torchrun: start the ranks as a child process tree.  Nothing in this process has initialised HIP
     (no torch.cuda call, no library load), so no exec-after-GPU-init can happen; the child is a plain subprocess."""
@@ -211,9 +234,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="goldilocks_d65536_b16384", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch (debug only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and the measurements beyond the headline: property gate, oracle parity, roofline and "
+                         "per-kernel figures (K more steps), copy bandwidth, clock / power, profile replay, CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's output to DIR/c.npy (float64, at most 32 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the oracle parity and the CPU baseline")
     ap.add_argument("--calibrate", action="store_true",
-                    help="after the timed region, also time the one-stream plan (sr_plan.lanes = 1) on a second context and report it as "
+                    help="(with --full) after the timed region, also time the one-stream plan (sr_plan.lanes = 1) on a second context and report it as "
                          "roofline.single_stream -- context only, never the headline (off by default: profile runs and the driver's run "
                          "carry the timed configuration's launches only)")
     ap.add_argument("--no-calibration", action="store_true", help="(accepted for older scripts; calibration is off unless --calibrate)")
@@ -221,13 +249,13 @@ def main():
                     help="initialise the process group and run every collective of the N > 1 path even at N = 1 (a one-rank nccl group)")
     ap.add_argument("--lanes", type=int, default=0, choices=(0, 1, 2),
                     help="sr_plan.lanes: 0 = the library's own choice (default), 1 = one stream, 2 = two lanes (A/B runs)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(with --full) length of the timed CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--variant", default="mul", choices=("mul", "mul_ntt_rhs"),
                     help="mul: c = a * b, both in coefficient form (the metric).  mul_ntt_rhs: b kept in NTT form (constant operand), "
                          "sr_ring_mul_ntt_rhs_batch_dev -- informational, never the headline")
     ap.add_argument("--parity-sample", type=int, default=-1,
-                    help="elements per rank checked bit for bit against the oracle (default: 64 for the D = 2^20 shard, 3 otherwise)")
+                    help="(with --full) elements per rank checked bit for bit against the oracle (default: 64 for the D = 2^20 shard, 3 otherwise)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -251,7 +279,7 @@ def main():
     torch.cuda.set_device(dev_index)
     dev = torch.device("cuda", dev_index)
     sampler = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             pr = torch.cuda.get_device_properties(dev_index)
             bus = "%04x:%02x:%02x.0" % (pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id)
@@ -323,8 +351,9 @@ def main():
         mul_fn, crt_fn, icrt_fn, add_fn = ring.mul_dev, ring.elementwise_crt_dev, ring.elementwise_icrt_dev, ring.add_dev
         noncanonical = ring.count_noncanonical_dev
 
-    # ---- property gate (no oracle here: the oracle is only used inside the cpu_baseline leg below): one untimed step,
-    #      outputs canonical, icrt(crt(c)) == c on the result, sampled outputs kept for the cpu_baseline leg's bit-exact check
+    # ---- one untimed step (every run: the timed steps start from its result), then under --full the property gate (no oracle
+    #      here: the oracle is only used inside the parity / cpu_baseline legs below): outputs canonical, icrt(crt(c)) == c on the
+    #      result, sampled outputs kept for the parity leg's bit-exact check
     wpe = ring.words_per_elem
     if args.variant == "mul_ntt_rhs":
         b_ntt = b.clone()
@@ -348,18 +377,20 @@ def main():
         plan_used = "library default (sr_plan.lanes = 0, auto): two lanes, unmeasured -- the batch is below the eight chunks the probe wants"
     else:
         plan_used = "library default (no chunked plan applies to this ring / degree / batch)"
-    assert noncanonical(a) == 0, "non-canonical outputs"
-    n_sample = args.parity_sample if args.parity_sample >= 0 else (64 if k >= 20 else 3)
-    n_sample = min(n_sample, batch)
-    sample = sorted({(i * (batch - 1)) // max(n_sample - 1, 1) for i in range(n_sample)}) if n_sample else []
-    as_u64 = (lambda t: t.cpu().numpy().view(np.uint32).astype(np.uint64)) if packed else (lambda t: t.cpu().numpy().view(np.uint64).copy())
-    sample_out = {e: as_u64(a[e * wpe:(e + 1) * wpe]) for e in sample}
-    rt = a[:min(batch, 8) * wpe].clone()
-    crt_fn(rt)
-    icrt_fn(rt)
-    if not torch.equal(rt, a[:rt.numel()]):
-        raise SystemExit("PROPERTY FAILURE rank %d: icrt(crt(c)) != c" % rank)
-    del rt
+    sample = []
+    if args.full:
+        assert noncanonical(a) == 0, "non-canonical outputs"
+        n_sample = args.parity_sample if args.parity_sample >= 0 else (64 if k >= 20 else 3)
+        n_sample = min(n_sample, batch)
+        sample = sorted({(i * (batch - 1)) // max(n_sample - 1, 1) for i in range(n_sample)}) if n_sample else []
+        as_u64 = (lambda t: t.cpu().numpy().view(np.uint32).astype(np.uint64)) if packed else (lambda t: t.cpu().numpy().view(np.uint64).copy())
+        sample_out = {e: as_u64(a[e * wpe:(e + 1) * wpe]) for e in sample}
+        rt = a[:min(batch, 8) * wpe].clone()
+        crt_fn(rt)
+        icrt_fn(rt)
+        if not torch.equal(rt, a[:rt.numel()]):
+            raise SystemExit("PROPERTY FAILURE rank %d: icrt(crt(c)) != c" % rank)
+        del rt
 
     def barrier():
         torch.cuda.synchronize()
@@ -386,6 +417,46 @@ def main():
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         rank_ms = {"min": float(tmin.item()) / args.steps * 1e3, "max": float(t.item()) / args.steps * 1e3}
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, a, batch, wpe)
+
+    out = {
+        "metric": ("ring-muls/sec (Goldilocks, deg 2^16, batch 2^14)" if args.workload == "goldilocks_d65536_b16384"
+                   else "ring-muls/sec (%s)" % args.workload) + ("" if args.variant == "mul" else " [variant %s: b in NTT form]" % args.variant),
+        "value": world * batch * args.steps / elapsed,
+        "unit": "ring-muls/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"goldilocks": "u64", "babybear": "u32", "stark": "u256"}[ring_name],
+        "data": "synthetic",
+        "config": {"workload": args.workload, "ring": ring_name, "degree": d, "batch_per_gpu": batch,
+                   "global_batch": batch * world,
+                   "layout": ("packed uint32 = low half of the ark-ff Fp64 Montgomery limb (opt-in sr_*_packed32_* entry points), in place (a *= b), b read-only"
+                              if packed else "ark-ff Montgomery u64 limbs, in place (a *= b), b read-only"),
+                   "variant": args.variant, "plan": plan_used,
+                   "parallelism": "batch-sharded x%d, twiddle broadcast only" % world},
+    }
+
+    def multi_gpu(parity):
+        return {"backend": args.backend + (" (RCCL)" if args.backend == "nccl" else ""), "ranks_seen": ranks_seen,
+                "devices_visible": ndev, "twiddle_broadcast_bytes": bcast_bytes, "twiddle_broadcast_ms": bcast_ms,
+                "data_path_collectives": 0, "rank_ms_per_step": rank_ms,
+                "collectives_run": ["broadcast(twiddle block, device view)", "all_reduce(rank count)",
+                                    "all_reduce(step time: max, min)"] + (["all_reduce(parity: min)"] if parity else [])}
+
+    if not args.full:   # a plain run: the headline line and nothing else
+        if rank == 0:
+            if dist_on:
+                out["multi_gpu"] = multi_gpu(None)
+            print(json.dumps(out))
+        if dist_on:
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel durations over the same K steps, HIP events on the launch stream.  Every PROF_STRIDE-th launch is bracketed
     #      (7: coprime to the 3, 4 or 6 launches of a chunk, so every tag is sampled evenly): bracketing EVERY launch of a two-lane
@@ -499,8 +570,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    total_muls = world * batch * args.steps
-    value = total_muls / elapsed
+    value = out["value"]
     bytes_per_mul = 3 * d * coeff_bytes  # read a, read b, write c
     kern = {t: v for t, v in prof.items() if v["launches"]}
     # dominant kernel = the longest single launch of the step.  Since the forward column passes of both operands are ONE launch, that
@@ -633,26 +703,7 @@ def main():
     else:
         limiter = "undetermined: no PMC replay for this build (profiles/ carries another source hash)"
 
-    out = {
-        "metric": ("ring-muls/sec (Goldilocks, deg 2^16, batch 2^14)" if args.workload == "goldilocks_d65536_b16384"
-                   else "ring-muls/sec (%s)" % args.workload) + ("" if args.variant == "mul" else " [variant %s: b in NTT form]" % args.variant),
-        "value": value,
-        "unit": "ring-muls/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": {"goldilocks": "u64", "babybear": "u32", "stark": "u256"}[ring_name],
-        "data": "synthetic",
-        "config": {"workload": args.workload, "ring": ring_name, "degree": d, "batch_per_gpu": batch,
-                   "global_batch": batch * world,
-                   "layout": ("packed uint32 = low half of the ark-ff Fp64 Montgomery limb (opt-in sr_*_packed32_* entry points), in place (a *= b), b read-only"
-                              if packed else "ark-ff Montgomery u64 limbs, in place (a *= b), b read-only"),
-                   "variant": args.variant, "plan": plan_used,
-                   "parallelism": "batch-sharded x%d, twiddle broadcast only" % world},
+    out.update({
         "roofline": {"bound": "hbm", "achieved": frac_reported * HBM_PEAK_GBS, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": frac_reported, "traffic": traffic, "traffic_source": traffic_source,
                      "limiter": limiter,
@@ -677,7 +728,7 @@ def main():
                      "whole_step_hbm_traffic_gbs": (step_traffic / (elapsed / args.steps) / 1e9) if step_traffic else None,
                      "whole_step_hbm_traffic_frac": (step_traffic / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS) if step_traffic else None,
                      "per_kernel_ms_per_step": {t: v["ms"] / args.steps for t, v in kern.items()}},
-    }
+    })
     if prof_single:
         # what `kernel_avg_ms` above means when launches of two streams overlap, and the one-stream figures next to it
         ps = prof_single[dom_tag]
@@ -702,11 +753,7 @@ def main():
     if parity:
         out["parity"] = parity
     if dist_on:
-        out["multi_gpu"] = {"backend": args.backend + (" (RCCL)" if args.backend == "nccl" else ""), "ranks_seen": ranks_seen,
-                            "devices_visible": ndev, "twiddle_broadcast_bytes": bcast_bytes, "twiddle_broadcast_ms": bcast_ms,
-                            "data_path_collectives": 0, "rank_ms_per_step": rank_ms,
-                            "collectives_run": ["broadcast(twiddle block, device view)", "all_reduce(rank count)",
-                                                "all_reduce(step time: max, min)"] + (["all_reduce(parity: min)"] if parity else [])}
+        out["multi_gpu"] = multi_gpu(parity)
 
     if world == 1 and not args.no_cpu_baseline:
         import oracle_lib as O  # the timed CPU baseline (the parity check above used it as the checker)

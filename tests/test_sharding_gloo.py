@@ -102,7 +102,7 @@ def test_bench_launches_its_own_ranks_and_checks_every_shard():
     import subprocess
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--batch", "6", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--batch", "6", "--steps", "2",
            "--warmup", "1", "--parity-sample", "6", "--cpu-seconds", "0.5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -133,7 +133,7 @@ def test_bench_ranks_over_rccl_when_the_box_has_two_gpus():
         pytest.skip("one visible GPU: the gloo rehearsal above is the form of this test that applies")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--backend", "nccl", "--batch", "300", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(ranks), "--backend", "nccl", "--batch", "300", "--steps", "2",
            "--warmup", "1", "--parity-sample", "6", "--cpu-seconds", "0.5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -153,7 +153,7 @@ def test_sharded_path_at_config_4_degree_every_shard_sampled():
     import subprocess
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "goldilocks_d1048576_b8192",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--workload", "goldilocks_d1048576_b8192",
            "--batch", "16", "--steps", "2", "--warmup", "1", "--parity-sample", "16", "--cpu-seconds", "0.5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -176,7 +176,7 @@ def test_bench_single_rank_reports_the_plan_the_library_chose():
     import subprocess
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SR_LANES")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "1100", "--steps", "3", "--warmup", "1", "--parity-sample", "5",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "1100", "--steps", "3", "--warmup", "1", "--parity-sample", "5",
            "--cpu-seconds", "0.5", "--calibrate"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -229,7 +229,7 @@ def test_bench_force_dist_executes_the_rccl_path_on_one_gpu():
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SR_LANES")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--batch", "600", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--batch", "600", "--steps", "2", "--warmup", "1",
            "--parity-sample", "4", "--cpu-seconds", "0.5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

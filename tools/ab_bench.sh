@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/ab_bench.sh [bench.py args]  -- prints value, ms/step, roofline.frac and the per-kernel milliseconds of one bench line
-python bench.py --no-cpu-baseline "$@" 2>/dev/null | grep "^{" | python -c '
+python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | grep "^{" | python -c '
 import sys, json
 d = json.loads(sys.stdin.readline())
 r = d["roofline"]

@@ -3,7 +3,7 @@
 # multi-rank rehearsals on one GPU.  usage: bash tools/bench_lines.sh gpurun_out/<dir>
 out=${1:-gpurun_out/bench_lines}
 mkdir -p $out
-run() { name=$1; shift; python bench.py "$@" 2>$out/$name.err | grep "^{" > $out/bench_$name.json || { echo "FAILED $name"; tail -5 $out/$name.err; }; }
+run() { name=$1; shift; python bench.py --full "$@" 2>$out/$name.err | grep "^{" > $out/bench_$name.json || { echo "FAILED $name"; tail -5 $out/$name.err; }; }
 run default
 run default_20 --steps 20 --warmup 5 --no-cpu-baseline
 run one_stream --steps 20 --warmup 5 --lanes 1 --no-cpu-baseline

@@ -19,7 +19,7 @@ done
 if [ "$3" = onestream ]; then
   # the headline workload once more on ONE stream (bench.py --lanes 1 = sr_plan.lanes = 1): exclusive kernel durations
   mkdir -p /tmp/prof_one && cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_one/t -o p -- python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --lanes 1 > $out/bench_one_stream_under_trace.json 2> /tmp/prof_one/err.txt
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_one/t -o p -- python3 $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --lanes 1 > $out/bench_one_stream_under_trace.json 2> /tmp/prof_one/err.txt
   find /tmp/prof_one -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats_goldilocks_d65536_b16384_one_stream.csv \;
 fi
 ls -la $out | head -40

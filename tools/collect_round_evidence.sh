@@ -11,7 +11,7 @@ for p in issue mix lds icache; do echo "== pass $p (rocprofv3 --pmc, per kernel:
   echo "# xchg=0: the product kernel; xchg=1: all twelve LDS exchanges removed (wrong results, timing only)";
   for i in 1 2; do build_tmp/st_bench0 4096 30; build_tmp/st_bench1 4096 30; done; } > $O/st_bench.txt 2>&1
 for w in 5 50 200 1000; do
-  python3 bench.py --workload stark_d4096_b4096 --steps 50 --warmup $w --no-cpu-baseline 2>/dev/null | python3 -c "
+  python3 bench.py --full --workload stark_d4096_b4096 --steps 50 --warmup $w --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); c=d.get('clock_power',{})
 print('stark_d4096_b4096 --steps 50 --warmup $w: %.3f ms per step, %.0f ring-muls/s, sclk %.0f MHz, socket %.0f W (%d samples)' % (d['ms_per_step'], d['value'], c.get('sclk_mhz',0), c.get('socket_w',0), c.get('samples',0)))"

@@ -38,7 +38,7 @@ def main():
         d = os.path.join(outdir, name)
         shutil.rmtree(d, ignore_errors=True)
         cmd = ["rocprofv3", "--pmc"] + have + ["--output-format", "csv", "-d", d, "-o", "p", "--", "python3", os.path.join(ROOT, "bench.py"),
-               "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra
+               "--full", "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra
         with open(os.path.join(outdir, name + ".bench.json"), "w") as fo, open(os.path.join(outdir, name + ".err"), "w") as fe:
             rc = subprocess.call(cmd, env=env, stdout=fo, stderr=fe, cwd="/tmp")
         if rc:

@@ -57,7 +57,7 @@ def collect(workload, outdir, steps):
         d = os.path.join(outdir, name)
         shutil.rmtree(d, ignore_errors=True)
         cmd = ["rocprofv3"] + flags + ["--output-format", "csv", "-d", d, "-o", "p", "--", "python3", os.path.join(ROOT, "bench.py"),
-               "--workload", workload, "--steps", str(steps if name == "trace" else 2), "--warmup", "1", "--no-cpu-baseline"] + lanes
+               "--full", "--workload", workload, "--steps", str(steps if name == "trace" else 2), "--warmup", "1", "--no-cpu-baseline"] + lanes
         print("+", " ".join(cmd), flush=True)
         with open(os.path.join(outdir, name + ".bench.json"), "w") as fo, open(os.path.join(outdir, name + ".err"), "w") as fe:
             rc = subprocess.call(cmd, env=env, stdout=fo, stderr=fe, cwd="/tmp")
