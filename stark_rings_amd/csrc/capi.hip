@@ -68,6 +68,50 @@ struct Prof {
     }
 };
 
+// The kernel path of a context, chosen once by sr_ctx_create_ex (after init_pow2: GL_FAST needs the tuned tables built)
+enum Path {
+    FROG,           // the reference's own rings (frog_ring.hpp, small_rings.hpp)
+    SMALL_G24,
+    SMALL_B72,
+    RT_BABYBEAR,    // register-tiled (ntt_regtile.hpp), 2^12 <= D <= 2^24
+    RT_GOLDILOCKS,  // the same for Goldilocks under SR_PLAN_GL_REGTILE (a cross-check)
+    GL_FAST,        // tuned Goldilocks (ntt_goldilocks.hpp), 2^8 <= D <= 2^22
+    STARK_TUNED,    // Stark, k >= 4: the register-tiled kernels of ntt_stark.hpp on StarkL (SR_PLAN_STARK_GENERIC_ON_LAZY: STARK_LAZY)
+    STARK_LAZY,     // Stark: the generic kernels on StarkL (nine 28-bit limbs, lazy carries; stark_lazy.hpp)
+    GENERIC         // the generic kernels (ntt_generic.hpp) on the ring's own field
+};
+// Stark transforms and sums of products run on StarkL (SR_PLAN_STARK_NO_LAZY and D = 1: on sr::Stark)
+bool on_stark_lazy(Path p) { return p == STARK_TUNED || p == STARK_LAZY; }
+
+// The context's device buffers, each grow-only (grow() below).  The host-pointer temporaries and the pipeline stages are never
+// live in the same call, so they share the HOST_* slots.
+enum Buf {
+    OPERAND_A,     // operand scratch: the column-stage image of b in a fused ring product (every path), the packed intermediates of the
+    OPERAND_B,     // register-tiled path; a two-lane plan carves four chunk buffers out of OPERAND_A (on_lanes)
+    WIDE_A,        // the widened operands of packed-u32 calls below D = 4096 (packed_via_wide)
+    WIDE_B,
+    MATVEC_PARTS,  // the row parts of a short-and-wide small-ring mat-vec
+    FOLD_0,        // the partial elements of sr_sum_batch_dev / sr_product_batch_dev; FOLD_0 also holds the small rings' product tree
+    FOLD_1,
+    HOST_0,        // the host-pointer calls: device copies of their operands and results; the staging buffers of host_pipeline
+    HOST_1,        // (HOST_0, HOST_1: a / out and b of its first lane; HOST_2, HOST_3 of its second lane)
+    HOST_2,
+    HOST_3,
+    HOST_4,
+    ELEMENT,       // the one element of sr_mul_elem_batch (written by a blocking copy: no other call uses it)
+    N_BUFS
+};
+// graph: a captured graph can hold the buffer (a _dev call may use it), so it may not move once a capture has been seen
+// (sr_ctx::scratch_frozen).  The others are used only by host-pointer calls, which hold the context's mutex and synchronise before they
+// return.
+constexpr struct {
+    const char *name;
+    bool graph;
+} kBufs[N_BUFS] = {{"OPERAND_A", true}, {"OPERAND_B", true}, {"WIDE_A", true}, {"WIDE_B", true}, {"MATVEC_PARTS", true},
+                   {"FOLD_0", true},    {"FOLD_1", true},    {"HOST_0", false}, {"HOST_1", false}, {"HOST_2", false},
+                   {"HOST_3", false},   {"HOST_4", false},   {"ELEMENT", false}};
+static_assert(kBufs[N_BUFS - 1].name != nullptr, "one kBufs entry per buffer");
+
 }  // namespace
 
 struct sr_ctx {
@@ -77,26 +121,21 @@ struct sr_ctx {
     int limbs = 1;      // u64 limbs per coefficient
     int device = 0;
     int log_tile = 12;
-    bool fast_goldilocks = true;
-    bool regtile = false;   // BabyBear (and, for cross-checks, Goldilocks with SR_GOLDILOCKS_REGTILE=1): ntt_regtile.hpp
+    Path path = GENERIC;
     sr::rt::Hooks rt_hooks{};
     sr_plan plan{};         // fixed at creation (sr_ctx_create_ex); the library reads no environment variable
-    void *rt_scratch[2] = {nullptr, nullptr};   // operand scratch: [0] column-stage image of b in a fused ring product (every
-                                                // path); [0], [1] packed intermediates of the register-tiled path
-    size_t rt_scratch_bytes[2] = {0, 0};
-    // the scratch is shared by every call on this context: a call on another stream first waits for the previous user
-    hipEvent_t rt_scratch_free = nullptr;
-    hipStream_t rt_scratch_stream = nullptr;
-    bool rt_scratch_used = false;
+    void *buf[N_BUFS] = {};
+    size_t buf_bytes[N_BUFS] = {};
+    // the graph-held buffers are shared by every call on this context: a call on another stream first waits for the previous user
+    hipEvent_t scratch_free = nullptr;
+    hipStream_t scratch_stream = nullptr;
+    bool scratch_used = false;
     void *tables = nullptr;  // [tw (D elems) | itw (D elems)] in table form
     size_t table_bytes = 0;
     // inverse stage-0 constants (table form): plain inverse, and fused ring-mul (with boundary correction)
     unsigned char inv_scale0[40], inv_scale1[40], mul_scale0[40], mul_scale1[40];
     bool stark_one_tile = false;  // the ring element is one tile of st::tile_kernel (D <= 2048 unless SR_ST_WHOLE_MAX says otherwise)
-    bool stark_tuned = false;  // and k >= 4: the register-tiled kernels of ntt_stark.hpp (SR_STARK_TUNED=0: generic kernels on StarkL)
-    bool stark_lazy = false;  // Stark rings: transforms run on StarkL (nine 28-bit limbs, lazy carries; stark_lazy.hpp)
-    // staging for host-pointer entry points
-    sr::GlLanes gl_lanes;  // tuned Goldilocks ring product on two internal streams (streams and events created on first use)
+    sr::GlLanes gl_lanes;  // the two-lane plans (tuned Goldilocks, register-tiled) on two internal streams (events created on first use)
     // sr_plan.lanes = 0 (auto): the plan the context settled on -- 0 undecided, 1 one stream, 2 two lanes -- measured ONCE on this
     // process's actual stream-to-hardware-queue mapping (lanes_autoselect); lanes_probe_ms = what the two plans took ([0] two lanes,
     // [1] one stream; 0 = not measured).  probe_chunk != 0 only while the probe runs: the one-stream plan's chunk for that run.
@@ -105,17 +144,10 @@ struct sr_ctx {
     size_t lanes_probe_elems = 0;
     size_t probe_chunk = 0;
     bool probing = false;
-    static constexpr int kTmpSlots = 10;
-    void *host_tmp[kTmpSlots] = {};         // device temporaries of the host-pointer linear-algebra / decomposition calls (grow-only,
-    size_t host_tmp_bytes[kTmpSlots] = {};  // see DevBuf); [5], [6]: the widened operands of packed-u32 calls below D = 4096, [7]: the
-                                            // row parts of a short-and-wide small-ring mat-vec, [8], [9]: the partial elements of
-                                            // sr_sum_batch_dev / sr_product_batch_dev (DevBufLite)
-    // A _dev call has been seen on a stream under capture: a captured graph holds the scratch pointers of this context, so they may
+    // A _dev call has been seen on a stream under capture: a captured graph holds the graph-held buffers of this context, so they may
     // no longer move -- from then on only sr_ctx_reserve_scratch (explicit, blocking, documented to invalidate earlier graphs) grows
-    // a buffer; an asynchronous call that would have to fails with SR_E_INVALID instead of freeing memory a graph still writes to.
+    // one; an asynchronous call that would have to fails with SR_E_INVALID instead of freeing memory a graph still writes to.
     bool scratch_frozen = false;
-    void *stage[4] = {nullptr, nullptr, nullptr, nullptr};  // [2], [3]: second lane of the chunked host pipeline
-    size_t stage_bytes[4] = {0, 0, 0, 0};
     hipStream_t stream = nullptr;
     hipStream_t out_stream = nullptr;  // device-to-host copies of the chunked host pipeline
     unsigned long long *d_counter = nullptr;
@@ -255,13 +287,13 @@ typename F::elem pow_small(typename F::elem x, uint64_t e) {
 }
 
 template <class F>
-int init_pow2(sr_ctx *c) {
+int init_pow2(sr_ctx *c, bool stark_tuned = false) {
     using E = typename F::elem;
     const int k = c->k;
     if (k > F::kTwoAdicity - 1) return fail(SR_E_INVALID, "log2_degree exceeds the field's 2-adicity");
     c->log_tile = default_log_tile<F>();
     if (c->plan.log_tile >= 8 && c->plan.log_tile <= 12) c->log_tile = c->plan.log_tile;  // tuning knob of the generic kernels
-    if (k > 2 * c->log_tile && !c->stark_tuned) return fail(SR_E_INVALID, "log2_degree too large for the two-level kernels");
+    if (k > 2 * c->log_tile && !stark_tuned) return fail(SR_E_INVALID, "log2_degree too large for the two-level kernels");
     const size_t d = c->degree;
     size_t extra = 0;
     if constexpr (std::is_same<F, sr::Goldilocks>::value) extra = sr::gl_fast_extra_bytes(k);
@@ -469,10 +501,6 @@ int matmul_dev(sr_ctx *c, uint64_t *y, const uint64_t *a, const uint64_t *b, siz
     HIP_TRY(hipGetLastError());
     return SR_OK;
 }
-// operand scratch (defined below): grow-only device buffers owned by the context, ordered between streams by an event.  st = the
-// stream of the call that needs it (the null stream is a caller's stream like any other); reserving = the call is
-// sr_ctx_reserve_scratch, the one place that may grow a buffer after a capture has been seen.
-int ensure_scratch(sr_ctx *c, int n_buffers, size_t bytes, hipStream_t st, bool reserving = false);
 // remembers that a call arrived on a capturing stream (sr_ctx::scratch_frozen); true while `st` is being captured
 bool note_capture(sr_ctx *c, hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -483,15 +511,35 @@ bool note_capture(sr_ctx *c, hipStream_t st) {
     (void)hipGetLastError();
     return false;
 }
-int frozen_fail() {
-    return fail(SR_E_INVALID, "context scratch would have to grow, but a stream capture has used it (a captured graph holds its address): "
-                              "call sr_ctx_reserve_scratch for the largest batch BEFORE capturing (include/stark_rings_hip.h)");
+// Grows buffer b of the context to at least `bytes` (0 counts as 8, so that a temporary is never null); nothing is allocated or freed
+// once warm.  st = the stream of the call that needs it (the null stream is a caller's stream like any other); reserving = the call is
+// sr_ctx_reserve_scratch, the one place that may grow a graph-held buffer after a capture has been seen.  A hipMalloc here is why the
+// very first call of a given size is not graph-capturable.
+int grow(sr_ctx *c, Buf b, size_t bytes, hipStream_t st = nullptr, bool reserving = false) {
+    if (bytes == 0) bytes = 8;
+    const bool capturing = kBufs[b].graph && !reserving && note_capture(c, st);
+    if (c->buf_bytes[b] >= bytes) return SR_OK;
+    if (capturing || (kBufs[b].graph && !reserving && c->scratch_frozen))
+        return fail(SR_E_INVALID, std::string("context buffer ") + kBufs[b].name +
+                                      " would have to grow, but a stream capture has used it (a captured graph holds its address): call "
+                                      "sr_ctx_reserve_scratch for the largest batch BEFORE capturing (include/stark_rings_hip.h)");
+    if (c->buf[b]) {
+        HIP_TRY(hipDeviceSynchronize());  // a _dev call on another stream may still be using the smaller buffer
+        HIP_TRY(hipFree(c->buf[b]));
+        c->buf[b] = nullptr;
+        c->buf_bytes[b] = 0;
+    }
+    hipError_t e = hipMalloc(&c->buf[b], bytes);
+    if (e != hipSuccess) {
+        c->buf[b] = nullptr;
+        return fail(SR_E_ALLOC, std::string("hipMalloc ") + kBufs[b].name + ": " + hipGetErrorString(e));
+    }
+    c->buf_bytes[b] = bytes;
+    return SR_OK;
 }
-int rt_scratch_acquire(sr_ctx *c, hipStream_t st);
-int rt_scratch_release(sr_ctx *c, hipStream_t st);
-// One use of the shared operand scratch by a call on stream st.  The release (an event recorded on st, which the next user on another
-// stream waits for) happens on EVERY exit path once acquire() succeeded -- also after a failed launch, when earlier launches of the
-// same call may still be using the scratch.
+// One use of the graph-held buffers by a call on stream st (callers hold the context's mutex, so the bookkeeping itself is serialised).
+// The release (an event recorded on st, which the next user on another stream waits for) happens on EVERY exit path once acquire()
+// succeeded -- also after a failed launch, when earlier launches of the same call may still be using the buffers.
 struct ScratchUse {
     sr_ctx *c;
     hipStream_t st;
@@ -499,41 +547,21 @@ struct ScratchUse {
     ScratchUse(sr_ctx *ctx, hipStream_t s) : c(ctx), st(s) {}
     int acquire() {
         note_capture(c, st);
-        const int rc = rt_scratch_acquire(c, st);
-        held = rc == SR_OK;
-        return rc;
+        if (!c->scratch_free) HIP_TRY(hipEventCreateWithFlags(&c->scratch_free, hipEventDisableTiming));
+        if (c->scratch_used && c->scratch_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->scratch_free, 0));
+        held = true;
+        return SR_OK;
     }
     int release() {
         held = false;
-        return rt_scratch_release(c, st);
+        if (!c->scratch_free) HIP_TRY(hipEventCreateWithFlags(&c->scratch_free, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->scratch_free, st));
+        c->scratch_stream = st;
+        c->scratch_used = true;
+        return SR_OK;
     }
     ~ScratchUse() {
-        if (held) (void)rt_scratch_release(c, st);
-    }
-};
-// device temporary in slot `slot` of the context's grow-only set (see DevBuf below; this one is usable from the internal helpers)
-struct DevBufLite {
-    sr_ctx *c;
-    int slot;
-    void *p = nullptr;
-    DevBufLite(sr_ctx *c_, int slot_) : c(c_), slot(slot_) {}
-    int alloc(size_t bytes, hipStream_t st = nullptr, bool reserving = false) {
-        if (bytes == 0) bytes = 8;
-        const bool capturing = !reserving && note_capture(c, st);
-        if (c->host_tmp_bytes[slot] < bytes) {
-            if (capturing || (!reserving && c->scratch_frozen)) return frozen_fail();
-            if (c->host_tmp[slot]) {
-                HIP_TRY(hipDeviceSynchronize());  // a _dev call on another stream may still be using the smaller buffer
-                (void)hipFree(c->host_tmp[slot]);
-                c->host_tmp[slot] = nullptr;
-                c->host_tmp_bytes[slot] = 0;
-            }
-            hipError_t e = hipMalloc(&c->host_tmp[slot], bytes);
-            if (e != hipSuccess) return fail(SR_E_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
-            c->host_tmp_bytes[slot] = bytes;
-        }
-        p = c->host_tmp[slot];
-        return SR_OK;
+        if (held) (void)release();
     }
 };
 // ring elements of elem_bytes each the operand scratch may hold for a batch (plan cap; at least one element)
@@ -544,9 +572,6 @@ size_t scratch_polys(const sr_ctx *c, size_t batch, size_t elem_bytes) {
     if (c->plan.chunk_polys && n > c->plan.chunk_polys) n = c->plan.chunk_polys;
     return n < batch ? n : batch;
 }
-// tuned Goldilocks path: a large batch runs as eight chunks of launches (unless the plan fixes chunk_polys) -- measured on config 2:
-// 18.6 ms as one set of launches, 18.27 / 18.3 / 18.5 ms in chunks of 2048 / 4096 / 1024 ring elements (the inverse column pass
-// finds part of the rows kernel's output still in the Infinity Cache), and the operand scratch is an eighth of the batch
 // lanes the context runs its chunked products on: the plan's explicit choice, else what the probe settled on (two until it has run)
 int effective_lanes(const sr_ctx *c) { return c->plan.lanes ? (int)c->plan.lanes : (c->lanes_choice ? c->lanes_choice : 2); }
 // Small batches are the other regime: a set of launches over fewer elements than one lane chunk (64 MiB of coefficients) no longer fills
@@ -557,6 +582,9 @@ size_t lane_chunk_default(const sr_ctx *c, size_t elem_bytes) {
     const size_t n = ((size_t)64 << 20) / elem_bytes;
     return n ? n : 1;
 }
+// tuned Goldilocks path: a large batch runs as eight chunks of launches (unless the plan fixes chunk_polys) -- measured on config 2:
+// 18.6 ms as one set of launches, 18.27 / 18.3 / 18.5 ms in chunks of 2048 / 4096 / 1024 ring elements (the inverse column pass
+// finds part of the rows kernel's output still in the Infinity Cache), and the operand scratch is an eighth of the batch
 size_t gl_chunk_polys(const sr_ctx *c, size_t batch) {
     if (c->probe_chunk) return c->probe_chunk < batch ? c->probe_chunk : batch;  // the probe times ONE set of launches of the real chunk size
     size_t chunk = scratch_polys(c, batch, (size_t)8 << c->k);
@@ -564,12 +592,13 @@ size_t gl_chunk_polys(const sr_ctx *c, size_t batch) {
     if (!c->plan.chunk_polys && eighth >= lane_chunk_default(c, (size_t)8 << c->k) && chunk > eighth) chunk = eighth;
     return chunk;
 }
-// Two-lane plan of the tuned Goldilocks product (sr::gl_fast_ring_mul_lanes): chunk of a lane in ring elements -- 64 MiB of
-// coefficients per scratch buffer by default, so that the four buffers of the two lanes are the 256 MiB of the Infinity Cache --
-// capped by the plan's scratch limit (four buffers) and by sr_plan.chunk_polys when set.  Taken when the plan allows lanes
-// (sr_plan.lanes != 1), the column passes are cols256 launches and the batch has enough such chunks for the lanes to pay (lanes_pay).
-size_t gl_lane_chunk(const sr_ctx *c) {
-    const size_t elem = (size_t)8 << c->k;
+// bytes of one ring element in the scratch of the two-lane plans: packed words on the register-tiled BabyBear path, else 8-byte words
+size_t lane_elem_bytes(const sr_ctx *c) { return (size_t)(c->path == RT_BABYBEAR ? 4 : 8) << c->k; }
+// Two-lane plans of the tuned Goldilocks product (cols256) and of the register-tiled path: chunk of a lane in ring elements -- 64 MiB
+// of words per scratch buffer by default, so that the four buffers of the two lanes are the 256 MiB of the Infinity Cache -- capped by
+// the plan's scratch limit (four buffers) and by sr_plan.chunk_polys when set.
+size_t lane_chunk(const sr_ctx *c) {
+    const size_t elem = lane_elem_bytes(c);
     size_t chunk = c->plan.chunk_polys ? (size_t)c->plan.chunk_polys : (((size_t)64 << 20) / elem);
     const size_t cap = c->plan.scratch_limit_bytes ? (size_t)c->plan.scratch_limit_bytes : ((size_t)16 << 30);
     if (chunk > cap / (4 * elem)) chunk = cap / (4 * elem);
@@ -583,17 +612,19 @@ size_t gl_lane_chunk(const sr_ctx *c) {
 bool lanes_pay(const sr_ctx *c, size_t batch, size_t lane_chunk) {
     return c->plan.chunk_polys ? batch > lane_chunk : 2 * batch >= 7 * lane_chunk;
 }
-bool gl_use_lanes(const sr_ctx *c, size_t batch) {
-    return effective_lanes(c) != 1 && c->k > 12 && c->gl_fast.cols256 && lanes_pay(c, batch, gl_lane_chunk(c));
-}
 // The stand-alone transforms (two launches per chunk, in place) need more chunks before the lanes pay: at four chunks one set of
 // launches on the caller's stream is a quarter faster (512 Goldilocks elements of degree 2^16: 0.169 against 0.222 ms; 32 of degree
 // 2^20: 0.210 against 0.268; 1 024 BabyBear: 0.251 against 0.294), at eight the two are level (tools/bench_small_transforms.py).
 bool lanes_pay_transform(const sr_ctx *c, size_t batch, size_t lane_chunk) {
     return c->plan.chunk_polys ? batch > lane_chunk : batch >= 8 * lane_chunk;
 }
-bool gl_use_lanes_transform(const sr_ctx *c, size_t batch) {
-    return effective_lanes(c) != 1 && c->k > 12 && c->gl_fast.cols256 && lanes_pay_transform(c, batch, gl_lane_chunk(c));
+// A call of the tuned Goldilocks path (cols256 plans only) or of the register-tiled path takes the lanes when the plan allows them
+// (sr_plan.lanes != 1), the batch has enough chunks for them to pay, and the call is not on the lanes themselves: the host-pointer
+// pipeline drives the device calls on the very streams the lanes are (and is bound by PCIe anyway).
+bool use_lanes(const sr_ctx *c, size_t batch, hipStream_t st, bool transform) {
+    if (effective_lanes(c) == 1 || c->k <= 12 || st == c->stream || st == c->out_stream) return false;
+    if (c->path == GL_FAST && !c->gl_fast.cols256) return false;
+    return transform ? lanes_pay_transform(c, batch, lane_chunk(c)) : lanes_pay(c, batch, lane_chunk(c));
 }
 int gl_lanes_init(sr_ctx *c) {
     sr::GlLanes &L = c->gl_lanes;
@@ -611,6 +642,22 @@ int gl_lanes_init(sr_ctx *c) {
     L.n = 2;
     return SR_OK;
 }
+// A batch on the two lanes with per-lane scratch: lane i gets buffers 2i and 2i + 1 of four chunk-sized buffers in OPERAND_A, and
+// body(first, n, s0, s1, lane stream) enqueues the launches of elements [first, first + n).  `what`: the error of a failed launch.
+template <class Body>
+int on_lanes(sr_ctx *c, size_t batch, hipStream_t st, const char *what, Body body) {
+    const size_t chunk = lane_chunk(c), bytes = chunk * lane_elem_bytes(c);
+    if (int rc = grow(c, OPERAND_A, 4 * bytes, st)) return rc;
+    if (int rc = gl_lanes_init(c)) return rc;
+    ScratchUse su(c, st);
+    if (int rc = su.acquire()) return rc;
+    char *base = static_cast<char *>(c->buf[OPERAND_A]);
+    const int rc = sr::for_each_lane_chunk(c->gl_lanes, batch, chunk, st, [&](int i, size_t first, size_t n, hipStream_t lane) {
+        return body(first, n, (void *)(base + (size_t)(2 * i) * bytes), (void *)(base + (size_t)(2 * i + 1) * bytes), lane);
+    });
+    if (int r2 = su.release()) return r2;
+    return rc ? fail(SR_E_HIP, what) : SR_OK;
+}
 template <class F>
 int ring_mul_dev(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch, hipStream_t st) {
     using S = typename F::storage;
@@ -626,10 +673,10 @@ int ring_mul_dev(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b,
         // neither operand is written (coeff_form.rs:250-258); batches beyond the scratch cap run in chunks
         const size_t elem = sizeof(S) << c->k;
         const size_t chunk = scratch_polys(c, batch, elem);
-        if (int rc = ensure_scratch(c, 1, chunk * elem, st)) return rc;
+        if (int rc = grow(c, OPERAND_A, chunk * elem, st)) return rc;
         ScratchUse su(c, st);
         if (int rc = su.acquire()) return rc;
-        S *sb = reinterpret_cast<S *>(c->rt_scratch[0]);
+        S *sb = reinterpret_cast<S *>(c->buf[OPERAND_A]);
         for (size_t e = 0; e < batch; e += chunk) {
             const size_t n = batch - e < chunk ? batch - e : chunk;
             S *o = reinterpret_cast<S *>(out) + (e << c->k);
@@ -700,100 +747,6 @@ sr::rt::Params<F> make_rt_params(const sr_ctx *c, bool fused) {
     p.no_cols256 = (c->plan.flags & SR_PLAN_RT_NO_COLS256) != 0;
     return p;
 }
-// grow-only scratch for packed intermediates (allocated on first use; a hipMalloc here is why the very first
-// call of a given size is not graph-capturable)
-int ensure_scratch(sr_ctx *c, int n_buffers, size_t bytes, hipStream_t st, bool reserving) {
-    const bool capturing = !reserving && note_capture(c, st);
-    for (int i = 0; i < n_buffers; i++) {
-        if (c->rt_scratch_bytes[i] >= bytes) continue;
-        if (capturing || (!reserving && c->scratch_frozen)) return frozen_fail();
-        HIP_TRY(hipDeviceSynchronize());
-        if (c->rt_scratch[i]) HIP_TRY(hipFree(c->rt_scratch[i]));
-        c->rt_scratch[i] = nullptr;
-        c->rt_scratch_bytes[i] = 0;
-        hipError_t e = hipMalloc(&c->rt_scratch[i], bytes);
-        if (e != hipSuccess) return fail(SR_E_ALLOC, std::string("hipMalloc scratch: ") + hipGetErrorString(e));
-        c->rt_scratch_bytes[i] = bytes;
-    }
-    return SR_OK;
-}
-// stream ordering of the shared scratch (callers hold the context's mutex, so the bookkeeping itself is serialised)
-int rt_ensure_scratch(sr_ctx *c, int n_buffers, size_t bytes, hipStream_t st) {
-    if (c->k <= 12) return SR_OK;
-    return ensure_scratch(c, n_buffers, bytes, st);
-}
-int rt_scratch_acquire(sr_ctx *c, hipStream_t st) {
-    if (!c->rt_scratch_free) HIP_TRY(hipEventCreateWithFlags(&c->rt_scratch_free, hipEventDisableTiming));
-    if (c->rt_scratch_used && c->rt_scratch_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->rt_scratch_free, 0));
-    return SR_OK;
-}
-int rt_scratch_release(sr_ctx *c, hipStream_t st) {
-    if (!c->rt_scratch_free) HIP_TRY(hipEventCreateWithFlags(&c->rt_scratch_free, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->rt_scratch_free, st));
-    c->rt_scratch_stream = st;
-    c->rt_scratch_used = true;
-    return SR_OK;
-}
-template <class F> size_t rt_lane_chunk(const sr_ctx *c);
-template <class F> bool rt_use_lanes(const sr_ctx *c, size_t batch, hipStream_t st);
-template <class F> bool rt_use_lanes_transform(const sr_ctx *c, size_t batch, hipStream_t st);
-int gl_lanes_init(sr_ctx *c);
-// stand-alone transform in chunks on the context's two streams, each lane with its own packed scratch (the two-lane plan of
-// rt_ring_mul below; the scratch has the product's size, so one allocation serves both)
-template <class F, int DIR, class VB = sr::rt::Boundary>
-int rt_transform_lanes(sr_ctx *c, void *d, size_t batch, hipStream_t st) {
-    using E = typename F::elem;
-    using S = typename sr::rt::View<F, VB>::T;
-    const size_t chunk = rt_lane_chunk<F>(c), words = chunk << c->k;
-    if (int rc = ensure_scratch(c, 1, 4 * words * sizeof(E), st)) return rc;
-    if (int rc = gl_lanes_init(c)) return rc;
-    ScratchUse su(c, st);
-    if (int rc = su.acquire()) return rc;
-    sr::GlLanes &L = c->gl_lanes;
-    E *base = reinterpret_cast<E *>(c->rt_scratch[0]);
-    HIP_TRY(hipEventRecord(L.fork, st));  // (nothing is in flight on the lanes yet if one of these three fails)
-    for (int i = 0; i < 2; i++) HIP_TRY(hipStreamWaitEvent(L.st[i], L.fork, 0));
-    int rc = 0;
-    size_t ci = 0;
-    for (size_t e = 0; e < batch && !rc; e += chunk, ci++) {
-        const int i = (int)(ci & 1);
-        const size_t n = batch - e < chunk ? batch - e : chunk;
-        S *dc = reinterpret_cast<S *>(d) + (e << c->k);
-        rc = DIR == 0 ? sr::rt::fwd<F, VB>(c->rt_hooks, dc, n, make_rt_params<F>(c, false), base + (size_t)(2 * i) * words, L.st[i])
-                      : sr::rt::inv<F, VB>(c->rt_hooks, dc, n, make_rt_params<F>(c, false), base + (size_t)(2 * i) * words, L.st[i]);
-    }
-    for (int i = 0; i < 2; i++) {  // join even after a failed launch
-        if (hipEventRecord(L.join[i], L.st[i]) != hipSuccess) rc = 1;
-        if (hipStreamWaitEvent(st, L.join[i], 0) != hipSuccess) rc = 1;
-    }
-    if (int r2 = su.release()) return r2;
-    return rc ? fail(SR_E_HIP, "register-tiled launch failed") : SR_OK;
-}
-// VB: the view of the caller's words -- sr::rt::Boundary (the reference's 8-byte limbs) or sr::rt::PackedStream (the packed-u32 entry points)
-template <class F, class VB = sr::rt::Boundary>
-int rt_fwd(sr_ctx *c, void *d, size_t batch, hipStream_t st) {
-    using E = typename F::elem;
-    if (rt_use_lanes_transform<F>(c, batch, st)) return rt_transform_lanes<F, 0, VB>(c, d, batch, st);
-    if (int rc = rt_ensure_scratch(c, 1, (batch << c->k) * sizeof(E), st)) return rc;
-    ScratchUse su(c, st);
-    if (int rc = su.acquire()) return rc;
-    if (sr::rt::fwd<F, VB>(c->rt_hooks, reinterpret_cast<typename sr::rt::View<F, VB>::T *>(d), batch, make_rt_params<F>(c, false),
-                           (E *)c->rt_scratch[0], st))
-        return fail(SR_E_HIP, "register-tiled launch failed");
-    return su.release();
-}
-template <class F, class VB = sr::rt::Boundary>
-int rt_inv(sr_ctx *c, void *d, size_t batch, hipStream_t st) {
-    using E = typename F::elem;
-    if (rt_use_lanes_transform<F>(c, batch, st)) return rt_transform_lanes<F, 1, VB>(c, d, batch, st);
-    if (int rc = rt_ensure_scratch(c, 1, (batch << c->k) * sizeof(E), st)) return rc;
-    ScratchUse su(c, st);
-    if (int rc = su.acquire()) return rc;
-    if (sr::rt::inv<F, VB>(c->rt_hooks, reinterpret_cast<typename sr::rt::View<F, VB>::T *>(d), batch, make_rt_params<F>(c, false),
-                           (E *)c->rt_scratch[0], st))
-        return fail(SR_E_HIP, "register-tiled launch failed");
-    return su.release();
-}
 // a large batch runs as eight chunks of launches (unless the plan fixes chunk_polys), like the tuned Goldilocks path: measured on
 // config 3 (BabyBear D = 2^16, batch 2^14): 11.68 ms as one set of launches, 11.38 / 11.41 / 11.56 ms in chunks of 2048 / 4096 / 1024
 // ring elements, 12.4 ms and worse below 512 -- and the packed scratch is an eighth of the batch
@@ -801,70 +754,52 @@ size_t rt_chunk_polys(const sr_ctx *c, size_t batch) {
     if (c->probe_chunk) return c->probe_chunk < batch ? c->probe_chunk : batch;
     if (c->plan.chunk_polys) return c->plan.chunk_polys < batch ? c->plan.chunk_polys : batch;
     const size_t eighth = (batch + 7) / 8;   // never below one lane chunk of packed words (see gl_chunk_polys): 128 BabyBear elements of
-    return eighth >= lane_chunk_default(c, (size_t)(c->ring == SR_RING_BABYBEAR_POW2 ? 4 : 8) << c->k) ? eighth : batch;   // degree 2^16 took 0.196 ms in eight chunks, 0.095 as one
+    return eighth >= lane_chunk_default(c, lane_elem_bytes(c)) ? eighth : batch;   // degree 2^16 took 0.196 ms in eight chunks, 0.095 as one
 }
-// two-lane plan of the register-tiled product, as for the tuned Goldilocks path (gl_lane_chunk / gl_fast_ring_mul_lanes): chunks of
-// 64 MiB of packed words per scratch buffer on the context's two streams, each lane with its own pair of packed buffers
-template <class F>
-size_t rt_lane_chunk(const sr_ctx *c) {
-    const size_t elem = sizeof(typename F::elem) << c->k;
-    size_t chunk = c->plan.chunk_polys ? (size_t)c->plan.chunk_polys : (((size_t)64 << 20) / elem);
-    const size_t cap = c->plan.scratch_limit_bytes ? (size_t)c->plan.scratch_limit_bytes : ((size_t)16 << 30);
-    if (chunk > cap / (4 * elem)) chunk = cap / (4 * elem);
-    return chunk ? chunk : 1;
-}
-template <class F>
-bool rt_use_lanes(const sr_ctx *c, size_t batch, hipStream_t st) {
-    return effective_lanes(c) != 1 && c->k > 12 && lanes_pay(c, batch, rt_lane_chunk<F>(c)) && st != c->stream && st != c->out_stream;
-}
-template <class F>
-bool rt_use_lanes_transform(const sr_ctx *c, size_t batch, hipStream_t st) {
-    return effective_lanes(c) != 1 && c->k > 12 && lanes_pay_transform(c, batch, rt_lane_chunk<F>(c)) && st != c->stream && st != c->out_stream;
+// VB: the view of the caller's words -- sr::rt::Boundary (the reference's 8-byte limbs) or sr::rt::PackedStream (the packed-u32 entry
+// points).  DIR 0 forward, 1 inverse.
+template <class F, int DIR, class VB = sr::rt::Boundary>
+int rt_transform(sr_ctx *c, void *d, size_t batch, hipStream_t st) {
+    using E = typename F::elem;
+    using S = typename sr::rt::View<F, VB>::T;
+    const auto p = make_rt_params<F>(c, false);
+    auto run = [&](S *dc, size_t n, void *scratch, hipStream_t s) {
+        return DIR == 0 ? sr::rt::fwd<F, VB>(c->rt_hooks, dc, n, p, (E *)scratch, s) : sr::rt::inv<F, VB>(c->rt_hooks, dc, n, p, (E *)scratch, s);
+    };
+    // chunks on the two lanes, each with its own packed scratch (the product's: one allocation serves both)
+    if (use_lanes(c, batch, st, true))
+        return on_lanes(c, batch, st, "register-tiled launch failed", [&](size_t first, size_t n, void *s0, void *, hipStream_t lane) {
+            return run(reinterpret_cast<S *>(d) + (first << c->k), n, s0, lane);
+        });
+    if (c->k > 12 && batch)
+        if (int rc = grow(c, OPERAND_A, (batch << c->k) * sizeof(E), st)) return rc;
+    ScratchUse su(c, st);
+    if (int rc = su.acquire()) return rc;
+    if (run(reinterpret_cast<S *>(d), batch, c->buf[OPERAND_A], st)) return fail(SR_E_HIP, "register-tiled launch failed");
+    return su.release();
 }
 template <class F, class VB = sr::rt::Boundary>
 int rt_ring_mul(sr_ctx *c, void *out, const void *a, const void *b, size_t batch, hipStream_t st) {
     using S = typename sr::rt::View<F, VB>::T;
     using E = typename F::elem;
     if (batch == 0) return SR_OK;
-    if (rt_use_lanes<F>(c, batch, st)) {
-        const size_t chunk = rt_lane_chunk<F>(c), words = chunk << c->k;
-        if (int rc = ensure_scratch(c, 1, 4 * words * sizeof(E), st)) return rc;
-        if (int rc = gl_lanes_init(c)) return rc;
-        ScratchUse su(c, st);
-        if (int rc = su.acquire()) return rc;
-        sr::GlLanes &L = c->gl_lanes;
-        E *base = reinterpret_cast<E *>(c->rt_scratch[0]);
-        HIP_TRY(hipEventRecord(L.fork, st));  // (nothing is in flight on the lanes yet if one of these three fails)
-        for (int i = 0; i < 2; i++) HIP_TRY(hipStreamWaitEvent(L.st[i], L.fork, 0));
-        int rc = 0;
-        size_t ci = 0;
-        for (size_t e = 0; e < batch && !rc; e += chunk, ci++) {
-            const int i = (int)(ci & 1);
-            const size_t n = batch - e < chunk ? batch - e : chunk;
-            const size_t off = e << c->k;
-            rc = sr::rt::ring_mul<F, VB>(c->rt_hooks, reinterpret_cast<S *>(out) + off, reinterpret_cast<const S *>(a) + off,
-                                         reinterpret_cast<const S *>(b) + off, n, make_rt_params<F>(c, true), base + (size_t)(2 * i) * words,
-                                         base + (size_t)(2 * i + 1) * words, L.st[i]);
-        }
-        for (int i = 0; i < 2; i++) {  // join even after a failed launch
-            if (hipEventRecord(L.join[i], L.st[i]) != hipSuccess) rc = 1;
-            if (hipStreamWaitEvent(st, L.join[i], 0) != hipSuccess) rc = 1;
-        }
-        if (int r2 = su.release()) return r2;
-        return rc ? fail(SR_E_HIP, "register-tiled launch failed") : SR_OK;
-    }
+    const auto p = make_rt_params<F>(c, true);
+    auto run = [&](size_t first, size_t n, void *s0, void *s1, hipStream_t s) {
+        const size_t off = first << c->k;
+        return sr::rt::ring_mul<F, VB>(c->rt_hooks, reinterpret_cast<S *>(out) + off, reinterpret_cast<const S *>(a) + off,
+                                       reinterpret_cast<const S *>(b) + off, n, p, (E *)s0, (E *)s1, s);
+    };
+    if (use_lanes(c, batch, st, false)) return on_lanes(c, batch, st, "register-tiled launch failed", run);
     const size_t chunk = c->k > 12 ? rt_chunk_polys(c, batch) : batch;
-    if (int rc = rt_ensure_scratch(c, 2, (chunk << c->k) * sizeof(E), st)) return rc;
+    if (c->k > 12) {
+        if (int rc = grow(c, OPERAND_A, (chunk << c->k) * sizeof(E), st)) return rc;
+        if (int rc = grow(c, OPERAND_B, (chunk << c->k) * sizeof(E), st)) return rc;
+    }
     ScratchUse su(c, st);
     if (int rc = su.acquire()) return rc;
-    for (size_t e = 0; e < batch; e += chunk) {
-        const size_t n = batch - e < chunk ? batch - e : chunk;
-        const size_t off = e << c->k;
-        if (sr::rt::ring_mul<F, VB>(c->rt_hooks, reinterpret_cast<S *>(out) + off, reinterpret_cast<const S *>(a) + off,
-                                    reinterpret_cast<const S *>(b) + off, n, make_rt_params<F>(c, true), (E *)c->rt_scratch[0],
-                                    (E *)c->rt_scratch[1], st))
+    for (size_t e = 0; e < batch; e += chunk)
+        if (run(e, batch - e < chunk ? batch - e : chunk, c->buf[OPERAND_A], c->buf[OPERAND_B], st))
             return fail(SR_E_HIP, "register-tiled launch failed");
-    }
     return su.release();
 }
 
@@ -905,10 +840,10 @@ int st_ring_mul(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, 
     // strided stages of both operands first: a's go straight to out, b's into the operand scratch (neither is written)
     const size_t elem = sizeof(S) << c->k;
     const size_t chunk = scratch_polys(c, batch, elem);
-    if (int rc = ensure_scratch(c, 1, chunk * elem, st)) return rc;
+    if (int rc = grow(c, OPERAND_A, chunk * elem, st)) return rc;
     ScratchUse su(c, st);
     if (int rc = su.acquire()) return rc;
-    S *sb = reinterpret_cast<S *>(c->rt_scratch[0]);
+    S *sb = reinterpret_cast<S *>(c->buf[OPERAND_A]);
     auto hook_f = [&](bool begin) { begin ? gl_prof_begin(c, 0, st) : gl_prof_end(c, st); };
     auto hook_i = [&](bool begin) { begin ? gl_prof_begin(c, 2, st) : gl_prof_end(c, st); };
     for (size_t e = 0; e < batch; e += chunk) {
@@ -1087,17 +1022,6 @@ int dev_recompose_any(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t lo,
     return hi ? dev_recompose_wide(c, out, in, lo, hi, k, batch_out, st) : dev_recompose(c, out, in, lo, k, batch_out, st);
 }
 
-int ensure_stage(sr_ctx *c, int which, size_t bytes) {
-    if (c->stage_bytes[which] >= bytes) return SR_OK;
-    if (c->stage[which]) HIP_TRY(hipFree(c->stage[which]));
-    c->stage[which] = nullptr;
-    c->stage_bytes[which] = 0;
-    hipError_t e = hipMalloc(&c->stage[which], bytes);
-    if (e != hipSuccess) return fail(SR_E_ALLOC, std::string("hipMalloc staging: ") + hipGetErrorString(e));
-    c->stage_bytes[which] = bytes;
-    return SR_OK;
-}
-
 int check(sr_ctx *c, const void *p0, const void *p1 = (const void *)1, const void *p2 = (const void *)1) {
     if (!c) return fail(SR_E_INVALID, "null context");
     if (!p0 || !p1 || !p2) return fail(SR_E_INVALID, "null buffer");
@@ -1113,58 +1037,65 @@ int check_count(const sr_ctx *c, size_t n_elems, size_t per_elem = 1) {
 
 // ---- per-ring device dispatch (pow2 rings and the reference-native small rings) --------------
 int lanes_autoselect(sr_ctx *c, size_t batch);  // sr_plan.lanes = 0: measure once which plan this process's queues favour (below)
+// one launch on the reference's own rings (frog_ring.hpp, small_rings.hpp): op = sr::FROG_CRT .. sr::FROG_REDUCE, numbered like the
+// SMALL_G24_* and SMALL_B72_* operations
+static_assert(sr::SMALL_G24_REDUCE - sr::SMALL_G24_CRT == sr::FROG_REDUCE && sr::SMALL_B72_REDUCE - sr::SMALL_B72_CRT == sr::FROG_REDUCE,
+              "small-ring operations numbered alike");
+int small_ring_launch(sr_ctx *c, int op, const uint64_t *a, const uint64_t *b, size_t in_len, uint64_t *out, size_t batch, hipStream_t st) {
+    if (c->path == FROG) return sr::frog_launch(c->frog, op, a, b, in_len, out, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
+    const int first = c->path == SMALL_G24 ? sr::SMALL_G24_CRT : sr::SMALL_B72_CRT;
+    return sr::small_launch(c->small, first + op, a, b, in_len, out, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
+}
+// the tuned Goldilocks transforms: in chunks on the two lanes (in place: no scratch, no ScratchUse), else one set of launches
+template <int DIR>
+int gl_transform(sr_ctx *c, uint64_t *d, size_t batch, hipStream_t st) {
+    int rc;
+    if (use_lanes(c, batch, st, true)) {
+        if (int r = gl_lanes_init(c)) return r;
+        rc = sr::for_each_lane_chunk(c->gl_lanes, batch, lane_chunk(c), st, [&](int, size_t first, size_t n, hipStream_t lane) {
+            return sr::gl_fast_transform_chunk<DIR>(c->gl_fast, d + (first << c->k), n, lane);
+        });
+    } else {
+        rc = DIR == 0 ? sr::gl_fast_fwd(c->gl_fast, d, batch, st) : sr::gl_fast_inv(c->gl_fast, d, batch, st);
+    }
+    return rc ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
+}
 int dev_fwd(sr_ctx *c, uint64_t *d, size_t batch, hipStream_t st) {
-    if (c->ring == SR_RING_FROG_16) return sr::frog_launch(c->frog, sr::FROG_CRT, d, nullptr, 0, d, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_GOLDILOCKS_24) return sr::small_launch(c->small, sr::SMALL_G24_CRT, d, nullptr, 0, d, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_BABYBEAR_72) return sr::small_launch(c->small, sr::SMALL_B72_CRT, d, nullptr, 0, d, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    if (c->regtile) {
-        if (c->ring == SR_RING_BABYBEAR_POW2) return rt_fwd<sr::BabyBear>(c, d, batch, st);
-        return rt_fwd<sr::Goldilocks>(c, d, batch, st);
+    switch (c->path) {
+        case FROG: case SMALL_G24: case SMALL_B72: return small_ring_launch(c, sr::FROG_CRT, d, nullptr, 0, d, batch, st);
+        case RT_BABYBEAR: return rt_transform<sr::BabyBear, 0>(c, d, batch, st);
+        case RT_GOLDILOCKS: return rt_transform<sr::Goldilocks, 0>(c, d, batch, st);
+        case GL_FAST: return gl_transform<0>(c, d, batch, st);
+        case STARK_TUNED: return st_fwd(c, d, batch, st);
+        case STARK_LAZY: return fwd_dev<sr::StarkL>(c, d, batch, st);
+        default: DISPATCH_POW2(c, (fwd_dev<F>(c, d, batch, st)));
     }
-    if (c->ring == SR_RING_GOLDILOCKS_POW2 && c->fast_goldilocks && sr::gl_fast_supported(c->gl_fast)) {
-        if (gl_use_lanes_transform(c, batch) && st != c->stream && st != c->out_stream) {  // chunks on the two lanes, in place (no scratch)
-            if (int rc = gl_lanes_init(c)) return rc;
-            c->gl_lanes.chunk = gl_lane_chunk(c);
-            return sr::gl_fast_transform_lanes<0>(c->gl_fast, d, c->gl_lanes, batch, st) ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
-        }
-        return sr::gl_fast_fwd(c->gl_fast, d, batch, st) ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
-    }
-    if (c->stark_tuned) return st_fwd(c, d, batch, st);
-    if (c->stark_lazy) return fwd_dev<sr::StarkL>(c, d, batch, st);
-    DISPATCH_POW2(c, (fwd_dev<F>(c, d, batch, st)));
 }
 int dev_inv(sr_ctx *c, uint64_t *d, size_t batch, hipStream_t st) {
-    if (c->ring == SR_RING_FROG_16) return sr::frog_launch(c->frog, sr::FROG_ICRT, d, nullptr, 0, d, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_GOLDILOCKS_24) return sr::small_launch(c->small, sr::SMALL_G24_ICRT, d, nullptr, 0, d, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_BABYBEAR_72) return sr::small_launch(c->small, sr::SMALL_B72_ICRT, d, nullptr, 0, d, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    if (c->regtile) {
-        if (c->ring == SR_RING_BABYBEAR_POW2) return rt_inv<sr::BabyBear>(c, d, batch, st);
-        return rt_inv<sr::Goldilocks>(c, d, batch, st);
+    switch (c->path) {
+        case FROG: case SMALL_G24: case SMALL_B72: return small_ring_launch(c, sr::FROG_ICRT, d, nullptr, 0, d, batch, st);
+        case RT_BABYBEAR: return rt_transform<sr::BabyBear, 1>(c, d, batch, st);
+        case RT_GOLDILOCKS: return rt_transform<sr::Goldilocks, 1>(c, d, batch, st);
+        case GL_FAST: return gl_transform<1>(c, d, batch, st);
+        case STARK_TUNED: return st_inv(c, d, batch, st);
+        case STARK_LAZY: return inv_dev<sr::StarkL>(c, d, batch, st);
+        default: DISPATCH_POW2(c, (inv_dev<F>(c, d, batch, st)));
     }
-    if (c->ring == SR_RING_GOLDILOCKS_POW2 && c->fast_goldilocks && sr::gl_fast_supported(c->gl_fast)) {
-        if (gl_use_lanes_transform(c, batch) && st != c->stream && st != c->out_stream) {
-            if (int rc = gl_lanes_init(c)) return rc;
-            c->gl_lanes.chunk = gl_lane_chunk(c);
-            return sr::gl_fast_transform_lanes<1>(c->gl_fast, d, c->gl_lanes, batch, st) ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
-        }
-        return sr::gl_fast_inv(c->gl_fast, d, batch, st) ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
-    }
-    if (c->stark_tuned) return st_inv(c, d, batch, st);
-    if (c->stark_lazy) return inv_dev<sr::StarkL>(c, d, batch, st);
-    DISPATCH_POW2(c, (inv_dev<F>(c, d, batch, st)));
 }
 int dev_pointwise(sr_ctx *c, uint64_t *l, const uint64_t *r, size_t batch, hipStream_t st) {
-    if (c->ring == SR_RING_FROG_16) return sr::frog_launch(c->frog, sr::FROG_MUL, l, r, 0, l, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_GOLDILOCKS_24) return sr::small_launch(c->small, sr::SMALL_G24_MUL, l, r, 0, l, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_BABYBEAR_72) return sr::small_launch(c->small, sr::SMALL_B72_MUL, l, r, 0, l, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    DISPATCH_POW2(c, (pointwise_dev<F>(c, l, r, batch << c->k, st)));
+    switch (c->path) {
+        case FROG: case SMALL_G24: case SMALL_B72: return small_ring_launch(c, sr::FROG_MUL, l, r, 0, l, batch, st);
+        default: DISPATCH_POW2(c, (pointwise_dev<F>(c, l, r, batch << c->k, st)));
+    }
 }
 // every element of the batch *= ONE ring element r, slot-wise (CRT / NTT form): Matrix<R> *= &R, SparseMatrix<R> *= &R
 int dev_mul_elem(sr_ctx *c, uint64_t *l, const uint64_t *r, size_t batch, hipStream_t st) {
-    if (c->ring == SR_RING_FROG_16) return sr::frog_launch(c->frog, sr::FROG_MULB, l, r, 0, l, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_GOLDILOCKS_24 || c->ring == SR_RING_BABYBEAR_72)
-        return sr::small_launch_mul_bcast(c->small, c->ring == SR_RING_BABYBEAR_72, l, r, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    DISPATCH_POW2(c, (pointwise_bcast_dev<F>(c, l, r, batch << c->k, st)));
+    switch (c->path) {
+        case FROG: return sr::frog_launch(c->frog, sr::FROG_MULB, l, r, 0, l, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
+        case SMALL_G24: case SMALL_B72:
+            return sr::small_launch_mul_bcast(c->small, c->path == SMALL_B72, l, r, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
+        default: DISPATCH_POW2(c, (pointwise_bcast_dev<F>(c, l, r, batch << c->k, st)));
+    }
 }
 int dev_addsub(sr_ctx *c, uint64_t *l, const uint64_t *r, size_t batch, bool sub, hipStream_t st) {
     const size_t n = batch * c->degree;
@@ -1261,7 +1192,6 @@ template <class F, bool MUL>
 int fold_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, hipStream_t st) {
     using S = typename F::storage;
     const size_t w = c->degree;  // storage words (coefficients) per ring element
-    DevBufLite t0(c, 8), t1(c, 9);
     ScratchUse su(c, st);
     const S *src = reinterpret_cast<const S *>(in);
     bool tmp_used = false;
@@ -1270,13 +1200,13 @@ int fold_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, hipStream_t
         const size_t r = fold_parts(n, w);
         S *dst = reinterpret_cast<S *>(out);
         if (r > 1) {
-            DevBufLite &t = flip ? t1 : t0;
-            if (int rc = t.alloc(fold_tmp_words(w) * sizeof(S), st)) return rc;
+            const Buf t = flip ? FOLD_1 : FOLD_0;
+            if (int rc = grow(c, t, fold_tmp_words(w) * sizeof(S), st)) return rc;
             if (!tmp_used) {
                 if (int rc = su.acquire()) return rc;
                 tmp_used = true;
             }
-            dst = reinterpret_cast<S *>(t.p);
+            dst = reinterpret_cast<S *>(c->buf[t]);
             flip ^= 1;
         }
         const size_t lanes = r * w;
@@ -1300,12 +1230,6 @@ void mont_one_image(uint64_t out[4]) {
     memcpy(out, &s, sizeof(s));
 }
 }  // extern "C++"
-// out = l (.) r slot-wise, out of place, for the three reference-native rings (their slot-product kernels take an output pointer)
-int small_slot_mul_to(sr_ctx *c, uint64_t *out, const uint64_t *l, const uint64_t *r, size_t batch, hipStream_t st) {
-    if (c->ring == SR_RING_FROG_16) return sr::frog_launch(c->frog, sr::FROG_MUL, l, r, 0, out, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
-    const int op = c->ring == SR_RING_GOLDILOCKS_24 ? sr::SMALL_G24_MUL : sr::SMALL_B72_MUL;
-    return sr::small_launch(c->small, op, l, r, 0, out, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-}
 // n == 0: zero() / one() (one(): component 0 of every slot is the base field's 1)
 int fold_empty(sr_ctx *c, uint64_t *out, bool mul, hipStream_t st) {
     const size_t bytes = c->degree * c->limbs * 8;
@@ -1337,14 +1261,13 @@ int dev_product(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, hipStrea
         return SR_OK;
     }
     size_t h = n / 2, m = n - h;
-    DevBufLite t(c, 8);
-    if (int rc = t.alloc(m * bytes, st)) return rc;
+    if (int rc = grow(c, FOLD_0, m * bytes, st)) return rc;
     ScratchUse su(c, st);
     if (int rc = su.acquire()) return rc;
-    uint64_t *tmp = (uint64_t *)t.p;
+    uint64_t *tmp = (uint64_t *)c->buf[FOLD_0];
     {
         ProfScope ps(c, st, K_POINTWISE);
-        if (int rc = small_slot_mul_to(c, tmp, in, in + m * w, h, st)) return rc;
+        if (int rc = small_ring_launch(c, sr::FROG_MUL, in, in + m * w, 0, tmp, h, st)) return rc;
     }
     if (m > h) HIP_TRY(hipMemcpyAsync(tmp + h * w, in + h * w, bytes, hipMemcpyDeviceToDevice, st));
     n = m;
@@ -1352,7 +1275,7 @@ int dev_product(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, hipStrea
         h = n / 2;
         m = n - h;
         ProfScope ps(c, st, K_POINTWISE);
-        if (int rc = small_slot_mul_to(c, tmp, tmp, tmp + m * w, h, st)) return rc;
+        if (int rc = small_ring_launch(c, sr::FROG_MUL, tmp, tmp + m * w, 0, tmp, h, st)) return rc;
         n = m;
     }
     HIP_TRY(hipMemcpyAsync(out, tmp, bytes, hipMemcpyDeviceToDevice, st));
@@ -1371,7 +1294,7 @@ int dev_spmv(sr_ctx *c, uint64_t *y, const uint64_t *vals, const uint32_t *cols,
         ProfScope ps(c, st, K_OTHER);
         DISPATCH_SLOT(c, (sr::slot_spmv<SL>(K, y, vals, cols, row_ptr, v, nrows, ncols, c->d_counter + 1, st)));
     }
-    if (c->stark_lazy) return spmv_dev<sr::StarkL>(c, y, vals, cols, row_ptr, v, nrows, ncols, st);  // sums of products on 28-bit lazy limbs (stark_lazy.hpp)
+    if (on_stark_lazy(c->path)) return spmv_dev<sr::StarkL>(c, y, vals, cols, row_ptr, v, nrows, ncols, st);  // sums of products on 28-bit lazy limbs (stark_lazy.hpp)
     DISPATCH_POW2(c, (spmv_dev<F>(c, y, vals, cols, row_ptr, v, nrows, ncols, st)));
 }
 int dev_matmul(sr_ctx *c, uint64_t *y, const uint64_t *a, const uint64_t *b, size_t n, size_t m, size_t p, hipStream_t st) {
@@ -1379,7 +1302,7 @@ int dev_matmul(sr_ctx *c, uint64_t *y, const uint64_t *a, const uint64_t *b, siz
         ProfScope ps(c, st, K_OTHER);
         DISPATCH_SLOT(c, (sr::slot_matmul<SL>(K, y, a, b, n, m, p, st)));
     }
-    if (c->stark_lazy) return matmul_dev<sr::StarkL>(c, y, a, b, n, m, p, st);  // sums of products on 28-bit lazy limbs (stark_lazy.hpp)
+    if (on_stark_lazy(c->path)) return matmul_dev<sr::StarkL>(c, y, a, b, n, m, p, st);  // sums of products on 28-bit lazy limbs (stark_lazy.hpp)
     DISPATCH_POW2(c, (matmul_dev<F>(c, y, a, b, n, m, p, st)));
 }
 int dev_matvec(sr_ctx *c, uint64_t *y, const uint64_t *m, const uint64_t *v, size_t nrows, size_t ncols, hipStream_t st) {
@@ -1393,14 +1316,13 @@ int dev_matvec(sr_ctx *c, uint64_t *y, const uint64_t *m, const uint64_t *v, siz
         // operand scratch (an event recorded at release, awaited by the next user on another stream)
         ScratchUse su(c, st);
         if (nsplit > 1) {
-            DevBufLite pb(c, 7);
-            if (int rc = pb.alloc(nrows * nsplit * c->degree * 8, st)) return rc;
-            part = (uint64_t *)pb.p;
+            if (int rc = grow(c, MATVEC_PARTS, nrows * nsplit * c->degree * 8, st)) return rc;
+            part = (uint64_t *)c->buf[MATVEC_PARTS];
             if (int rc = su.acquire()) return rc;
         }
         DISPATCH_SLOT(c, (sr::slot_matvec<SL>(K, y, m, v, nrows, ncols, part, nsplit, st)));
     }
-    if (c->stark_lazy) return matvec_dev<sr::StarkL>(c, y, m, v, nrows, ncols, st);  // sums of products on 28-bit lazy limbs (stark_lazy.hpp)
+    if (on_stark_lazy(c->path)) return matvec_dev<sr::StarkL>(c, y, m, v, nrows, ncols, st);  // sums of products on 28-bit lazy limbs (stark_lazy.hpp)
     DISPATCH_POW2(c, (matvec_dev<F>(c, y, m, v, nrows, ncols, st)));
 }
 // ---- plan selection: sr_plan.lanes = 0 means "measure once, keep the winner" ------------------------------------------------
@@ -1419,19 +1341,17 @@ int dev_matvec(sr_ctx *c, uint64_t *y, const uint64_t *m, const uint64_t *v, siz
 //   reserves runs two lanes, unmeasured -- an asynchronous _dev call never probes (it may be under stream capture, and its latency
 //   belongs to the caller).  sr_ctx_plan_in_use reports the outcome.
 int dev_ring_mul(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch, hipStream_t st);
-size_t lanes_chunk_of(const sr_ctx *c) {
-    if (c->regtile) return c->ring == SR_RING_BABYBEAR_POW2 ? rt_lane_chunk<sr::BabyBear>(c) : rt_lane_chunk<sr::Goldilocks>(c);
-    return gl_lane_chunk(c);
-}
 bool lanes_candidate(const sr_ctx *c, size_t batch) {
-    if (!is_pow2_ring(c->ring) || c->k <= 12) return false;
-    const bool gl = c->ring == SR_RING_GOLDILOCKS_POW2 && !c->regtile && c->fast_goldilocks && sr::gl_fast_supported(c->gl_fast) && c->gl_fast.cols256;
-    if (!gl && !c->regtile) return false;
-    return batch > lanes_chunk_of(c);
+    switch (c->path) {
+        case RT_BABYBEAR: case RT_GOLDILOCKS: break;
+        case GL_FAST: if (c->gl_fast.cols256) break; return false;
+        default: return false;
+    }
+    return c->k > 12 && batch > lane_chunk(c);
 }
 int lanes_autoselect(sr_ctx *c, size_t batch) {
     if (c->plan.lanes || c->lanes_choice || c->probing || !lanes_candidate(c, batch)) return SR_OK;
-    const size_t chunk = lanes_chunk_of(c);
+    const size_t chunk = lane_chunk(c);
     if (batch < 8 * chunk) return SR_OK;  // too small for a steady state: two lanes, unmeasured (effective_lanes)
     // up to 32 chunks per call (2 GiB per buffer)
     size_t nch = batch / chunk;
@@ -1473,7 +1393,7 @@ int lanes_autoselect(sr_ctx *c, size_t batch) {
             c->lanes_choice = plan == 0 ? 2 : 1;
             c->probe_chunk = 0;
             if (plan == 1) {  // one stream: sets of launches of the size the REAL batch will run in (an eighth of it by default)
-                const size_t real = c->regtile ? rt_chunk_polys(c, batch) : gl_chunk_polys(c, batch);
+                const size_t real = c->path == GL_FAST ? gl_chunk_polys(c, batch) : rt_chunk_polys(c, batch);
                 c->probe_chunk = real < n ? real : n;
             }
             double warm = 0;
@@ -1490,12 +1410,12 @@ int lanes_autoselect(sr_ctx *c, size_t batch) {
         if (e) (void)hipEventDestroy(e);
     if (st) (void)hipStreamDestroy(st);
     // the probe sized the operand scratch for ITS one-stream run: drop it, the plan that won allocates what it needs
-    for (int i = 0; i < 2; i++) {
-        if (c->rt_scratch[i]) (void)hipFree(c->rt_scratch[i]);
-        c->rt_scratch[i] = nullptr;
-        c->rt_scratch_bytes[i] = 0;
+    for (Buf b : {OPERAND_A, OPERAND_B}) {
+        if (c->buf[b]) (void)hipFree(c->buf[b]);
+        c->buf[b] = nullptr;
+        c->buf_bytes[b] = 0;
     }
-    c->rt_scratch_used = false;
+    c->scratch_used = false;
     c->probe_chunk = 0;
     c->probing = false;
     c->prof.on = prof_was;
@@ -1513,72 +1433,47 @@ int lanes_autoselect(sr_ctx *c, size_t batch) {
     return SR_OK;
 }
 
+// the tuned Goldilocks product: chunks on two internal streams, intermediates in per-lane scratch pairs; else one stream, b's column
+// stages through the operand scratch
+int gl_ring_mul(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch, hipStream_t st) {
+    if (use_lanes(c, batch, st, false))
+        return on_lanes(c, batch, st, "goldilocks fast-path launch failed", [&](size_t first, size_t n, void *sa, void *sb, hipStream_t lane) {
+            const size_t off = first << c->k;
+            return sr::gl_fast_ring_mul_chunk(c->gl_fast, out + off, a + off, b + off, (uint64_t *)sa, (uint64_t *)sb, n, lane);
+        });
+    uint64_t *scratch = nullptr;
+    size_t chunk = 0;
+    ScratchUse su(c, st);
+    if (c->k > 12 && batch) {
+        chunk = gl_chunk_polys(c, batch);
+        if (int rc = grow(c, OPERAND_A, chunk * ((size_t)8 << c->k), st)) return rc;
+        if (int rc = su.acquire()) return rc;
+        scratch = reinterpret_cast<uint64_t *>(c->buf[OPERAND_A]);
+    }
+    if (sr::gl_fast_ring_mul(c->gl_fast, out, a, b, scratch, chunk, batch, st)) return fail(SR_E_HIP, "goldilocks fast-path launch failed");
+    return scratch ? su.release() : SR_OK;
+}
 int dev_ring_mul(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch, hipStream_t st) {
-    if (c->ring == SR_RING_FROG_16) return sr::frog_launch(c->frog, sr::FROG_RINGMUL, a, b, 0, out, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_GOLDILOCKS_24) return sr::small_launch(c->small, sr::SMALL_G24_RINGMUL, a, b, 0, out, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    if (c->ring == SR_RING_BABYBEAR_72) return sr::small_launch(c->small, sr::SMALL_B72_RINGMUL, a, b, 0, out, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    if (c->regtile) {
-        if (c->ring == SR_RING_BABYBEAR_POW2) return rt_ring_mul<sr::BabyBear>(c, out, a, b, batch, st);
-        return rt_ring_mul<sr::Goldilocks>(c, out, a, b, batch, st);
+    switch (c->path) {
+        case FROG: case SMALL_G24: case SMALL_B72: return small_ring_launch(c, sr::FROG_RINGMUL, a, b, 0, out, batch, st);
+        case RT_BABYBEAR: return rt_ring_mul<sr::BabyBear>(c, out, a, b, batch, st);
+        case RT_GOLDILOCKS: return rt_ring_mul<sr::Goldilocks>(c, out, a, b, batch, st);
+        case GL_FAST: return gl_ring_mul(c, out, a, b, batch, st);
+        case STARK_TUNED: return st_ring_mul(c, out, a, b, batch, st);
+        case STARK_LAZY: return ring_mul_dev<sr::StarkL>(c, out, a, b, batch, st);
+        default: DISPATCH_POW2(c, (ring_mul_dev<F>(c, out, a, b, batch, st)));
     }
-    if (c->ring == SR_RING_GOLDILOCKS_POW2 && c->fast_goldilocks && sr::gl_fast_supported(c->gl_fast)) {
-        // chunks on two internal streams, intermediates in per-lane scratch pairs (not for the host-pointer pipeline, which
-        // drives this function on the very streams the lanes are and is bound by PCIe anyway)
-        if (gl_use_lanes(c, batch) && st != c->stream && st != c->out_stream) {
-            const size_t chunk = gl_lane_chunk(c), words = chunk << c->k;
-            if (int rc = ensure_scratch(c, 1, 4 * words * 8, st)) return rc;
-            if (int rc = gl_lanes_init(c)) return rc;
-            ScratchUse su(c, st);
-            if (int rc = su.acquire()) return rc;
-            sr::GlLanes &L = c->gl_lanes;
-            uint64_t *base = reinterpret_cast<uint64_t *>(c->rt_scratch[0]);
-            L.chunk = chunk;
-            for (int i = 0; i < 2; i++) {
-                L.sa[i] = base + (size_t)(2 * i) * words;
-                L.sb[i] = base + (size_t)(2 * i + 1) * words;
-            }
-            const int rc = sr::gl_fast_ring_mul_lanes(c->gl_fast, out, a, b, L, batch, st);  // joins the lanes itself, also on failure
-            if (int r2 = su.release()) return r2;
-            return rc ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
-        }
-        uint64_t *scratch = nullptr;
-        size_t chunk = 0;
-        ScratchUse su(c, st);
-        if (c->k > 12 && batch) {  // b's column stages go through the operand scratch
-            chunk = gl_chunk_polys(c, batch);
-            if (int rc = ensure_scratch(c, 1, chunk * ((size_t)8 << c->k), st)) return rc;
-            if (int rc = su.acquire()) return rc;
-            scratch = reinterpret_cast<uint64_t *>(c->rt_scratch[0]);
-        }
-        if (sr::gl_fast_ring_mul(c->gl_fast, out, a, b, scratch, chunk, batch, st)) return fail(SR_E_HIP, "goldilocks fast-path launch failed");
-        return scratch ? su.release() : SR_OK;
-    }
-    if (c->stark_tuned) return st_ring_mul(c, out, a, b, batch, st);
-    if (c->stark_lazy) return ring_mul_dev<sr::StarkL>(c, out, a, b, batch, st);
-    DISPATCH_POW2(c, (ring_mul_dev<F>(c, out, a, b, batch, st)));
 }
 // out = icrt(crt(a) (.) b_ntt): forward transform, slot product and inverse transform on out, one after the other (the
-// Goldilocks tuned path fuses them: gl_fast_ring_mul_rhs)
+// Goldilocks tuned path fuses them: gl_fast_ring_mul_rhs, on the lanes gl_fast_ring_mul_rhs_chunk)
 int dev_ring_mul_ntt_rhs(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b_ntt, size_t batch, hipStream_t st) {
     if (batch == 0) return SR_OK;
-    if (c->ring == SR_RING_GOLDILOCKS_POW2 && !c->regtile && c->fast_goldilocks && sr::gl_fast_supported(c->gl_fast) && c->k >= 8) {
-        if (gl_use_lanes(c, batch) && st != c->stream && st != c->out_stream) {  // as dev_ring_mul: chunks on the two lanes
-            const size_t chunk = gl_lane_chunk(c), words = chunk << c->k;
-            if (int rc = ensure_scratch(c, 1, 4 * words * 8, st)) return rc;
-            if (int rc = gl_lanes_init(c)) return rc;
-            ScratchUse su(c, st);
-            if (int rc = su.acquire()) return rc;
-            sr::GlLanes &L = c->gl_lanes;
-            uint64_t *base = reinterpret_cast<uint64_t *>(c->rt_scratch[0]);
-            L.chunk = chunk;
-            for (int i = 0; i < 2; i++) {
-                L.sa[i] = base + (size_t)(2 * i) * words;
-                L.sb[i] = base + (size_t)(2 * i + 1) * words;
-            }
-            const int rc = sr::gl_fast_ring_mul_rhs_lanes(c->gl_fast, out, a, b_ntt, L, batch, st);
-            if (int r2 = su.release()) return r2;
-            return rc ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
-        }
+    if (c->path == GL_FAST) {
+        if (use_lanes(c, batch, st, false))
+            return on_lanes(c, batch, st, "goldilocks fast-path launch failed", [&](size_t first, size_t n, void *sa, void *, hipStream_t lane) {
+                const size_t off = first << c->k;
+                return sr::gl_fast_ring_mul_rhs_chunk(c->gl_fast, out + off, a + off, b_ntt + off, (uint64_t *)sa, n, lane);
+            });
         return sr::gl_fast_ring_mul_rhs(c->gl_fast, out, a, b_ntt, batch, st) ? fail(SR_E_HIP, "goldilocks fast-path launch failed") : SR_OK;
     }
     if (out != a) HIP_TRY(hipMemcpyAsync(out, a, batch * c->degree * c->limbs * 8, hipMemcpyDeviceToDevice, st));
@@ -1587,16 +1482,12 @@ int dev_ring_mul_ntt_rhs(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint
     return dev_inv(c, out, batch, st);
 }
 int dev_reduce(sr_ctx *c, const uint64_t *in, size_t in_len, uint64_t *out, size_t batch, hipStream_t st) {
-    if (c->ring == SR_RING_FROG_16) {
-        if (in_len > 2 * c->degree) return fail(SR_E_INVALID, "reduce: in_len_per_elem > 2D");
-        return sr::frog_launch(c->frog, sr::FROG_REDUCE, in, nullptr, in_len, out, batch, st) ? fail(SR_E_HIP, "frog-ring launch failed") : SR_OK;
+    switch (c->path) {
+        case FROG: case SMALL_G24: case SMALL_B72:
+            if (in_len > 2 * c->degree) return fail(SR_E_INVALID, "reduce: in_len_per_elem > 2D");
+            return small_ring_launch(c, sr::FROG_REDUCE, in, nullptr, in_len, out, batch, st);
+        default: DISPATCH_POW2(c, (reduce_dev<F>(c, in, in_len, out, batch, st)));
     }
-    if (c->ring == SR_RING_GOLDILOCKS_24 || c->ring == SR_RING_BABYBEAR_72) {
-        if (in_len > 2 * c->degree) return fail(SR_E_INVALID, "reduce: in_len_per_elem > 2D");
-        int op = c->ring == SR_RING_GOLDILOCKS_24 ? sr::SMALL_G24_REDUCE : sr::SMALL_B72_REDUCE;
-        return sr::small_launch(c->small, op, in, nullptr, in_len, out, batch, st) ? fail(SR_E_HIP, "small-ring launch failed") : SR_OK;
-    }
-    DISPATCH_POW2(c, (reduce_dev<F>(c, in, in_len, out, batch, st)));
 }
 
 }  // namespace
@@ -1646,41 +1537,48 @@ int sr_ctx_create_ex(int ring, int log2_degree, int device, const sr_plan *plan,
     if (hipMalloc(&c->d_counter, 4 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_ALLOC, "hipMalloc counter failed"));
     if (hipMemset(c->d_counter, 0, 4 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_HIP, "hipMemset counter failed"));
     if (is_pow2_ring(ring)) {
-        c->k = log2_degree;
-        c->degree = (size_t)1 << log2_degree;
+        const int k = log2_degree;
+        c->k = k;
+        c->degree = (size_t)1 << k;
         c->limbs = ring == SR_RING_STARK_POW2 ? 4 : 1;
+        // SR_PLAN_STARK_NO_LAZY keeps the Stark transforms on the 8 x 32-bit-limb arithmetic (differential tests); D = 1 has none
+        const bool stark_lazy = ring == SR_RING_STARK_POW2 && !(pf & SR_PLAN_STARK_NO_LAZY) && k >= 1;
+        const bool stark_tuned = stark_lazy && !(pf & (SR_PLAN_STARK_GENERIC_ON_LAZY | SR_PLAN_GENERIC_KERNELS)) && sr::st::supported(k);
+        const bool regtile = k >= 12 && k <= 24;
         switch (ring) {
-            case SR_RING_GOLDILOCKS_POW2: rc = init_pow2<sr::Goldilocks>(c); break;
-            case SR_RING_BABYBEAR_POW2: rc = init_pow2<sr::BabyBear>(c); break;
-            default: {
-                // SR_PLAN_STARK_NO_LAZY keeps the transforms on the 8 x 32-bit-limb arithmetic (differential tests); D = 1 has none
-                c->stark_lazy = !(pf & SR_PLAN_STARK_NO_LAZY) && log2_degree >= 1;
-                c->stark_tuned = c->stark_lazy && !(pf & (SR_PLAN_STARK_GENERIC_ON_LAZY | SR_PLAN_GENERIC_KERNELS)) && sr::st::supported(log2_degree);
-                c->stark_one_tile = sr::st::whole(log2_degree, sr::st::whole_max(c->plan.stark_whole_max));
-                rc = c->stark_lazy ? init_pow2<sr::StarkL>(c) : init_pow2<sr::Stark>(c);
+            case SR_RING_GOLDILOCKS_POW2:
+                c->gl_fast.prof_user = c;
+                c->gl_fast.prof_begin = gl_prof_begin;
+                c->gl_fast.prof_end = gl_prof_end;
+                rc = init_pow2<sr::Goldilocks>(c);
                 break;
-            }
+            case SR_RING_BABYBEAR_POW2: rc = init_pow2<sr::BabyBear>(c); break;
+            default:
+                c->stark_one_tile = sr::st::whole(k, sr::st::whole_max(c->plan.stark_whole_max));
+                rc = stark_lazy ? init_pow2<sr::StarkL>(c, stark_tuned) : init_pow2<sr::Stark>(c);
+                break;
         }
         if (rc) return bail(rc);
-        if (ring == SR_RING_GOLDILOCKS_POW2) {
-            c->fast_goldilocks = !(pf & SR_PLAN_GENERIC_KERNELS);
-            c->gl_fast.prof_user = c;
-            c->gl_fast.prof_begin = gl_prof_begin;
-            c->gl_fast.prof_end = gl_prof_end;
-            c->regtile = (pf & SR_PLAN_GL_REGTILE) && c->k >= 12 && c->k <= 24;
-        }
-        if (ring == SR_RING_BABYBEAR_POW2) {
-            c->regtile = !(pf & SR_PLAN_GENERIC_KERNELS) && c->k >= 12 && c->k <= 24;
+        switch (ring) {
+            case SR_RING_GOLDILOCKS_POW2:
+                c->path = (pf & SR_PLAN_GL_REGTILE) && regtile ? RT_GOLDILOCKS
+                          : !(pf & SR_PLAN_GENERIC_KERNELS) && sr::gl_fast_supported(c->gl_fast) ? GL_FAST
+                                                                                                 : GENERIC;
+                break;
+            case SR_RING_BABYBEAR_POW2: c->path = !(pf & SR_PLAN_GENERIC_KERNELS) && regtile ? RT_BABYBEAR : GENERIC; break;
+            default: c->path = stark_tuned ? STARK_TUNED : stark_lazy ? STARK_LAZY : GENERIC; break;
         }
         c->rt_hooks.user = c;
         c->rt_hooks.begin = gl_prof_begin;
         c->rt_hooks.end = gl_prof_end;
     } else if (ring == SR_RING_FROG_16) {
+        c->path = FROG;
         c->k = 0;
         c->degree = 16;
         c->limbs = 1;
         sr::frog_init(c->frog);
     } else {
+        c->path = ring == SR_RING_GOLDILOCKS_24 ? SMALL_G24 : SMALL_B72;
         c->k = 0;
         c->degree = ring == SR_RING_GOLDILOCKS_24 ? 24 : 72;
         c->limbs = 1;
@@ -1701,14 +1599,10 @@ int sr_ctx_destroy(sr_ctx *c) {
     sr::gl_fast_destroy(c->gl_fast);
     sr::small_destroy(c->small);
     if (c->tables) (void)hipFree(c->tables);
-    for (int i = 0; i < 4; i++)
-        if (c->stage[i]) (void)hipFree(c->stage[i]);
-    for (int i = 0; i < 2; i++)
-        if (c->rt_scratch[i]) (void)hipFree(c->rt_scratch[i]);
+    for (void *p : c->buf)
+        if (p) (void)hipFree(p);
     if (c->out_stream) (void)hipStreamDestroy(c->out_stream);
-    if (c->rt_scratch_free) (void)hipEventDestroy(c->rt_scratch_free);
-    for (int i = 0; i < sr_ctx::kTmpSlots; i++)
-        if (c->host_tmp[i]) (void)hipFree(c->host_tmp[i]);
+    if (c->scratch_free) (void)hipEventDestroy(c->scratch_free);
     if (c->gl_lanes.n) {
         for (int i = 0; i < 2; i++)
             if (c->gl_lanes.join[i]) (void)hipEventDestroy(c->gl_lanes.join[i]);  // the streams are the context's own
@@ -1917,11 +1811,11 @@ int sr_rot_batch(sr_ctx *c, uint64_t *data, size_t batch) {
     DeviceGuard g(c->device);
     const size_t bytes = batch * c->degree * c->limbs * 8;
     if (bytes == 0) return SR_OK;
-    if (int rc = ensure_stage(c, 0, bytes)) return rc;
-    if (int rc = ensure_stage(c, 1, bytes)) return rc;
-    HIP_TRY(hipMemcpyAsync(c->stage[0], data, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_rot(c, (uint64_t *)c->stage[1], (const uint64_t *)c->stage[0], batch, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(data, c->stage[1], bytes, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = grow(c, HOST_0, bytes)) return rc;
+    if (int rc = grow(c, HOST_1, bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], data, bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_rot(c, (uint64_t *)c->buf[HOST_1], (const uint64_t *)c->buf[HOST_0], batch, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(data, c->buf[HOST_1], bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -1991,46 +1885,22 @@ int sr_recompose_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_
 }
 
 // ---- host-pointer variants of the linear-algebra entry points (convenience entry points for callers that hold Vec<..> on the
-// host; resident data uses the _dev forms): their device temporaries live in the context and only grow
-namespace {
-// device temporary of a host-pointer call: slot `slot` of the context's grow-only set (the calls hold the context mutex and end with a
-// stream synchronisation, so a slot is free again when the next call starts; nothing is allocated or freed per call once warm)
-struct DevBuf {
-    sr_ctx *c;
-    int slot;
-    void *p = nullptr;
-    DevBuf(sr_ctx *c_, int slot_) : c(c_), slot(slot_) {}
-    int alloc(size_t bytes) {
-        if (bytes == 0) bytes = 8;
-        if (c->host_tmp_bytes[slot] < bytes) {
-            if (c->host_tmp[slot]) {
-                (void)hipFree(c->host_tmp[slot]);
-                c->host_tmp[slot] = nullptr;
-                c->host_tmp_bytes[slot] = 0;
-            }
-            hipError_t e = hipMalloc(&c->host_tmp[slot], bytes);
-            if (e != hipSuccess) return fail(SR_E_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
-            c->host_tmp_bytes[slot] = bytes;
-        }
-        p = c->host_tmp[slot];
-        return SR_OK;
-    }
-};
-}  // namespace
+// host; resident data uses the _dev forms): their device temporaries are the context's HOST_* buffers (the calls hold the context
+// mutex and end with a stream synchronisation, so a buffer is free again when the next call starts)
 int sr_matmul_ntt(sr_ctx *c, uint64_t *y, const uint64_t *a, const uint64_t *b, size_t n, size_t m, size_t p) {
     if (int rc = check(c, y, a, b)) return rc;
     if (check_count(c, n, m) || check_count(c, m, p) || check_count(c, n, p)) return SR_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     const size_t w = c->degree * c->limbs * 8;
-    DevBuf da(c, 0), db(c, 1), dy(c, 2);
-    if (int rc = da.alloc(n * m * w)) return rc;
-    if (int rc = db.alloc(m * p * w)) return rc;
-    if (int rc = dy.alloc(n * p * w)) return rc;
-    if (n * m) HIP_TRY(hipMemcpyAsync(da.p, a, n * m * w, hipMemcpyHostToDevice, c->stream));
-    if (m * p) HIP_TRY(hipMemcpyAsync(db.p, b, m * p * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_matmul(c, (uint64_t *)dy.p, (const uint64_t *)da.p, (const uint64_t *)db.p, n, m, p, c->stream)) return rc;
-    if (n * p) HIP_TRY(hipMemcpyAsync(y, dy.p, n * p * w, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = grow(c, HOST_0, n * m * w)) return rc;
+    if (int rc = grow(c, HOST_1, m * p * w)) return rc;
+    if (int rc = grow(c, HOST_2, n * p * w)) return rc;
+    uint64_t *da = (uint64_t *)c->buf[HOST_0], *db = (uint64_t *)c->buf[HOST_1], *dy = (uint64_t *)c->buf[HOST_2];
+    if (n * m) HIP_TRY(hipMemcpyAsync(da, a, n * m * w, hipMemcpyHostToDevice, c->stream));
+    if (m * p) HIP_TRY(hipMemcpyAsync(db, b, m * p * w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_matmul(c, dy, da, db, n, m, p, c->stream)) return rc;
+    if (n * p) HIP_TRY(hipMemcpyAsync(y, dy, n * p * w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -2040,14 +1910,14 @@ int sr_matvec_ntt(sr_ctx *c, uint64_t *y, const uint64_t *m, const uint64_t *v, 
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     const size_t w = c->degree * c->limbs * 8;
-    DevBuf dm(c, 0), dv(c, 1), dy(c, 2);
-    if (int rc = dm.alloc(nrows * ncols * w)) return rc;
-    if (int rc = dv.alloc(ncols * w)) return rc;
-    if (int rc = dy.alloc(nrows * w)) return rc;
-    if (nrows * ncols) HIP_TRY(hipMemcpyAsync(dm.p, m, nrows * ncols * w, hipMemcpyHostToDevice, c->stream));
-    if (ncols) HIP_TRY(hipMemcpyAsync(dv.p, v, ncols * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_matvec(c, (uint64_t *)dy.p, (const uint64_t *)dm.p, (const uint64_t *)dv.p, nrows, ncols, c->stream)) return rc;
-    if (nrows) HIP_TRY(hipMemcpyAsync(y, dy.p, nrows * w, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = grow(c, HOST_0, nrows * ncols * w)) return rc;
+    if (int rc = grow(c, HOST_1, ncols * w)) return rc;
+    if (int rc = grow(c, HOST_2, nrows * w)) return rc;
+    uint64_t *dm = (uint64_t *)c->buf[HOST_0], *dv = (uint64_t *)c->buf[HOST_1], *dy = (uint64_t *)c->buf[HOST_2];
+    if (nrows * ncols) HIP_TRY(hipMemcpyAsync(dm, m, nrows * ncols * w, hipMemcpyHostToDevice, c->stream));
+    if (ncols) HIP_TRY(hipMemcpyAsync(dv, v, ncols * w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_matvec(c, dy, dm, dv, nrows, ncols, c->stream)) return rc;
+    if (nrows) HIP_TRY(hipMemcpyAsync(y, dy, nrows * w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -2064,22 +1934,22 @@ int sr_spmv_ntt(sr_ctx *c, uint64_t *y, const uint64_t *vals, const uint32_t *co
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     const size_t w = c->degree * c->limbs * 8;
-    DevBuf dvals(c, 0), dcols(c, 1), dptr(c, 2), dv(c, 3), dy(c, 4);
-    if (int rc = dvals.alloc(nnz * w)) return rc;
-    if (int rc = dcols.alloc(nnz * 4)) return rc;
-    if (int rc = dptr.alloc((nrows + 1) * 8)) return rc;
-    if (int rc = dv.alloc(ncols * w)) return rc;
-    if (int rc = dy.alloc(nrows * w)) return rc;
+    if (int rc = grow(c, HOST_0, nnz * w)) return rc;
+    if (int rc = grow(c, HOST_1, nnz * 4)) return rc;
+    if (int rc = grow(c, HOST_2, (nrows + 1) * 8)) return rc;
+    if (int rc = grow(c, HOST_3, ncols * w)) return rc;
+    if (int rc = grow(c, HOST_4, nrows * w)) return rc;
+    uint64_t *dvals = (uint64_t *)c->buf[HOST_0], *dptr = (uint64_t *)c->buf[HOST_2], *dv = (uint64_t *)c->buf[HOST_3];
+    uint64_t *dy = (uint64_t *)c->buf[HOST_4];
+    uint32_t *dcols = (uint32_t *)c->buf[HOST_1];
     if (nnz) {
-        HIP_TRY(hipMemcpyAsync(dvals.p, vals, nnz * w, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(dcols.p, cols, nnz * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(dvals, vals, nnz * w, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(dcols, cols, nnz * 4, hipMemcpyHostToDevice, c->stream));
     }
-    HIP_TRY(hipMemcpyAsync(dptr.p, row_ptr, (nrows + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (ncols) HIP_TRY(hipMemcpyAsync(dv.p, v, ncols * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_spmv(c, (uint64_t *)dy.p, (const uint64_t *)dvals.p, (const uint32_t *)dcols.p, (const uint64_t *)dptr.p,
-                          (const uint64_t *)dv.p, nrows, ncols, c->stream))
-        return rc;
-    if (nrows) HIP_TRY(hipMemcpyAsync(y, dy.p, nrows * w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dptr, row_ptr, (nrows + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (ncols) HIP_TRY(hipMemcpyAsync(dv, v, ncols * w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_spmv(c, dy, dvals, dcols, dptr, dv, nrows, ncols, c->stream)) return rc;
+    if (nrows) HIP_TRY(hipMemcpyAsync(y, dy, nrows * w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -2089,15 +1959,15 @@ static int host_fold(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, boo
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     const size_t w = (size_t)c->degree * c->limbs * 8;
-    DevBuf di(c, 0), dout(c, 1);
-    if (int rc = di.alloc(n * w)) return rc;
-    if (int rc = dout.alloc(w)) return rc;
-    if (n) HIP_TRY(hipMemcpyAsync(di.p, in, n * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = mul ? dev_product(c, (uint64_t *)dout.p, (const uint64_t *)di.p, n, c->stream) : dev_sum(c, (uint64_t *)dout.p, (const uint64_t *)di.p, n, c->stream)) {
+    if (int rc = grow(c, HOST_0, n * w)) return rc;
+    if (int rc = grow(c, HOST_1, w)) return rc;
+    uint64_t *di = (uint64_t *)c->buf[HOST_0], *dout = (uint64_t *)c->buf[HOST_1];
+    if (n) HIP_TRY(hipMemcpyAsync(di, in, n * w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = mul ? dev_product(c, dout, di, n, c->stream) : dev_sum(c, dout, di, n, c->stream)) {
         (void)hipStreamSynchronize(c->stream);
         return rc;
     }
-    HIP_TRY(hipMemcpyAsync(out, dout.p, w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout, w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -2115,15 +1985,15 @@ int sr_decompose_balanced_batch_wide(sr_ctx *c, uint64_t *out, const uint64_t *i
     DeviceGuard g(c->device);
     const size_t w = c->degree * c->limbs * 8;
     if (batch == 0 || padding_size == 0) return SR_OK;
-    DevBuf din(c, 0), dout(c, 1);
-    if (int rc = din.alloc(batch * w)) return rc;
-    if (int rc = dout.alloc(batch * padding_size * w)) return rc;
-    HIP_TRY(hipMemcpyAsync(din.p, in, batch * w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = grow(c, HOST_0, batch * w)) return rc;
+    if (int rc = grow(c, HOST_1, batch * padding_size * w)) return rc;
+    uint64_t *din = (uint64_t *)c->buf[HOST_0], *dout = (uint64_t *)c->buf[HOST_1];
+    HIP_TRY(hipMemcpyAsync(din, in, batch * w, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counter + 2, 0, sizeof(unsigned long long), c->stream));
-    if (int rc = dev_decompose_any(c, (uint64_t *)dout.p, (const uint64_t *)din.p, basis, basis_hi, padding_size, batch, c->stream)) return rc;
+    if (int rc = dev_decompose_any(c, dout, din, basis, basis_hi, padding_size, batch, c->stream)) return rc;
     unsigned long long over = 0;
     HIP_TRY(hipMemcpyAsync(&over, c->d_counter + 2, sizeof over, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out, dout.p, batch * padding_size * w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout, batch * padding_size * w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counter + 2, 0, sizeof(unsigned long long), c->stream));
     // the reference indexes out[padding_size] and panics (mod.rs:81-91)
@@ -2137,12 +2007,11 @@ int sr_serialize_batch(sr_ctx *c, uint8_t *wire, const uint64_t *in, size_t batc
     DeviceGuard g(c->device);
     const size_t n = batch * c->degree;
     if (n == 0) return SR_OK;
-    DevBuf din(c, 0), dw(c, 1);
-    if (int rc = din.alloc(n * c->limbs * 8)) return rc;
-    if (int rc = dw.alloc(n * wire_coeff_bytes(c))) return rc;
-    HIP_TRY(hipMemcpyAsync(din.p, in, n * c->limbs * 8, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_wire(c, true, dw.p, din.p, nullptr, batch, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(wire, dw.p, n * wire_coeff_bytes(c), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = grow(c, HOST_0, n * c->limbs * 8)) return rc;
+    if (int rc = grow(c, HOST_1, n * wire_coeff_bytes(c))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], in, n * c->limbs * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_wire(c, true, c->buf[HOST_1], c->buf[HOST_0], nullptr, batch, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(wire, c->buf[HOST_1], n * wire_coeff_bytes(c), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -2153,19 +2022,18 @@ int sr_deserialize_batch(sr_ctx *c, uint64_t *out, const uint8_t *wire, size_t b
     DeviceGuard g(c->device);
     const size_t n = batch * c->degree;
     if (n == 0) return SR_OK;
-    DevBuf dout(c, 0), dw(c, 1);
-    if (int rc = dout.alloc(n * c->limbs * 8)) return rc;
-    if (int rc = dw.alloc(n * wire_coeff_bytes(c))) return rc;
-    HIP_TRY(hipMemcpyAsync(dw.p, wire, n * wire_coeff_bytes(c), hipMemcpyHostToDevice, c->stream));
+    if (int rc = grow(c, HOST_0, n * c->limbs * 8)) return rc;
+    if (int rc = grow(c, HOST_1, n * wire_coeff_bytes(c))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->buf[HOST_1], wire, n * wire_coeff_bytes(c), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
-    if (int rc = dev_wire(c, false, dout.p, dw.p, nullptr, batch, c->stream)) return rc;
+    if (int rc = dev_wire(c, false, c->buf[HOST_0], c->buf[HOST_1], nullptr, batch, c->stream)) return rc;
     unsigned long long bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, c->d_counter + 3, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
     // Fp::deserialize_with_flags: from_bigint(..) is None for an integer >= p -> SerializationError::InvalidData
     if (bad) return fail(SR_E_INVALID, "deserialize: a coefficient is not below the modulus (InvalidData)");
-    HIP_TRY(hipMemcpyAsync(out, dout.p, n * c->limbs * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_0], n * c->limbs * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -2180,12 +2048,12 @@ int sr_recompose_batch_wide(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64
     DeviceGuard g(c->device);
     const size_t w = c->degree * c->limbs * 8;
     if (batch_out == 0) return SR_OK;
-    DevBuf din(c, 0), dout(c, 1);
-    if (int rc = din.alloc(batch_out * padding_size * w)) return rc;
-    if (int rc = dout.alloc(batch_out * w)) return rc;
-    if (padding_size) HIP_TRY(hipMemcpyAsync(din.p, in, batch_out * padding_size * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_recompose_any(c, (uint64_t *)dout.p, (const uint64_t *)din.p, basis, basis_hi, padding_size, batch_out, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout.p, batch_out * w, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = grow(c, HOST_0, batch_out * padding_size * w)) return rc;
+    if (int rc = grow(c, HOST_1, batch_out * w)) return rc;
+    uint64_t *din = (uint64_t *)c->buf[HOST_0], *dout = (uint64_t *)c->buf[HOST_1];
+    if (padding_size) HIP_TRY(hipMemcpyAsync(din, in, batch_out * padding_size * w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_recompose_any(c, dout, din, basis, basis_hi, padding_size, batch_out, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout, batch_out * w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }
@@ -2211,47 +2079,45 @@ int sr_ctx_reserve_scratch(sr_ctx *c, size_t batch) {
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     if (batch == 0) return SR_OK;
-    {   // the two partial-element buffers of sr_sum_batch_dev / sr_product_batch_dev (a few MiB; the small rings' product tree sizes its
-        // own by the slice length on first use)
-        const size_t sw = (size_t)c->limbs * 8;  // bytes per coefficient
-        for (int slot = 8; slot <= 9; slot++) {
-            DevBufLite t(c, slot);
-            if (int rc = t.alloc(fold_tmp_words(c->degree) * sw, nullptr, true)) return rc;
-        }
-    }
+    // the two partial-element buffers of sr_sum_batch_dev / sr_product_batch_dev (a few MiB; the small rings' product tree sizes FOLD_0
+    // by the slice length on first use)
+    for (Buf b : {FOLD_0, FOLD_1})
+        if (int rc = grow(c, b, fold_tmp_words(c->degree) * c->limbs * 8, nullptr, true)) return rc;
     if (!is_pow2_ring(c->ring)) return SR_OK;  // the small rings need no operand scratch
     if (int rc = lanes_autoselect(c, batch)) return rc;      // sr_plan.lanes = 0: settle the plan now, then size the scratch for it
     const size_t elem = c->degree * c->limbs * 8;
-    if (c->regtile) {
-        // BOTH users of the packed scratch: the ring product (four lane chunks on two lanes, else two buffers of one chunk) and the
-        // stand-alone transforms, whose lanes only start at eight chunks (lanes_pay_transform): below that they run on the caller's
-        // stream through ONE buffer of the whole batch (a batch of 4 .. 8 lane chunks used to be reserved for the product
-        // only, and the first transform afterwards synchronised the device and reallocated)
-        const bool bb = c->ring == SR_RING_BABYBEAR_POW2;
-        const size_t w = bb ? 4 : 8;
-        const bool lanes = bb ? rt_use_lanes<sr::BabyBear>(c, batch, nullptr) : rt_use_lanes<sr::Goldilocks>(c, batch, nullptr);
-        const bool lanes_t = bb ? rt_use_lanes_transform<sr::BabyBear>(c, batch, nullptr) : rt_use_lanes_transform<sr::Goldilocks>(c, batch, nullptr);
-        const size_t chunk = bb ? rt_lane_chunk<sr::BabyBear>(c) : rt_lane_chunk<sr::Goldilocks>(c);
-        const size_t whole = (batch << c->k) * w, four = 4 * (chunk << c->k) * w;
-        if (lanes || lanes_t)
-            if (int rc = gl_lanes_init(c)) return rc;
-        if (c->k <= 12) return SR_OK;
-        size_t need0 = lanes ? four : ((c->k > 12 ? rt_chunk_polys(c, batch) : batch) << c->k) * w, need1 = lanes ? 0 : need0;
-        const size_t transform = lanes_t ? four : whole;
-        if (transform > need0) need0 = transform;
-        if (int rc = ensure_scratch(c, 1, need0, nullptr, true)) return rc;
-        return need1 ? ensure_scratch(c, 2, need1, nullptr, true) : SR_OK;
+    switch (c->path) {
+        case RT_BABYBEAR: case RT_GOLDILOCKS: {
+            // BOTH users of the packed scratch: the ring product (four lane chunks on two lanes, else two buffers of one chunk) and the
+            // stand-alone transforms, whose lanes only start at eight chunks (lanes_pay_transform): below that they run on the caller's
+            // stream through ONE buffer of the whole batch (a batch of 4 .. 8 lane chunks used to be reserved for the product
+            // only, and the first transform afterwards synchronised the device and reallocated)
+            const bool lanes = use_lanes(c, batch, nullptr, false), lanes_t = use_lanes(c, batch, nullptr, true);
+            const size_t whole = batch * lane_elem_bytes(c), four = 4 * lane_chunk(c) * lane_elem_bytes(c);
+            if (lanes || lanes_t)
+                if (int rc = gl_lanes_init(c)) return rc;
+            if (c->k <= 12) return SR_OK;
+            size_t need0 = lanes ? four : rt_chunk_polys(c, batch) * lane_elem_bytes(c), need1 = lanes ? 0 : need0;
+            const size_t transform = lanes_t ? four : whole;
+            if (transform > need0) need0 = transform;
+            if (int rc = grow(c, OPERAND_A, need0, nullptr, true)) return rc;
+            return need1 ? grow(c, OPERAND_B, need1, nullptr, true) : SR_OK;
+        }
+        case GL_FAST:
+            if (c->k <= 12) return SR_OK;
+            if (use_lanes(c, batch, nullptr, false)) {
+                if (int rc = gl_lanes_init(c)) return rc;
+                return grow(c, OPERAND_A, 4 * lane_chunk(c) * elem, nullptr, true);
+            }
+            return grow(c, OPERAND_A, gl_chunk_polys(c, batch) * elem, nullptr, true);
+        case STARK_TUNED:
+            if (c->stark_one_tile) return SR_OK;
+            break;
+        default:
+            if (c->k <= c->log_tile) return SR_OK;
+            break;
     }
-    const bool one_launch = c->ring == SR_RING_GOLDILOCKS_POW2 && c->fast_goldilocks && sr::gl_fast_supported(c->gl_fast)
-                                ? c->k <= 12
-                                : (c->stark_tuned ? c->stark_one_tile : c->k <= c->log_tile);
-    if (one_launch) return SR_OK;
-    const bool gl = c->ring == SR_RING_GOLDILOCKS_POW2 && c->fast_goldilocks && sr::gl_fast_supported(c->gl_fast);
-    if (gl && gl_use_lanes(c, batch)) {
-        if (int rc = gl_lanes_init(c)) return rc;
-        return ensure_scratch(c, 1, 4 * gl_lane_chunk(c) * elem, nullptr, true);
-    }
-    return ensure_scratch(c, 1, (gl ? gl_chunk_polys(c, batch) : scratch_polys(c, batch, elem)) * elem, nullptr, true);
+    return grow(c, OPERAND_A, scratch_polys(c, batch, elem) * elem, nullptr, true);
 }
 // ---- packed-u32 boundary (BabyBear power-of-two rings; csrc/packed32.hpp) ----------------------------------------------------
 extern "C++" {
@@ -2279,17 +2145,17 @@ int launch_unpack32(sr_ctx *c, uint64_t *out, const uint32_t *in, size_t n, hipS
 template <class Fn>
 int packed_via_wide(sr_ctx *c, uint32_t *out, const uint32_t *a, const uint32_t *b, size_t batch, hipStream_t st, Fn run) {
     const size_t n = batch << c->k;
-    DevBufLite wa(c, 5), wb(c, 6);
-    if (int rc = wa.alloc(n * 8, st)) return rc;
+    if (int rc = grow(c, WIDE_A, n * 8, st)) return rc;
     if (b)
-        if (int rc = wb.alloc(n * 8, st)) return rc;
+        if (int rc = grow(c, WIDE_B, n * 8, st)) return rc;
     ScratchUse su(c, st);  // the staging buffers belong to the context, the call may arrive on any stream: ordered like the operand scratch
     if (int rc = su.acquire()) return rc;
-    if (int rc = launch_unpack32(c, (uint64_t *)wa.p, a, n, st)) return rc;
+    uint64_t *wa = (uint64_t *)c->buf[WIDE_A], *wb = (uint64_t *)c->buf[WIDE_B];
+    if (int rc = launch_unpack32(c, wa, a, n, st)) return rc;
     if (b)
-        if (int rc = launch_unpack32(c, (uint64_t *)wb.p, b, n, st)) return rc;
-    if (int rc = run((uint64_t *)wa.p, (uint64_t *)wb.p)) return rc;
-    return launch_pack32(c, out, (const uint64_t *)wa.p, n, st);
+        if (int rc = launch_unpack32(c, wb, b, n, st)) return rc;
+    if (int rc = run(wa, wb)) return rc;
+    return launch_pack32(c, out, wa, n, st);
 }
 }  // namespace
 }  // extern "C++"
@@ -2317,9 +2183,7 @@ int sr_ntt_fwd_packed32_batch_dev(sr_ctx *c, uint32_t *d, size_t batch, void *st
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (batch == 0) return SR_OK;
-    if (c->regtile) {
-        return rt_fwd<sr::BabyBear, sr::rt::PackedStream>(c, d, batch, st);
-    }
+    if (c->path == RT_BABYBEAR) return rt_transform<sr::BabyBear, 0, sr::rt::PackedStream>(c, d, batch, st);
     return packed_via_wide(c, d, d, nullptr, batch, st, [&](uint64_t *wa, uint64_t *) { return dev_fwd(c, wa, batch, st); });
 }
 int sr_ntt_inv_packed32_batch_dev(sr_ctx *c, uint32_t *d, size_t batch, void *stream) {
@@ -2330,9 +2194,7 @@ int sr_ntt_inv_packed32_batch_dev(sr_ctx *c, uint32_t *d, size_t batch, void *st
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (batch == 0) return SR_OK;
-    if (c->regtile) {
-        return rt_inv<sr::BabyBear, sr::rt::PackedStream>(c, d, batch, st);
-    }
+    if (c->path == RT_BABYBEAR) return rt_transform<sr::BabyBear, 1, sr::rt::PackedStream>(c, d, batch, st);
     return packed_via_wide(c, d, d, nullptr, batch, st, [&](uint64_t *wa, uint64_t *) { return dev_inv(c, wa, batch, st); });
 }
 int sr_ring_mul_packed32_batch_dev(sr_ctx *c, uint32_t *d_out, const uint32_t *d_a, const uint32_t *d_b, size_t batch, void *stream) {
@@ -2344,9 +2206,7 @@ int sr_ring_mul_packed32_batch_dev(sr_ctx *c, uint32_t *d_out, const uint32_t *d
     DeviceGuard g(c->device);
     hipStream_t st = (hipStream_t)stream;
     if (batch == 0) return SR_OK;
-    if (c->regtile) {
-        return rt_ring_mul<sr::BabyBear, sr::rt::PackedStream>(c, d_out, d_a, d_b, batch, st);
-    }
+    if (c->path == RT_BABYBEAR) return rt_ring_mul<sr::BabyBear, sr::rt::PackedStream>(c, d_out, d_a, d_b, batch, st);
     return packed_via_wide(c, d_out, d_a, d_b, batch, st, [&](uint64_t *wa, uint64_t *wb) { return dev_ring_mul(c, wa, wa, wb, batch, st); });
 }
 static int packed_elementwise(sr_ctx *c, uint32_t *l, const uint32_t *r, size_t batch, void *stream, int op) {
@@ -2444,20 +2304,20 @@ static int host_pipeline(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint
     size_t chunk = (chunk_mb << 20) / elem_bytes;
     if (chunk == 0) chunk = 1;
     if (batch <= 2 * chunk) {  // one shot
-        if (int rc = ensure_stage(c, 0, bytes)) return rc;
+        if (int rc = grow(c, HOST_0, bytes)) return rc;
         if (b)
-            if (int rc = ensure_stage(c, 1, bytes)) return rc;
-        HIP_TRY(hipMemcpyAsync(c->stage[0], a, bytes, hipMemcpyHostToDevice, c->stream));
-        if (b) HIP_TRY(hipMemcpyAsync(c->stage[1], b, bytes, hipMemcpyHostToDevice, c->stream));
-        if (int rc = compute((uint64_t *)c->stage[0], (uint64_t *)c->stage[1], batch, c->stream)) return rc;
-        HIP_TRY(hipMemcpyAsync(out, c->stage[0], bytes, hipMemcpyDeviceToHost, c->stream));
+            if (int rc = grow(c, HOST_1, bytes)) return rc;
+        HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], a, bytes, hipMemcpyHostToDevice, c->stream));
+        if (b) HIP_TRY(hipMemcpyAsync(c->buf[HOST_1], b, bytes, hipMemcpyHostToDevice, c->stream));
+        if (int rc = compute((uint64_t *)c->buf[HOST_0], (uint64_t *)c->buf[HOST_1], batch, c->stream)) return rc;
+        HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_0], bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         return SR_OK;
     }
     const size_t chunk_bytes = chunk * elem_bytes;
     for (int i = 0; i < 4; i++)
         if (b || (i & 1) == 0)
-            if (int rc = ensure_stage(c, i, chunk_bytes)) return rc;
+            if (int rc = grow(c, Buf(HOST_0 + i), chunk_bytes)) return rc;
     hipEvent_t ready[2];
     for (auto &e : ready) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     struct Job {
@@ -2505,7 +2365,7 @@ static int host_pipeline(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint
             std::unique_lock<std::mutex> lk(m);  // the lane's buffers are free once chunk i - 2 has been copied out
             cv.wait(lk, [&] { return i < 2 || done + 1 >= i; });
         }
-        uint64_t *s0 = (uint64_t *)c->stage[2 * lane], *s1 = (uint64_t *)c->stage[2 * lane + 1];
+        uint64_t *s0 = (uint64_t *)c->buf[HOST_0 + 2 * lane], *s1 = (uint64_t *)c->buf[HOST_1 + 2 * lane];
         main_err = hipMemcpyAsync(s0, a + first * (elem_bytes / 8), n * elem_bytes, hipMemcpyHostToDevice, c->stream);
         if (main_err == hipSuccess && b)
             main_err = hipMemcpyAsync(s1, b + first * (elem_bytes / 8), n * elem_bytes, hipMemcpyHostToDevice, c->stream);
@@ -2560,21 +2420,19 @@ int sr_scale_batch(sr_ctx *c, uint64_t *data, const uint64_t *scalar, size_t bat
 int sr_add_scalar_batch(sr_ctx *c, uint64_t *data, const uint64_t *scalar, int ntt_form, size_t batch) {
     return host_unary(c, data, scalar, batch, ntt_form ? 3 : 2);
 }
-// host buffers: the one element goes to a device temporary of its own, the batch through the staged pipeline
+// host buffers: the one element goes to ELEMENT, the batch through the staged pipeline
 int sr_mul_elem_batch(sr_ctx *c, uint64_t *data, const uint64_t *elem, size_t batch) {
     if (int rc = check(c, data, elem)) return rc;
     if (int rc = check_count(c, batch)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     const size_t bytes = (size_t)c->degree * c->limbs * 8;
-    uint64_t *dr = nullptr;
-    HIP_TRY(hipMalloc((void **)&dr, bytes));
-    hipError_t e = hipMemcpy(dr, elem, bytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? host_pipeline(c, data, data, nullptr, batch, [&](uint64_t *s0, uint64_t *, size_t n, hipStream_t st) {
+    if (int rc = grow(c, ELEMENT, bytes)) return rc;
+    const uint64_t *dr = (const uint64_t *)c->buf[ELEMENT];
+    HIP_TRY(hipMemcpy(c->buf[ELEMENT], elem, bytes, hipMemcpyHostToDevice));
+    return host_pipeline(c, data, data, nullptr, batch, [&](uint64_t *s0, uint64_t *, size_t n, hipStream_t st) {
         return dev_mul_elem(c, s0, dr, n, st);
-    }) : fail(SR_E_HIP, std::string("mul_elem: ") + hipGetErrorString(e));
-    (void)hipFree(dr);   // host_pipeline returned with its stream synchronised
-    return rc;
+    });
 }
 int sr_ntt_fwd_batch(sr_ctx *c, uint64_t *data, size_t batch) { return host_inplace(c, data, batch, true); }
 int sr_ntt_inv_batch(sr_ctx *c, uint64_t *data, size_t batch) { return host_inplace(c, data, batch, false); }
@@ -2611,11 +2469,11 @@ int sr_reduce_batch(sr_ctx *c, const uint64_t *in, size_t in_len, uint64_t *out,
     DeviceGuard g(c->device);
     size_t in_bytes = batch * in_len * c->limbs * 8, out_bytes = batch * c->degree * c->limbs * 8;
     if (out_bytes == 0) return SR_OK;
-    if (int rc = ensure_stage(c, 0, in_bytes ? in_bytes : 8)) return rc;
-    if (int rc = ensure_stage(c, 1, out_bytes)) return rc;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(c->stage[0], in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_reduce(c, (const uint64_t *)c->stage[0], in_len, (uint64_t *)c->stage[1], batch, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->stage[1], out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = grow(c, HOST_0, in_bytes)) return rc;
+    if (int rc = grow(c, HOST_1, out_bytes)) return rc;
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_reduce(c, (const uint64_t *)c->buf[HOST_0], in_len, (uint64_t *)c->buf[HOST_1], batch, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }

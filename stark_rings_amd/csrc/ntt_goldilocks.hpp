@@ -39,7 +39,7 @@ constexpr int kW16Exp = 156;  // omega_16 = 2^156 (= (8^13)^4)
 
 // Operand reads and result writes happen once per launch: non-temporal.  Intermediates (column-pass output, rows output) are written
 // and read WITHOUT the hint, so that they allocate in the 256 MB Infinity Cache: the ring product runs in chunks small enough for a
-// chunk's intermediates to stay there (gl_fast_ring_mul_lanes).  Tables keep the default policy and stay in L2.
+// chunk's intermediates to stay there (gl_fast_ring_mul_chunk).  Tables keep the default policy and stay in L2.
 __device__ __forceinline__ u64 ld_stream(const u64 *p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void st_stream(u64 *p, u64 v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ u64 ld_scratch(const u64 *p) { return *p; }
@@ -1382,104 +1382,70 @@ inline int gl_fast_ring_mul(const GoldilocksFastTables &f, uint64_t *out, const 
     return 0;
 }
 
-// The same product on LANES streams (cols256 plans: 2^16 <= D <= 2^20).  Chunks of `chunk` ring elements are dealt round-robin to
-// the lanes; a lane runs a chunk's four launches through ITS OWN scratch pair (sa: a's column-pass output, rows output; sb: b's), so
-// that (i) a chunk's intermediates -- 2 x chunk x D x 8 bytes, 128 MB at the default chunk -- are re-read from the Infinity Cache
-// instead of HBM (61 against ~100 pJ per byte on a step that runs at the socket's power cap: tools/ubench/l2_power.hip), and (ii)
+// The same product on LANES streams (cols256 plans: 2^16 <= D <= 2^20).  Chunks of ring elements are dealt round-robin to the lanes
+// (for_each_lane_chunk); a lane runs a chunk's four launches through ITS OWN scratch pair (sa: a's column-pass output, rows output; sb:
+// b's), so that (i) a chunk's intermediates -- 2 x chunk x D x 8 bytes, 128 MB at the default chunk -- are re-read from the Infinity
+// Cache instead of HBM (61 against ~100 pJ per byte on a step that runs at the socket's power cap: tools/ubench/l2_power.hip), and (ii)
 // the other lane's kernels fill the tail of every small launch (one stream at this chunk size: 21.5 ms per config-2 batch; two:
 // 16.3-16.9 ms against 17.3-17.6 ms for the former eight large chunks on one stream).  fork / join: events owned by the caller.
 struct GlLanes {
     int n = 0;                       // streams in use (<= 2)
     hipStream_t st[2] = {nullptr, nullptr};
     hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr};
-    uint64_t *sa[2] = {nullptr, nullptr}, *sb[2] = {nullptr, nullptr};
-    size_t chunk = 0;                // ring elements per chunk (each of sa[i], sb[i] holds that many)
 };
-inline int gl_fast_ring_mul_lanes(const GoldilocksFastTables &f, uint64_t *out, const uint64_t *a, const uint64_t *b, const GlLanes &L,
-                                  size_t batch, hipStream_t st) {
-    if (batch == 0) return 0;
-    if (!f.cols256 || L.n < 1 || L.chunk == 0) return 1;
+// Chunk i of `chunk` ring elements (the last one shorter) goes to lane i % L.n: body(lane, first, n, lane stream) enqueues elements
+// [first, first + n) and returns nonzero on failure, which stops the dealing.  The lanes fork from st, and st waits for every lane
+// again -- also after a failed launch: the caller's stream must not run ahead of the lanes.
+template <class Body>
+inline int for_each_lane_chunk(const GlLanes &L, size_t batch, size_t chunk, hipStream_t st, Body body) {
     if (hipEventRecord(L.fork, st) != hipSuccess) return 1;
     for (int i = 0; i < L.n; i++)
         if (hipStreamWaitEvent(L.st[i], L.fork, 0) != hipSuccess) return 1;
-    const size_t stride = (size_t)1 << f.k;
     int rc = 0;
     size_t c = 0;
-    for (size_t e = 0; e < batch && !rc; e += L.chunk, c++) {
+    for (size_t e = 0; e < batch && !rc; e += chunk, c++) {
         const int i = (int)(c % (size_t)L.n);
-        const size_t n = batch - e < L.chunk ? batch - e : L.chunk;
-        rc = gl_launch_cols256_lane_pair(f, L.sa[i], a + e * stride, L.sb[i], b + e * stride, n, L.st[i]);
-        if (f.split_rows) {
-            if (!rc) rc = gl_launch_rows<0>(f, L.sb[i], nullptr, L.sb[i], n, false, L.st[i]);
-            if (!rc) rc = gl_launch_rows<3>(f, L.sa[i], L.sb[i], L.sa[i], n, true, L.st[i]);
-        } else if (!rc) {
-            rc = gl_launch_rows<2>(f, L.sa[i], L.sb[i], L.sa[i], n, true, L.st[i]);
-        }
-        if (!rc) rc = gl_launch_cols256_lane<1>(f, out + e * stride, L.sa[i], n, f.t.wci, f.t.twist_i_mul, L.st[i]);
+        rc = body(i, e, batch - e < chunk ? batch - e : chunk, L.st[i]);
     }
-    for (int i = 0; i < L.n; i++) {  // join even after a failed launch: the caller's stream must not run ahead of the lanes
+    for (int i = 0; i < L.n; i++) {
         if (hipEventRecord(L.join[i], L.st[i]) != hipSuccess) rc = 1;
         if (hipStreamWaitEvent(st, L.join[i], 0) != hipSuccess) rc = 1;
     }
     return rc;
+}
+// one lane chunk of the product: n elements, out / a / b at the chunk's first element
+inline int gl_fast_ring_mul_chunk(const GoldilocksFastTables &f, uint64_t *out, const uint64_t *a, const uint64_t *b, uint64_t *sa,
+                                  uint64_t *sb, size_t n, hipStream_t st) {
+    if (gl_launch_cols256_lane_pair(f, sa, a, sb, b, n, st)) return 1;
+    if (f.split_rows) {
+        if (gl_launch_rows<0>(f, sb, nullptr, sb, n, false, st)) return 1;
+        if (gl_launch_rows<3>(f, sa, sb, sa, n, true, st)) return 1;
+    } else if (gl_launch_rows<2>(f, sa, sb, sa, n, true, st)) {
+        return 1;
+    }
+    return gl_launch_cols256_lane<1>(f, out, sa, n, f.t.wci, f.t.twist_i_mul, st);
 }
 
 // the stand-alone transforms (elementwise_crt / elementwise_icrt) in the same chunks on the same lanes: in place, no scratch; the chunk
 // written by the first launch is re-read by the second from the Infinity Cache
 template <int DIR>
-inline int gl_fast_transform_lanes(const GoldilocksFastTables &f, uint64_t *d, const GlLanes &L, size_t batch, hipStream_t st) {
-    if (batch == 0) return 0;
-    if (!f.cols256 || L.n < 1 || L.chunk == 0) return 1;
-    if (hipEventRecord(L.fork, st) != hipSuccess) return 1;
-    for (int i = 0; i < L.n; i++)
-        if (hipStreamWaitEvent(L.st[i], L.fork, 0) != hipSuccess) return 1;
-    const size_t stride = (size_t)1 << f.k;
-    int rc = 0;
-    size_t c = 0;
-    for (size_t e = 0; e < batch && !rc; e += L.chunk, c++) {
-        const int i = (int)(c % (size_t)L.n);
-        const size_t n = batch - e < L.chunk ? batch - e : L.chunk;
-        uint64_t *dc = d + e * stride;
-        if (DIR == 0) {
-            rc = gl_launch_cols256_lane<0>(f, dc, dc, n, f.t.wcf, f.t.twist_f, L.st[i]);
-            if (!rc) rc = gl_launch_rows<0>(f, dc, nullptr, dc, n, false, L.st[i]);
-        } else {
-            rc = gl_launch_rows<1>(f, dc, nullptr, dc, n, false, L.st[i]);
-            // the plain inverse pass here: behind the light rows256_kernel<1> of a stand-alone icrt the workgroup-owns-its-columns
-            // kernel lost 2.4 % (6.06-6.13 against 5.94-5.95 ms per config-2 batch); the forward one above gains 1.2 %
-            if (!rc) rc = gl_launch_cols256<1>(f, dc, dc, n, f.t.wci, f.t.twist_i_plain, L.st[i]);
-        }
+inline int gl_fast_transform_chunk(const GoldilocksFastTables &f, uint64_t *d, size_t n, hipStream_t st) {
+    if (DIR == 0) {
+        if (gl_launch_cols256_lane<0>(f, d, d, n, f.t.wcf, f.t.twist_f, st)) return 1;
+        return gl_launch_rows<0>(f, d, nullptr, d, n, false, st);
     }
-    for (int i = 0; i < L.n; i++) {
-        if (hipEventRecord(L.join[i], L.st[i]) != hipSuccess) rc = 1;
-        if (hipStreamWaitEvent(st, L.join[i], 0) != hipSuccess) rc = 1;
-    }
-    return rc;
+    if (gl_launch_rows<1>(f, d, nullptr, d, n, false, st)) return 1;
+    // the plain inverse pass here: behind the light rows256_kernel<1> of a stand-alone icrt the workgroup-owns-its-columns
+    // kernel lost 2.4 % (6.06-6.13 against 5.94-5.95 ms per config-2 batch); the forward one above gains 1.2 %
+    return gl_launch_cols256<1>(f, d, d, n, f.t.wci, f.t.twist_i_plain, st);
 }
 
 // the constant-operand product (b already in NTT form) on the same lanes: three launches per chunk, one scratch buffer per lane
-inline int gl_fast_ring_mul_rhs_lanes(const GoldilocksFastTables &f, uint64_t *out, const uint64_t *a, const uint64_t *b_ntt, const GlLanes &L,
-                                      size_t batch, hipStream_t st) {
-    if (batch == 0) return 0;
-    if (!f.cols256 || L.n < 1 || L.chunk == 0) return 1;
-    if (hipEventRecord(L.fork, st) != hipSuccess) return 1;
-    for (int i = 0; i < L.n; i++)
-        if (hipStreamWaitEvent(L.st[i], L.fork, 0) != hipSuccess) return 1;
-    const size_t stride = (size_t)1 << f.k;
-    int rc = 0;
-    size_t c = 0;
-    for (size_t e = 0; e < batch && !rc; e += L.chunk, c++) {
-        const int i = (int)(c % (size_t)L.n);
-        const size_t n = batch - e < L.chunk ? batch - e : L.chunk;
-        rc = gl_launch_cols256_lane<0>(f, L.sa[i], a + e * stride, n, f.t.wcf, f.t.twist_f, L.st[i]);
-        if (!rc) rc = gl_launch_rows<3>(f, L.sa[i], b_ntt + e * stride, L.sa[i], n, true, L.st[i]);
-        if (!rc) rc = gl_launch_cols256_lane<1>(f, out + e * stride, L.sa[i], n, f.t.wci, f.t.twist_i_mul, L.st[i]);
-    }
-    for (int i = 0; i < L.n; i++) {
-        if (hipEventRecord(L.join[i], L.st[i]) != hipSuccess) rc = 1;
-        if (hipStreamWaitEvent(st, L.join[i], 0) != hipSuccess) rc = 1;
-    }
-    return rc;
+inline int gl_fast_ring_mul_rhs_chunk(const GoldilocksFastTables &f, uint64_t *out, const uint64_t *a, const uint64_t *b_ntt, uint64_t *sa,
+                                      size_t n, hipStream_t st) {
+    if (gl_launch_cols256_lane<0>(f, sa, a, n, f.t.wcf, f.t.twist_f, st)) return 1;
+    if (gl_launch_rows<3>(f, sa, b_ntt, sa, n, true, st)) return 1;
+    return gl_launch_cols256_lane<1>(f, out, sa, n, f.t.wci, f.t.twist_i_mul, st);
 }
 
 // out = icrt(crt(a) (.) b_ntt), b_ntt = crt(b) as sr_ntt_fwd leaves it: a's column stages go straight to out, the rows kernel

@@ -1554,7 +1554,7 @@ def test_column_pass_tile_order_covers_every_tile(torch_cuda, name, k, batch):
 @pytest.mark.parametrize("k,batch,plan_kw", [(16, 460, {}), (16, 300, {"chunk_polys": 64}), (16, 131, {"chunk_polys": 1}), (17, 7, {"chunk_polys": 2}),
                                              (20, 3, {"chunk_polys": 1}), (16, 300, {"lanes": 1}), (16, 129, {"scratch_limit_bytes": 16 << 20})])
 def test_goldilocks_product_on_two_lanes(torch_cuda, k, batch, plan_kw):
-    """Tuned Goldilocks product above one chunk: chunks dealt to two internal streams, each with its own scratch pair (gl_fast_ring_mul_lanes);
+    """Tuned Goldilocks product above one chunk: chunks dealt to two internal streams, each with its own scratch pair (gl_fast_ring_mul_chunk);
     ragged last chunks, chunk of one element, a scratch cap that shrinks the chunk, and the one-stream plan (lanes = 1) for comparison.  Against the
     oracle: out of place with operands intact, then in place over a (out == a) and squaring (a and b the same buffer), and a second call on ANOTHER
     caller stream right behind the first (the scratch is ordered across streams by an event)."""
