@@ -10,6 +10,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -170,6 +171,13 @@ struct DeviceGuard {
     ~DeviceGuard() {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
+};
+// The preamble of an entry point once its arguments are checked: the context's mutex, then its device; st = the caller's stream
+struct Call {
+    std::lock_guard<std::mutex> lk;
+    DeviceGuard g;
+    hipStream_t st;
+    explicit Call(sr_ctx *c, void *stream = nullptr) : lk(c->mu), g(c->device), st((hipStream_t)stream) {}
 };
 
 // RAII for optional per-kernel event timing on the launch stream
@@ -1022,17 +1030,18 @@ int dev_recompose_any(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t lo,
     return hi ? dev_recompose_wide(c, out, in, lo, hi, k, batch_out, st) : dev_recompose(c, out, in, lo, k, batch_out, st);
 }
 
-int check(sr_ctx *c, const void *p0, const void *p1 = (const void *)1, const void *p2 = (const void *)1) {
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (!p0 || !p1 || !p2) return fail(SR_E_INVALID, "null buffer");
-    return SR_OK;
-}
-
 // element counts are bounded so that no byte count or shift below can wrap (64 TiB of ring elements is far past any device)
 int check_count(const sr_ctx *c, size_t n_elems, size_t per_elem = 1) {
     const size_t cap = ((size_t)1 << 46) / (c->degree * (size_t)c->limbs * 8);
     if (n_elems > cap || (per_elem > 1 && n_elems && per_elem > cap / n_elems)) return fail(SR_E_INVALID, "element count too large");
     return SR_OK;
+}
+// the first checks of an entry point: the context, then its buffers, then n_elems ring elements of per_elem each (check_count)
+int check(const sr_ctx *c, std::initializer_list<const void *> bufs, size_t n_elems = 0, size_t per_elem = 1) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    for (const void *p : bufs)
+        if (!p) return fail(SR_E_INVALID, "null buffer");
+    return check_count(c, n_elems, per_elem);
 }
 
 // ---- per-ring device dispatch (pow2 rings and the reference-native small rings) --------------
@@ -1490,6 +1499,304 @@ int dev_reduce(sr_ctx *c, const uint64_t *in, size_t in_len, uint64_t *out, size
     }
 }
 
+int check_fold(sr_ctx *c, const uint64_t *out, const uint64_t *in, size_t n) {
+    if (int rc = check(c, {out, n ? (const void *)in : (const void *)1}, n)) return rc;
+    const uintptr_t w = (uintptr_t)c->degree * c->limbs * 8, po = (uintptr_t)out, pi = (uintptr_t)in;
+    if (n && po + w > pi && pi + n * w > po) return fail(SR_E_INVALID, "sum / product: out must not overlap the input elements");
+    return SR_OK;
+}
+// d_counter[i] (sr_ctx_create_ex) to the host, then cleared
+int read_counter(sr_ctx *c, int i, unsigned long long *out, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(out, c->d_counter + i, sizeof *out, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(c->d_counter + i, 0, sizeof *out, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SR_OK;
+}
+
+// ---- host-pointer entry points: stage, run, copy back ----
+// One operand of a one-shot host-pointer call: `bytes` in its HOST_* slot, uploaded from `up` and / or downloaded to `down`
+struct Staged {
+    const void *up;
+    void *down;
+    size_t bytes;
+};
+// Operand i lives in HOST_i.  The slots grow to fit, the uploads are enqueued on the context's stream, body(device pointers, HOST_0
+// first) enqueues the work, the downloads follow and the stream is synchronised: the calls hold the context's mutex, so every HOST_*
+// slot is free again when the next one starts.  A failed body downloads nothing.  Zero-byte copies are skipped (an empty operand
+// may have no host buffer).
+template <size_t N, class Body>
+int staged(sr_ctx *c, const Staged (&ops)[N], Body body) {
+    static_assert(N <= HOST_4 - HOST_0 + 1, "one HOST_* slot per operand");
+    for (size_t i = 0; i < N; i++)
+        if (int rc = grow(c, Buf(HOST_0 + i), ops[i].bytes)) return rc;
+    for (size_t i = 0; i < N; i++)
+        if (ops[i].up && ops[i].bytes) HIP_TRY(hipMemcpyAsync(c->buf[HOST_0 + i], ops[i].up, ops[i].bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = body(c->buf + HOST_0)) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    for (size_t i = 0; i < N; i++)
+        if (ops[i].down && ops[i].bytes) HIP_TRY(hipMemcpyAsync(ops[i].down, c->buf[HOST_0 + i], ops[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SR_OK;
+}
+// Sum / Product on host buffers: the n elements go to a device temporary as a whole (like the linear-algebra calls)
+int host_fold(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, bool mul) {
+    if (int rc = check_fold(c, out, in, n)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    return staged(c, {{in, nullptr, n * w}, {nullptr, out, w}}, [&](void *const *d) {
+        const uint64_t *di = (const uint64_t *)d[0];
+        uint64_t *dout = (uint64_t *)d[1];
+        return mul ? dev_product(c, dout, di, n, c->stream) : dev_sum(c, dout, di, n, c->stream);
+    });
+}
+// Host-pointer batches: results = compute(a[, b]) element-wise over the batch, through device staging buffers.
+// Small batches: copy in, compute, copy out on the context's stream.  Large batches are cut into chunks (default 128 MiB per
+// operand, SR_HOST_CHUNK_MB) that alternate between two sets of staging buffers: the calling thread copies chunk i in and
+// launches it while a helper thread copies chunk i-1 out on a second stream, so the two PCIe directions overlap and the device
+// memory needed no longer grows with the batch.  compute(s0, s1, n, stream) works in place on s0 (n elements).
+int host_pipeline(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch,
+                  const std::function<int(uint64_t *, uint64_t *, size_t, hipStream_t)> &compute) {
+    const size_t elem_bytes = c->degree * c->limbs * 8;
+    const size_t bytes = batch * elem_bytes;
+    if (bytes == 0) return SR_OK;
+    // The caller's buffers are ordinary (pageable) host memory -- a Rust Vec -- and stay that way: round 3 registered them with the
+    // HIP runtime for the duration of the call (hipHostRegister), which measured inside the noise (69.8-78.3 against 66.9-73.0 GB/s:
+    // the pipeline is PCIe-bound either way) and had two lifetime hazards (a read-only operand shared by two contexts on two
+    // threads was unregistered by whichever call returned first while the other GPU's DMA still read it; an early error return
+    // unregistered pages under an in-flight copy).  Removed in round 4; SR_PLAN_NO_HOST_PIN is accepted and has no effect.
+    const size_t chunk_mb = c->plan.host_chunk_mb ? c->plan.host_chunk_mb : 128;
+    size_t chunk = (chunk_mb << 20) / elem_bytes;
+    if (chunk == 0) chunk = 1;
+    if (batch <= 2 * chunk) {  // one shot
+        auto run = [&](void *const *d) { return compute((uint64_t *)d[0], (uint64_t *)d[1], batch, c->stream); };
+        return b ? staged(c, {{a, out, bytes}, {b, nullptr, bytes}}, run) : staged(c, {{a, out, bytes}}, run);
+    }
+    const size_t chunk_bytes = chunk * elem_bytes;
+    for (int i = 0; i < 4; i++)
+        if (b || (i & 1) == 0)
+            if (int rc = grow(c, Buf(HOST_0 + i), chunk_bytes)) return rc;
+    hipEvent_t ready[2];
+    for (auto &e : ready) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    struct Job {
+        const void *src;
+        uint64_t *dst;
+        size_t bytes;
+    } jobs[2];
+    std::mutex m;
+    std::condition_variable cv;
+    size_t submitted = 0, done = 0;
+    bool stop = false;
+    hipError_t worker_err = hipSuccess;
+    const int device = c->device;
+    hipStream_t out_stream = c->out_stream;
+    std::thread worker([&] {
+        (void)hipSetDevice(device);
+        for (;;) {
+            Job j;
+            int lane;
+            {
+                std::unique_lock<std::mutex> lk(m);
+                cv.wait(lk, [&] { return done < submitted || stop; });
+                if (done == submitted) return;
+                lane = (int)(done & 1);
+                j = jobs[lane];
+            }
+            hipError_t e = hipStreamWaitEvent(out_stream, ready[lane], 0);
+            if (e == hipSuccess) e = hipMemcpyAsync(j.dst, j.src, j.bytes, hipMemcpyDeviceToHost, out_stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(out_stream);
+            {
+                std::lock_guard<std::mutex> lk(m);
+                if (e != hipSuccess && worker_err == hipSuccess) worker_err = e;
+                done++;
+            }
+            cv.notify_all();
+        }
+    });
+    int rc = SR_OK;
+    hipError_t main_err = hipSuccess;
+    const size_t nchunks = (batch + chunk - 1) / chunk;
+    for (size_t i = 0; i < nchunks && rc == SR_OK && main_err == hipSuccess; i++) {
+        const int lane = (int)(i & 1);
+        const size_t first = i * chunk, n = batch - first < chunk ? batch - first : chunk;
+        {
+            std::unique_lock<std::mutex> lk(m);  // the lane's buffers are free once chunk i - 2 has been copied out
+            cv.wait(lk, [&] { return i < 2 || done + 1 >= i; });
+        }
+        uint64_t *s0 = (uint64_t *)c->buf[HOST_0 + 2 * lane], *s1 = (uint64_t *)c->buf[HOST_1 + 2 * lane];
+        main_err = hipMemcpyAsync(s0, a + first * (elem_bytes / 8), n * elem_bytes, hipMemcpyHostToDevice, c->stream);
+        if (main_err == hipSuccess && b)
+            main_err = hipMemcpyAsync(s1, b + first * (elem_bytes / 8), n * elem_bytes, hipMemcpyHostToDevice, c->stream);
+        if (main_err != hipSuccess) break;
+        rc = compute(s0, s1, n, c->stream);
+        if (rc != SR_OK) break;
+        main_err = hipEventRecord(ready[lane], c->stream);
+        if (main_err != hipSuccess) break;
+        {
+            std::lock_guard<std::mutex> lk(m);
+            jobs[lane] = Job{s0, out + first * (elem_bytes / 8), n * elem_bytes};
+            submitted++;
+        }
+        cv.notify_all();
+    }
+    {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return done == submitted; });
+        stop = true;
+    }
+    cv.notify_all();
+    worker.join();
+    (void)hipStreamSynchronize(c->stream);
+    for (auto &e : ready) (void)hipEventDestroy(e);
+    if (rc != SR_OK) return rc;
+    if (main_err != hipSuccess) return fail(SR_E_HIP, std::string("host pipeline: ") + hipGetErrorString(main_err));
+    if (worker_err != hipSuccess) return fail(SR_E_HIP, std::string("host pipeline (copy out): ") + hipGetErrorString(worker_err));
+    return SR_OK;
+}
+int host_inplace(sr_ctx *c, uint64_t *data, size_t batch, bool fwd) {
+    if (int rc = check(c, {data}, batch)) return rc;
+    const Call call(c);
+    return host_pipeline(c, data, data, nullptr, batch, [&](uint64_t *s0, uint64_t *, size_t n, hipStream_t st) {
+        return fwd ? dev_fwd(c, s0, n, st) : dev_inv(c, s0, n, st);
+    });
+}
+// the unary operators on host buffers: op 0 neg, 1 scale, 2 add scalar (coefficient form), 3 add scalar (NTT form)
+int host_unary(sr_ctx *c, uint64_t *data, const uint64_t *scalar, size_t batch, int op) {
+    if (int rc = check(c, {data, op ? (const void *)scalar : (const void *)1}, batch)) return rc;
+    const Call call(c);
+    return host_pipeline(c, data, data, nullptr, batch, [&](uint64_t *s0, uint64_t *, size_t n, hipStream_t st) {
+        return op == 0 ? dev_neg(c, s0, n, st) : op == 1 ? dev_scale(c, s0, scalar, n, st) : dev_add_scalar(c, s0, scalar, op == 3, n, st);
+    });
+}
+enum { HB_POINTWISE = 0, HB_RING_MUL = 1, HB_ADD = 2, HB_SUB = 3, HB_RING_MUL_NTT_RHS = 4 };
+int host_binary(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch, int op) {
+    if (int rc = check(c, {out, a, b}, batch)) return rc;
+    const Call call(c);
+    return host_pipeline(c, out, a, b, batch, [&](uint64_t *s0, uint64_t *s1, size_t n, hipStream_t st) {
+        return op == HB_RING_MUL ? dev_ring_mul(c, s0, s0, s1, n, st)
+               : op == HB_RING_MUL_NTT_RHS ? dev_ring_mul_ntt_rhs(c, s0, s0, s1, n, st)
+               : op == HB_POINTWISE ? dev_pointwise(c, s0, s1, n, st)
+                                    : dev_addsub(c, s0, s1, n, op == HB_SUB, st);
+    });
+}
+// ---- packed-u32 boundary (BabyBear power-of-two rings; csrc/packed32.hpp) ----------------------------------------------------
+// check() of a packed-u32 entry point: the ring is tested between the buffers and the element count
+int check_packed(sr_ctx *c, std::initializer_list<const void *> bufs, size_t batch) {
+    if (int rc = check(c, bufs)) return rc;
+    if (c->ring != SR_RING_BABYBEAR_POW2) return fail(SR_E_INVALID, "packed32 entry points: BabyBear power-of-two rings only");
+    return check_count(c, batch);
+}
+int launch_pack32(sr_ctx *c, uint32_t *out, const uint64_t *in, size_t n, hipStream_t st) {
+    if (n == 0) return SR_OK;
+    ProfScope ps(c, st, K_OTHER);
+    hipLaunchKernelGGL(sr::p32::pack32_kernel, dim3(sr::p32::blocks_for(n)), dim3(256), 0, st, out, in, n);
+    HIP_TRY(hipGetLastError());
+    return SR_OK;
+}
+int launch_unpack32(sr_ctx *c, uint64_t *out, const uint32_t *in, size_t n, hipStream_t st) {
+    if (n == 0) return SR_OK;
+    ProfScope ps(c, st, K_OTHER);
+    hipLaunchKernelGGL(sr::p32::unpack32_kernel, dim3(sr::p32::blocks_for(n)), dim3(256), 0, st, out, in, n);
+    HIP_TRY(hipGetLastError());
+    return SR_OK;
+}
+// D < 4096 has no register-tiled path: such (small) batches are widened into the context's staging buffers, run through the 8-byte
+// kernels and narrowed again -- same values, only the traffic advantage is lost where it does not matter
+template <class Fn>
+int packed_via_wide(sr_ctx *c, uint32_t *out, const uint32_t *a, const uint32_t *b, size_t batch, hipStream_t st, Fn run) {
+    const size_t n = batch << c->k;
+    if (int rc = grow(c, WIDE_A, n * 8, st)) return rc;
+    if (b)
+        if (int rc = grow(c, WIDE_B, n * 8, st)) return rc;
+    ScratchUse su(c, st);  // the staging buffers belong to the context, the call may arrive on any stream: ordered like the operand scratch
+    if (int rc = su.acquire()) return rc;
+    uint64_t *wa = (uint64_t *)c->buf[WIDE_A], *wb = (uint64_t *)c->buf[WIDE_B];
+    if (int rc = launch_unpack32(c, wa, a, n, st)) return rc;
+    if (b)
+        if (int rc = launch_unpack32(c, wb, b, n, st)) return rc;
+    if (int rc = run(wa, wb)) return rc;
+    return launch_pack32(c, out, wa, n, st);
+}
+int packed_elementwise(sr_ctx *c, uint32_t *l, const uint32_t *r, size_t batch, void *stream, int op) {
+    if (int rc = check_packed(c, {l, r}, batch)) return rc;
+    const Call call(c, stream);
+    const size_t n = batch << c->k;
+    if (n == 0) return SR_OK;
+    ProfScope ps(c, call.st, K_POINTWISE);
+    const dim3 gr(sr::p32::blocks_for(n)), bl(256);
+    if (op == 0) hipLaunchKernelGGL(sr::p32::elementwise32_kernel<0>, gr, bl, 0, call.st, l, r, n);
+    else if (op == 1) hipLaunchKernelGGL(sr::p32::elementwise32_kernel<1>, gr, bl, 0, call.st, l, r, n);
+    else hipLaunchKernelGGL(sr::p32::elementwise32_kernel<2>, gr, bl, 0, call.st, l, r, n);
+    HIP_TRY(hipGetLastError());
+    return SR_OK;
+}
+// ---- host-side self-test hook: runs the SAME __host__ __device__ field routines the kernels use,
+// on the host, one scalar operation per call.  Lets the CPU test-suite check fields.hpp without a
+// GPU.  Not a compute path: no batch entry point routes through it.
+// op: 0 add, 1 sub, 2 mul_boundary (a*b*R_b^-1 on in-memory images), 3 mul_tw, 4 tw_from_u64(a[0])
+template <class F>
+int selftest_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out) {
+    using S = typename F::storage;
+    typename F::elem x = F::load(reinterpret_cast<const S *>(a)), y = F::load(reinterpret_cast<const S *>(b)), r;
+    switch (op) {
+        case 0: r = F::add(x, y); break;
+        case 1: r = F::sub(x, y); break;
+        case 2: r = F::mul_boundary(x, y); break;
+        case 3: r = F::mul_tw(x, y); break;
+        case 4: r = F::tw_from_u64(a[0]); break;
+        default: return fail(SR_E_INVALID, "selftest: unknown op");
+    }
+    F::store(reinterpret_cast<S *>(out), r);
+    return SR_OK;
+}
+// StarkL (stark_lazy.hpp): 0 add, 1 sub, 3 mul_tw, 4 table form, 5 a chain of six lazy additions and subtractions feeding
+// mul_tw and mul_data, 6 repeated quadrupling with weak reductions, 7 / 8 signed combinations -- results leave through the
+// canonicalising store
+int selftest_lazy(int op, const uint64_t *a, const uint64_t *b, uint64_t *out) {
+    using F = sr::StarkL;
+    using S = F::storage;
+    F::elem x = F::load(reinterpret_cast<const S *>(a)), y = F::load(reinterpret_cast<const S *>(b)), r;
+    switch (op) {
+        case 0: r = F::add(x, y); break;
+        case 1: r = F::sub(x, y); break;
+        case 3: r = F::mul_tw(x, y); break;
+        case 4: r = F::tw_from_u64(a[0]); break;
+        case 5: {
+            F::elem s = x, d = x;
+            for (int i = 0; i < 6; i++) {
+                s = F::add(s, y);
+                d = F::sub(d, y);
+            }
+            r = F::add(F::mul_tw(s, y), F::mul_data(d, s));
+            break;
+        }
+        case 6: {
+            r = x;
+            for (int i = 0; i < 4; i++) r = F::weak_reduce(F::add(F::add(r, r), F::add(r, r)));  // 256 a, reduced weakly on the way
+            break;
+        }
+        case 7: {  // 3 a - 5 b and, case 8, 7 a - 2 b without any carry in between: canonical() on signed lazy states
+            r = F::sub(F::add(F::add(x, x), x), F::add(F::add(F::add(y, y), F::add(y, y)), y));
+            break;
+        }
+        case 8: {
+            F::elem x2 = F::add(x, x), x4 = F::add(x2, x2);
+            r = F::sub(F::add(F::add(x4, x2), x), F::add(y, y));
+            break;
+        }
+        default: return fail(SR_E_INVALID, "selftest: unknown op");
+    }
+    F::store(reinterpret_cast<S *>(out), r);
+    return SR_OK;
+}
+// op 5, field 0: the compile-time shift product of the tuned Goldilocks path, gl::mul_pow2<E>(a[0]) with E = b[0] in [1, 95]
+template <int... Es>
+uint64_t mul_pow2_any(uint64_t x, int e, std::integer_sequence<int, Es...>) {
+    uint64_t r = 0;
+    ((e == Es + 1 ? (r = sr::gl::mul_pow2<Es + 1>(x), 0) : 0), ...);
+    return r;
+}
 }  // namespace
 
 // ===============================================================================================
@@ -1633,8 +1940,7 @@ int sr_ctx_twiddle_block(sr_ctx *c, void **dev_ptr, size_t *bytes) {
 }
 int sr_ctx_twiddles_updated(sr_ctx *c) {
     if (!c) return fail(SR_E_INVALID, "null context");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    const Call call(c);
     HIP_TRY(hipDeviceSynchronize());  // every table (generic and tuned) lives in the one block: nothing to rebuild
     return SR_OK;
 }
@@ -1677,207 +1983,145 @@ int sr_shard_range(size_t batch, int n, int i, size_t *first, size_t *count) {
 
 // ---- device-resident entry points ----
 int sr_ntt_fwd_batch_dev(sr_ctx *c, uint64_t *d, size_t batch, void *stream) {
-    if (int rc = check(c, d)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_fwd(c, d, batch, (hipStream_t)stream);
+    if (int rc = check(c, {d}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_fwd(c, d, batch, call.st);
 }
 int sr_ntt_inv_batch_dev(sr_ctx *c, uint64_t *d, size_t batch, void *stream) {
-    if (int rc = check(c, d)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_inv(c, d, batch, (hipStream_t)stream);
+    if (int rc = check(c, {d}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_inv(c, d, batch, call.st);
 }
 int sr_pointwise_mul_batch_dev(sr_ctx *c, uint64_t *l, const uint64_t *r, size_t batch, void *stream) {
-    if (int rc = check(c, l, r)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_pointwise(c, l, r, batch, (hipStream_t)stream);
+    if (int rc = check(c, {l, r}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_pointwise(c, l, r, batch, call.st);
 }
 int sr_mul_elem_batch_dev(sr_ctx *c, uint64_t *d, const uint64_t *elem, size_t batch, void *stream) {
-    if (int rc = check(c, d, elem)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check(c, {d, elem}, batch)) return rc;
     const uintptr_t w = (uintptr_t)c->degree * c->limbs * 8, pe = (uintptr_t)elem, pd = (uintptr_t)d;
     if (pe + w > pd && pd + batch * w > pe) return fail(SR_E_INVALID, "mul_elem: the element must not lie inside the batch it multiplies");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_mul_elem(c, d, elem, batch, (hipStream_t)stream);
-}
-static int check_fold(sr_ctx *c, const uint64_t *out, const uint64_t *in, size_t n) {
-    if (int rc = check(c, out, n ? (const void *)in : (const void *)1)) return rc;
-    if (int rc = check_count(c, n)) return rc;
-    const uintptr_t w = (uintptr_t)c->degree * c->limbs * 8, po = (uintptr_t)out, pi = (uintptr_t)in;
-    if (n && po + w > pi && pi + n * w > po) return fail(SR_E_INVALID, "sum / product: out must not overlap the input elements");
-    return SR_OK;
+    const Call call(c, stream);
+    return dev_mul_elem(c, d, elem, batch, call.st);
 }
 int sr_sum_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, void *stream) {
     if (int rc = check_fold(c, out, in, n)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_sum(c, out, in, n, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_sum(c, out, in, n, call.st);
 }
 int sr_product_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, void *stream) {
     if (int rc = check_fold(c, out, in, n)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_product(c, out, in, n, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_product(c, out, in, n, call.st);
 }
 int sr_add_batch_dev(sr_ctx *c, uint64_t *l, const uint64_t *r, size_t batch, void *stream) {
-    if (int rc = check(c, l, r)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_addsub(c, l, r, batch, false, (hipStream_t)stream);
+    if (int rc = check(c, {l, r}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_addsub(c, l, r, batch, false, call.st);
 }
 int sr_sub_batch_dev(sr_ctx *c, uint64_t *l, const uint64_t *r, size_t batch, void *stream) {
-    if (int rc = check(c, l, r)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_addsub(c, l, r, batch, true, (hipStream_t)stream);
+    if (int rc = check(c, {l, r}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_addsub(c, l, r, batch, true, call.st);
 }
 int sr_neg_batch_dev(sr_ctx *c, uint64_t *d, size_t batch, void *stream) {
-    if (int rc = check(c, d)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_neg(c, d, batch, (hipStream_t)stream);
+    if (int rc = check(c, {d}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_neg(c, d, batch, call.st);
 }
 int sr_scale_batch_dev(sr_ctx *c, uint64_t *d, const uint64_t *scalar, size_t batch, void *stream) {
-    if (int rc = check(c, d, scalar)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_scale(c, d, scalar, batch, (hipStream_t)stream);
+    if (int rc = check(c, {d, scalar}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_scale(c, d, scalar, batch, call.st);
 }
 int sr_add_scalar_batch_dev(sr_ctx *c, uint64_t *d, const uint64_t *scalar, int ntt_form, size_t batch, void *stream) {
-    if (int rc = check(c, d, scalar)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_add_scalar(c, d, scalar, ntt_form != 0, batch, (hipStream_t)stream);
+    if (int rc = check(c, {d, scalar}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_add_scalar(c, d, scalar, ntt_form != 0, batch, call.st);
 }
 int sr_matvec_ntt_dev(sr_ctx *c, uint64_t *y, const uint64_t *m, const uint64_t *v, size_t nrows, size_t ncols, void *stream) {
-    if (int rc = check(c, y, m, v)) return rc;
-    if (check_count(c, nrows, ncols)) return SR_E_INVALID;
+    if (int rc = check(c, {y, m, v}, nrows, ncols)) return rc;
     if (y == m || y == v) return fail(SR_E_INVALID, "matvec: y must not alias M or v");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_matvec(c, y, m, v, nrows, ncols, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_matvec(c, y, m, v, nrows, ncols, call.st);
 }
 int sr_spmv_ntt_dev(sr_ctx *c, uint64_t *y, const uint64_t *vals, const uint32_t *cols, const uint64_t *row_ptr, const uint64_t *v,
                     size_t nrows, size_t ncols, void *stream) {
-    if (int rc = check(c, y, row_ptr, v)) return rc;
-    if (check_count(c, nrows) || check_count(c, ncols)) return SR_E_INVALID;   // the dense product nrows * ncols is irrelevant here
+    if (int rc = check(c, {y, row_ptr, v}, nrows)) return rc;
+    if (int rc = check_count(c, ncols)) return rc;   // the dense product nrows * ncols is irrelevant here
     if (y == v || y == vals) return fail(SR_E_INVALID, "spmv: y must not alias the matrix or v");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_spmv(c, y, vals, cols, row_ptr, v, nrows, ncols, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_spmv(c, y, vals, cols, row_ptr, v, nrows, ncols, call.st);
 }
 int sr_spmv_bad_index_count(sr_ctx *c, unsigned long long *out, void *stream) {
-    if (int rc = check(c, out)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(out, c->d_counter + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(c->d_counter + 1, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SR_OK;
+    if (int rc = check(c, {out})) return rc;
+    const Call call(c, stream);
+    return read_counter(c, 1, out, call.st);
 }
 int sr_matmul_ntt_dev(sr_ctx *c, uint64_t *y, const uint64_t *a, const uint64_t *b, size_t n, size_t m, size_t p, void *stream) {
-    if (int rc = check(c, y, a, b)) return rc;
-    if (check_count(c, n, m) || check_count(c, m, p) || check_count(c, n, p)) return SR_E_INVALID;
+    if (int rc = check(c, {y, a, b}, n, m)) return rc;
+    if (check_count(c, m, p) || check_count(c, n, p)) return SR_E_INVALID;
     if (y == a || y == b) return fail(SR_E_INVALID, "matmul: y must not alias A or B");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_matmul(c, y, a, b, n, m, p, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_matmul(c, y, a, b, n, m, p, call.st);
 }
 
 int sr_rot_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t batch, void *stream) {
-    if (int rc = check(c, out, in)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check(c, {out, in}, batch)) return rc;
     if (out == in) return fail(SR_E_INVALID, "rot: out must not alias in");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_rot(c, out, in, batch, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_rot(c, out, in, batch, call.st);
 }
 int sr_rot_batch(sr_ctx *c, uint64_t *data, size_t batch) {
-    if (int rc = check(c, data)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {data}, batch)) return rc;
+    const Call call(c);
     const size_t bytes = batch * c->degree * c->limbs * 8;
     if (bytes == 0) return SR_OK;
-    if (int rc = grow(c, HOST_0, bytes)) return rc;
-    if (int rc = grow(c, HOST_1, bytes)) return rc;
-    HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], data, bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_rot(c, (uint64_t *)c->buf[HOST_1], (const uint64_t *)c->buf[HOST_0], batch, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(data, c->buf[HOST_1], bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    return staged(c, {{data, nullptr, bytes}, {nullptr, data, bytes}}, [&](void *const *d) {
+        return dev_rot(c, (uint64_t *)d[1], (const uint64_t *)d[0], batch, c->stream);
+    });
 }
 size_t sr_wire_coeff_bytes(const sr_ctx *c) { return c ? wire_coeff_bytes(c) : 0; }
 int sr_serialize_batch_dev(sr_ctx *c, uint8_t *wire, const uint64_t *in, const uint64_t *offsets, size_t batch, void *stream) {
-    if (int rc = check(c, wire, in)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check(c, {wire, in}, batch)) return rc;
     if ((const void *)wire == (const void *)in) return fail(SR_E_INVALID, "serialize: wire must not alias in");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_wire(c, true, wire, in, offsets, batch, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_wire(c, true, wire, in, offsets, batch, call.st);
 }
 int sr_deserialize_batch_dev(sr_ctx *c, uint64_t *out, const uint8_t *wire, const uint64_t *offsets, size_t batch, void *stream) {
-    if (int rc = check(c, out, wire)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check(c, {out, wire}, batch)) return rc;
     if ((const void *)wire == (const void *)out) return fail(SR_E_INVALID, "deserialize: out must not alias wire");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_wire(c, false, out, wire, offsets, batch, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_wire(c, false, out, wire, offsets, batch, call.st);
 }
 int sr_wire_invalid_count(sr_ctx *c, unsigned long long *out, void *stream) {
-    if (int rc = check(c, out)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(out, c->d_counter + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SR_OK;
+    if (int rc = check(c, {out})) return rc;
+    const Call call(c, stream);
+    return read_counter(c, 3, out, call.st);
 }
 int sr_decompose_balanced_batch_wide_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t basis_lo, uint64_t basis_hi,
                                          size_t padding_size, size_t batch, void *stream) {
-    if (int rc = check(c, out, in)) return rc;
-    if (int rc = check_count(c, batch, padding_size)) return rc;
+    if (int rc = check(c, {out, in}, batch, padding_size)) return rc;
     if (int rc = check_basis_wide(basis_lo, basis_hi)) return rc;
     if (out == in) return fail(SR_E_INVALID, "decompose: out must not alias in");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_decompose_any(c, out, in, basis_lo, basis_hi, padding_size, batch, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_decompose_any(c, out, in, basis_lo, basis_hi, padding_size, batch, call.st);
 }
 int sr_decompose_balanced_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t basis, size_t padding_size, size_t batch,
                                     void *stream) {
     return sr_decompose_balanced_batch_wide_dev(c, out, in, basis, 0, padding_size, batch, stream);
 }
 int sr_decompose_overflow_count(sr_ctx *c, unsigned long long *out, void *stream) {
-    if (int rc = check(c, out)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(out, c->d_counter + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(c->d_counter + 2, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SR_OK;
+    if (int rc = check(c, {out})) return rc;
+    const Call call(c, stream);
+    return read_counter(c, 2, out, call.st);
 }
 int sr_recompose_batch_wide_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t basis_lo, uint64_t basis_hi, size_t padding_size,
                                 size_t batch_out, void *stream) {
-    if (int rc = check(c, out, in)) return rc;
-    if (int rc = check_count(c, batch_out, padding_size)) return rc;
+    if (int rc = check(c, {out, in}, batch_out, padding_size)) return rc;
     if (out == in) return fail(SR_E_INVALID, "recompose: out must not alias in");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_recompose_any(c, out, in, basis_lo, basis_hi, padding_size, batch_out, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_recompose_any(c, out, in, basis_lo, basis_hi, padding_size, batch_out, call.st);
 }
 int sr_recompose_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t basis, size_t padding_size, size_t batch_out,
                            void *stream) {
@@ -1885,91 +2129,42 @@ int sr_recompose_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_
 }
 
 // ---- host-pointer variants of the linear-algebra entry points (convenience entry points for callers that hold Vec<..> on the
-// host; resident data uses the _dev forms): their device temporaries are the context's HOST_* buffers (the calls hold the context
-// mutex and end with a stream synchronisation, so a buffer is free again when the next call starts)
+// host; resident data uses the _dev forms)
 int sr_matmul_ntt(sr_ctx *c, uint64_t *y, const uint64_t *a, const uint64_t *b, size_t n, size_t m, size_t p) {
-    if (int rc = check(c, y, a, b)) return rc;
-    if (check_count(c, n, m) || check_count(c, m, p) || check_count(c, n, p)) return SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {y, a, b}, n, m)) return rc;
+    if (check_count(c, m, p) || check_count(c, n, p)) return SR_E_INVALID;
+    const Call call(c);
     const size_t w = c->degree * c->limbs * 8;
-    if (int rc = grow(c, HOST_0, n * m * w)) return rc;
-    if (int rc = grow(c, HOST_1, m * p * w)) return rc;
-    if (int rc = grow(c, HOST_2, n * p * w)) return rc;
-    uint64_t *da = (uint64_t *)c->buf[HOST_0], *db = (uint64_t *)c->buf[HOST_1], *dy = (uint64_t *)c->buf[HOST_2];
-    if (n * m) HIP_TRY(hipMemcpyAsync(da, a, n * m * w, hipMemcpyHostToDevice, c->stream));
-    if (m * p) HIP_TRY(hipMemcpyAsync(db, b, m * p * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_matmul(c, dy, da, db, n, m, p, c->stream)) return rc;
-    if (n * p) HIP_TRY(hipMemcpyAsync(y, dy, n * p * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    return staged(c, {{a, nullptr, n * m * w}, {b, nullptr, m * p * w}, {nullptr, y, n * p * w}}, [&](void *const *d) {
+        return dev_matmul(c, (uint64_t *)d[2], (const uint64_t *)d[0], (const uint64_t *)d[1], n, m, p, c->stream);
+    });
 }
 int sr_matvec_ntt(sr_ctx *c, uint64_t *y, const uint64_t *m, const uint64_t *v, size_t nrows, size_t ncols) {
-    if (int rc = check(c, y, m, v)) return rc;
-    if (check_count(c, nrows, ncols)) return SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {y, m, v}, nrows, ncols)) return rc;
+    const Call call(c);
     const size_t w = c->degree * c->limbs * 8;
-    if (int rc = grow(c, HOST_0, nrows * ncols * w)) return rc;
-    if (int rc = grow(c, HOST_1, ncols * w)) return rc;
-    if (int rc = grow(c, HOST_2, nrows * w)) return rc;
-    uint64_t *dm = (uint64_t *)c->buf[HOST_0], *dv = (uint64_t *)c->buf[HOST_1], *dy = (uint64_t *)c->buf[HOST_2];
-    if (nrows * ncols) HIP_TRY(hipMemcpyAsync(dm, m, nrows * ncols * w, hipMemcpyHostToDevice, c->stream));
-    if (ncols) HIP_TRY(hipMemcpyAsync(dv, v, ncols * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_matvec(c, dy, dm, dv, nrows, ncols, c->stream)) return rc;
-    if (nrows) HIP_TRY(hipMemcpyAsync(y, dy, nrows * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    return staged(c, {{m, nullptr, nrows * ncols * w}, {v, nullptr, ncols * w}, {nullptr, y, nrows * w}}, [&](void *const *d) {
+        return dev_matvec(c, (uint64_t *)d[2], (const uint64_t *)d[0], (const uint64_t *)d[1], nrows, ncols, c->stream);
+    });
 }
 int sr_spmv_ntt(sr_ctx *c, uint64_t *y, const uint64_t *vals, const uint32_t *cols, const uint64_t *row_ptr, const uint64_t *v,
                 size_t nrows, size_t ncols) {
-    if (int rc = check(c, y, row_ptr, v)) return rc;
-    if (check_count(c, nrows) || check_count(c, ncols)) return SR_E_INVALID;
+    if (int rc = check(c, {y, row_ptr, v}, nrows)) return rc;
+    if (int rc = check_count(c, ncols)) return rc;
     const size_t nnz = (size_t)row_ptr[nrows];
     if (nnz && (!vals || !cols)) return fail(SR_E_INVALID, "null buffer");
     for (size_t r = 0; r < nrows; r++)
         if (row_ptr[r] > row_ptr[r + 1]) return fail(SR_E_INVALID, "spmv: row_ptr is not monotone");
     for (size_t j = 0; j < nnz; j++)  // the reference indexes v[col] and panics when out of range (sparse_matrix.rs:208)
         if (cols[j] >= ncols) return fail(SR_E_INVALID, "spmv: column index out of range");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    const Call call(c);
     const size_t w = c->degree * c->limbs * 8;
-    if (int rc = grow(c, HOST_0, nnz * w)) return rc;
-    if (int rc = grow(c, HOST_1, nnz * 4)) return rc;
-    if (int rc = grow(c, HOST_2, (nrows + 1) * 8)) return rc;
-    if (int rc = grow(c, HOST_3, ncols * w)) return rc;
-    if (int rc = grow(c, HOST_4, nrows * w)) return rc;
-    uint64_t *dvals = (uint64_t *)c->buf[HOST_0], *dptr = (uint64_t *)c->buf[HOST_2], *dv = (uint64_t *)c->buf[HOST_3];
-    uint64_t *dy = (uint64_t *)c->buf[HOST_4];
-    uint32_t *dcols = (uint32_t *)c->buf[HOST_1];
-    if (nnz) {
-        HIP_TRY(hipMemcpyAsync(dvals, vals, nnz * w, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(dcols, cols, nnz * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(dptr, row_ptr, (nrows + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (ncols) HIP_TRY(hipMemcpyAsync(dv, v, ncols * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_spmv(c, dy, dvals, dcols, dptr, dv, nrows, ncols, c->stream)) return rc;
-    if (nrows) HIP_TRY(hipMemcpyAsync(y, dy, nrows * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
-}
-// Sum / Product on host buffers: the n elements go to a device temporary as a whole (like the linear-algebra calls above)
-static int host_fold(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, bool mul) {
-    if (int rc = check_fold(c, out, in, n)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    if (int rc = grow(c, HOST_0, n * w)) return rc;
-    if (int rc = grow(c, HOST_1, w)) return rc;
-    uint64_t *di = (uint64_t *)c->buf[HOST_0], *dout = (uint64_t *)c->buf[HOST_1];
-    if (n) HIP_TRY(hipMemcpyAsync(di, in, n * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = mul ? dev_product(c, dout, di, n, c->stream) : dev_sum(c, dout, di, n, c->stream)) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, dout, w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    const Staged ops[] = {{vals, nullptr, nnz * w}, {cols, nullptr, nnz * 4}, {row_ptr, nullptr, (nrows + 1) * 8}, {v, nullptr, ncols * w},
+                          {nullptr, y, nrows * w}};
+    return staged(c, ops, [&](void *const *d) {
+        return dev_spmv(c, (uint64_t *)d[4], (const uint64_t *)d[0], (const uint32_t *)d[1], (const uint64_t *)d[2], (const uint64_t *)d[3],
+                        nrows, ncols, c->stream);
+    });
 }
 int sr_sum_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n) { return host_fold(c, out, in, n, false); }
 int sr_product_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n) { return host_fold(c, out, in, n, true); }
@@ -1978,106 +2173,74 @@ int sr_decompose_balanced_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, ui
 }
 int sr_decompose_balanced_batch_wide(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t basis, uint64_t basis_hi, size_t padding_size,
                                      size_t batch) {
-    if (int rc = check(c, out, in)) return rc;
-    if (int rc = check_count(c, batch, padding_size)) return rc;
+    if (int rc = check(c, {out, in}, batch, padding_size)) return rc;
     if (int rc = check_basis_wide(basis, basis_hi)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    const Call call(c);
     const size_t w = c->degree * c->limbs * 8;
     if (batch == 0 || padding_size == 0) return SR_OK;
-    if (int rc = grow(c, HOST_0, batch * w)) return rc;
-    if (int rc = grow(c, HOST_1, batch * padding_size * w)) return rc;
-    uint64_t *din = (uint64_t *)c->buf[HOST_0], *dout = (uint64_t *)c->buf[HOST_1];
-    HIP_TRY(hipMemcpyAsync(din, in, batch * w, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_counter + 2, 0, sizeof(unsigned long long), c->stream));
-    if (int rc = dev_decompose_any(c, dout, din, basis, basis_hi, padding_size, batch, c->stream)) return rc;
+    int rc = staged(c, {{in, nullptr, batch * w}, {nullptr, out, batch * padding_size * w}}, [&](void *const *d) {
+        HIP_TRY(hipMemsetAsync(c->d_counter + 2, 0, sizeof(unsigned long long), c->stream));
+        return dev_decompose_any(c, (uint64_t *)d[1], (const uint64_t *)d[0], basis, basis_hi, padding_size, batch, c->stream);
+    });
     unsigned long long over = 0;
-    HIP_TRY(hipMemcpyAsync(&over, c->d_counter + 2, sizeof over, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out, dout, batch * padding_size * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_counter + 2, 0, sizeof(unsigned long long), c->stream));
-    // the reference indexes out[padding_size] and panics (mod.rs:81-91)
+    if (rc == SR_OK) rc = read_counter(c, 2, &over, c->stream);
+    if (rc) return rc;
+    // the digits are written; the reference indexes out[padding_size] and panics (mod.rs:81-91)
     if (over) return fail(SR_E_INVALID, "decompose: a coefficient needs more than padding_size digits");
     return SR_OK;
 }
 int sr_serialize_batch(sr_ctx *c, uint8_t *wire, const uint64_t *in, size_t batch) {
-    if (int rc = check(c, wire, in)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {wire, in}, batch)) return rc;
+    const Call call(c);
     const size_t n = batch * c->degree;
     if (n == 0) return SR_OK;
-    if (int rc = grow(c, HOST_0, n * c->limbs * 8)) return rc;
-    if (int rc = grow(c, HOST_1, n * wire_coeff_bytes(c))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], in, n * c->limbs * 8, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_wire(c, true, c->buf[HOST_1], c->buf[HOST_0], nullptr, batch, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(wire, c->buf[HOST_1], n * wire_coeff_bytes(c), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    return staged(c, {{in, nullptr, n * c->limbs * 8}, {nullptr, wire, n * wire_coeff_bytes(c)}}, [&](void *const *d) {
+        return dev_wire(c, true, d[1], d[0], nullptr, batch, c->stream);
+    });
 }
 int sr_deserialize_batch(sr_ctx *c, uint64_t *out, const uint8_t *wire, size_t batch) {
-    if (int rc = check(c, out, wire)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {out, wire}, batch)) return rc;
+    const Call call(c);
     const size_t n = batch * c->degree;
     if (n == 0) return SR_OK;
-    if (int rc = grow(c, HOST_0, n * c->limbs * 8)) return rc;
-    if (int rc = grow(c, HOST_1, n * wire_coeff_bytes(c))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->buf[HOST_1], wire, n * wire_coeff_bytes(c), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
-    if (int rc = dev_wire(c, false, c->buf[HOST_0], c->buf[HOST_1], nullptr, batch, c->stream)) return rc;
-    unsigned long long bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, c->d_counter + 3, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
-    // Fp::deserialize_with_flags: from_bigint(..) is None for an integer >= p -> SerializationError::InvalidData
-    if (bad) return fail(SR_E_INVALID, "deserialize: a coefficient is not below the modulus (InvalidData)");
-    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_0], n * c->limbs * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    return staged(c, {{nullptr, out, n * c->limbs * 8}, {wire, nullptr, n * wire_coeff_bytes(c)}}, [&](void *const *d) -> int {
+        HIP_TRY(hipMemsetAsync(c->d_counter + 3, 0, sizeof(unsigned long long), c->stream));
+        if (int rc = dev_wire(c, false, d[0], d[1], nullptr, batch, c->stream)) return rc;
+        unsigned long long bad = 0;
+        if (int rc = read_counter(c, 3, &bad, c->stream)) return rc;
+        // Fp::deserialize_with_flags: from_bigint(..) is None for an integer >= p -> SerializationError::InvalidData (out not written)
+        if (bad) return fail(SR_E_INVALID, "deserialize: a coefficient is not below the modulus (InvalidData)");
+        return SR_OK;
+    });
 }
 int sr_recompose_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t basis, size_t padding_size, size_t batch_out) {
     return sr_recompose_batch_wide(c, out, in, basis, 0, padding_size, batch_out);
 }
 int sr_recompose_batch_wide(sr_ctx *c, uint64_t *out, const uint64_t *in, uint64_t basis, uint64_t basis_hi, size_t padding_size,
                             size_t batch_out) {
-    if (int rc = check(c, out, in)) return rc;
-    if (int rc = check_count(c, batch_out, padding_size)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {out, in}, batch_out, padding_size)) return rc;
+    const Call call(c);
     const size_t w = c->degree * c->limbs * 8;
     if (batch_out == 0) return SR_OK;
-    if (int rc = grow(c, HOST_0, batch_out * padding_size * w)) return rc;
-    if (int rc = grow(c, HOST_1, batch_out * w)) return rc;
-    uint64_t *din = (uint64_t *)c->buf[HOST_0], *dout = (uint64_t *)c->buf[HOST_1];
-    if (padding_size) HIP_TRY(hipMemcpyAsync(din, in, batch_out * padding_size * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_recompose_any(c, dout, din, basis, basis_hi, padding_size, batch_out, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, dout, batch_out * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    return staged(c, {{in, nullptr, batch_out * padding_size * w}, {nullptr, out, batch_out * w}}, [&](void *const *d) {
+        return dev_recompose_any(c, (uint64_t *)d[1], (const uint64_t *)d[0], basis, basis_hi, padding_size, batch_out, c->stream);
+    });
 }
 int sr_ring_mul_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch, void *stream) {
-    if (int rc = check(c, out, a, b)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check(c, {out, a, b}, batch)) return rc;
     if (b == out) return fail(SR_E_INVALID, "ring_mul: b must not alias out");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_ring_mul(c, out, a, b, batch, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_ring_mul(c, out, a, b, batch, call.st);
 }
 int sr_ring_mul_ntt_rhs_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b_ntt, size_t batch, void *stream) {
-    if (int rc = check(c, out, a, b_ntt)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check(c, {out, a, b_ntt}, batch)) return rc;
     if (b_ntt == out) return fail(SR_E_INVALID, "ring_mul_ntt_rhs: b_ntt must not alias out");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_ring_mul_ntt_rhs(c, out, a, b_ntt, batch, (hipStream_t)stream);
+    const Call call(c, stream);
+    return dev_ring_mul_ntt_rhs(c, out, a, b_ntt, batch, call.st);
 }
 int sr_ctx_reserve_scratch(sr_ctx *c, size_t batch) {
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {}, batch)) return rc;
+    const Call call(c);
     if (batch == 0) return SR_OK;
     // the two partial-element buffers of sr_sum_batch_dev / sr_product_batch_dev (a few MiB; the small rings' product tree sizes FOLD_0
     // by the slice length on first use)
@@ -2119,112 +2282,37 @@ int sr_ctx_reserve_scratch(sr_ctx *c, size_t batch) {
     }
     return grow(c, OPERAND_A, scratch_polys(c, batch, elem) * elem, nullptr, true);
 }
-// ---- packed-u32 boundary (BabyBear power-of-two rings; csrc/packed32.hpp) ----------------------------------------------------
-extern "C++" {
-namespace {
-int check_packed(sr_ctx *c) {
-    if (c->ring != SR_RING_BABYBEAR_POW2) return fail(SR_E_INVALID, "packed32 entry points: BabyBear power-of-two rings only");
-    return SR_OK;
-}
-int launch_pack32(sr_ctx *c, uint32_t *out, const uint64_t *in, size_t n, hipStream_t st) {
-    if (n == 0) return SR_OK;
-    ProfScope ps(c, st, K_OTHER);
-    hipLaunchKernelGGL(sr::p32::pack32_kernel, dim3(sr::p32::blocks_for(n)), dim3(256), 0, st, out, in, n);
-    HIP_TRY(hipGetLastError());
-    return SR_OK;
-}
-int launch_unpack32(sr_ctx *c, uint64_t *out, const uint32_t *in, size_t n, hipStream_t st) {
-    if (n == 0) return SR_OK;
-    ProfScope ps(c, st, K_OTHER);
-    hipLaunchKernelGGL(sr::p32::unpack32_kernel, dim3(sr::p32::blocks_for(n)), dim3(256), 0, st, out, in, n);
-    HIP_TRY(hipGetLastError());
-    return SR_OK;
-}
-// D < 4096 has no register-tiled path: such (small) batches are widened into the context's staging buffers, run through the 8-byte
-// kernels and narrowed again -- same values, only the traffic advantage is lost where it does not matter
-template <class Fn>
-int packed_via_wide(sr_ctx *c, uint32_t *out, const uint32_t *a, const uint32_t *b, size_t batch, hipStream_t st, Fn run) {
-    const size_t n = batch << c->k;
-    if (int rc = grow(c, WIDE_A, n * 8, st)) return rc;
-    if (b)
-        if (int rc = grow(c, WIDE_B, n * 8, st)) return rc;
-    ScratchUse su(c, st);  // the staging buffers belong to the context, the call may arrive on any stream: ordered like the operand scratch
-    if (int rc = su.acquire()) return rc;
-    uint64_t *wa = (uint64_t *)c->buf[WIDE_A], *wb = (uint64_t *)c->buf[WIDE_B];
-    if (int rc = launch_unpack32(c, wa, a, n, st)) return rc;
-    if (b)
-        if (int rc = launch_unpack32(c, wb, b, n, st)) return rc;
-    if (int rc = run(wa, wb)) return rc;
-    return launch_pack32(c, out, wa, n, st);
-}
-}  // namespace
-}  // extern "C++"
 int sr_pack32_batch_dev(sr_ctx *c, uint32_t *d_out, const uint64_t *d_in, size_t batch, void *stream) {
-    if (int rc = check(c, d_out, d_in)) return rc;
-    if (int rc = check_packed(c)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return launch_pack32(c, d_out, d_in, batch << c->k, (hipStream_t)stream);
+    if (int rc = check_packed(c, {d_out, d_in}, batch)) return rc;
+    const Call call(c, stream);
+    return launch_pack32(c, d_out, d_in, batch << c->k, call.st);
 }
 int sr_unpack32_batch_dev(sr_ctx *c, uint64_t *d_out, const uint32_t *d_in, size_t batch, void *stream) {
-    if (int rc = check(c, d_out, d_in)) return rc;
-    if (int rc = check_packed(c)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return launch_unpack32(c, d_out, d_in, batch << c->k, (hipStream_t)stream);
+    if (int rc = check_packed(c, {d_out, d_in}, batch)) return rc;
+    const Call call(c, stream);
+    return launch_unpack32(c, d_out, d_in, batch << c->k, call.st);
 }
 int sr_ntt_fwd_packed32_batch_dev(sr_ctx *c, uint32_t *d, size_t batch, void *stream) {
-    if (int rc = check(c, d)) return rc;
-    if (int rc = check_packed(c)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_packed(c, {d}, batch)) return rc;
+    const Call call(c, stream);
     if (batch == 0) return SR_OK;
-    if (c->path == RT_BABYBEAR) return rt_transform<sr::BabyBear, 0, sr::rt::PackedStream>(c, d, batch, st);
-    return packed_via_wide(c, d, d, nullptr, batch, st, [&](uint64_t *wa, uint64_t *) { return dev_fwd(c, wa, batch, st); });
+    if (c->path == RT_BABYBEAR) return rt_transform<sr::BabyBear, 0, sr::rt::PackedStream>(c, d, batch, call.st);
+    return packed_via_wide(c, d, d, nullptr, batch, call.st, [&](uint64_t *wa, uint64_t *) { return dev_fwd(c, wa, batch, call.st); });
 }
 int sr_ntt_inv_packed32_batch_dev(sr_ctx *c, uint32_t *d, size_t batch, void *stream) {
-    if (int rc = check(c, d)) return rc;
-    if (int rc = check_packed(c)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_packed(c, {d}, batch)) return rc;
+    const Call call(c, stream);
     if (batch == 0) return SR_OK;
-    if (c->path == RT_BABYBEAR) return rt_transform<sr::BabyBear, 1, sr::rt::PackedStream>(c, d, batch, st);
-    return packed_via_wide(c, d, d, nullptr, batch, st, [&](uint64_t *wa, uint64_t *) { return dev_inv(c, wa, batch, st); });
+    if (c->path == RT_BABYBEAR) return rt_transform<sr::BabyBear, 1, sr::rt::PackedStream>(c, d, batch, call.st);
+    return packed_via_wide(c, d, d, nullptr, batch, call.st, [&](uint64_t *wa, uint64_t *) { return dev_inv(c, wa, batch, call.st); });
 }
 int sr_ring_mul_packed32_batch_dev(sr_ctx *c, uint32_t *d_out, const uint32_t *d_a, const uint32_t *d_b, size_t batch, void *stream) {
-    if (int rc = check(c, d_out, d_a, d_b)) return rc;
-    if (int rc = check_packed(c)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check_packed(c, {d_out, d_a, d_b}, batch)) return rc;
     if (d_b == d_out) return fail(SR_E_INVALID, "ring_mul: b must not alias out");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    const Call call(c, stream);
     if (batch == 0) return SR_OK;
-    if (c->path == RT_BABYBEAR) return rt_ring_mul<sr::BabyBear, sr::rt::PackedStream>(c, d_out, d_a, d_b, batch, st);
-    return packed_via_wide(c, d_out, d_a, d_b, batch, st, [&](uint64_t *wa, uint64_t *wb) { return dev_ring_mul(c, wa, wa, wb, batch, st); });
-}
-static int packed_elementwise(sr_ctx *c, uint32_t *l, const uint32_t *r, size_t batch, void *stream, int op) {
-    if (int rc = check(c, l, r)) return rc;
-    if (int rc = check_packed(c)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = batch << c->k;
-    if (n == 0) return SR_OK;
-    ProfScope ps(c, st, K_POINTWISE);
-    const dim3 gr(sr::p32::blocks_for(n)), bl(256);
-    if (op == 0) hipLaunchKernelGGL(sr::p32::elementwise32_kernel<0>, gr, bl, 0, st, l, r, n);
-    else if (op == 1) hipLaunchKernelGGL(sr::p32::elementwise32_kernel<1>, gr, bl, 0, st, l, r, n);
-    else hipLaunchKernelGGL(sr::p32::elementwise32_kernel<2>, gr, bl, 0, st, l, r, n);
-    HIP_TRY(hipGetLastError());
-    return SR_OK;
+    if (c->path == RT_BABYBEAR) return rt_ring_mul<sr::BabyBear, sr::rt::PackedStream>(c, d_out, d_a, d_b, batch, call.st);
+    return packed_via_wide(c, d_out, d_a, d_b, batch, call.st, [&](uint64_t *wa, uint64_t *wb) { return dev_ring_mul(c, wa, wa, wb, batch, call.st); });
 }
 int sr_pointwise_mul_packed32_batch_dev(sr_ctx *c, uint32_t *l, const uint32_t *r, size_t batch, void *stream) {
     return packed_elementwise(c, l, r, batch, stream, 0);
@@ -2248,173 +2336,21 @@ int sr_ctx_plan_in_use(sr_ctx *c, sr_plan *plan, double probe_ms[2], size_t *pro
     return SR_OK;
 }
 int sr_reduce_batch_dev(sr_ctx *c, const uint64_t *in, size_t in_len, uint64_t *out, size_t batch, void *stream) {
-    if (int rc = check(c, in, out)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return dev_reduce(c, in, in_len, out, batch, (hipStream_t)stream);
+    if (int rc = check(c, {in, out}, batch)) return rc;
+    const Call call(c, stream);
+    return dev_reduce(c, in, in_len, out, batch, call.st);
 }
 int sr_fill_uniform_dev(sr_ctx *c, uint64_t seed, uint64_t first, size_t n, uint64_t *out, void *stream) {
-    if (int rc = check(c, out)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    switch (c->ring) {
-        case SR_RING_GOLDILOCKS_POW2:
-        case SR_RING_GOLDILOCKS_24: return fill_dev<sr::Goldilocks>(c, seed, first, n, out, st);
-        case SR_RING_BABYBEAR_POW2:
-        case SR_RING_BABYBEAR_72: return fill_dev<sr::BabyBear>(c, seed, first, n, out, st);
-        case SR_RING_FROG_16: return fill_dev<sr::Frog>(c, seed, first, n, out, st);
-        default: return fill_dev<sr::Stark>(c, seed, first, n, out, st);
-    }
+    if (int rc = check(c, {out})) return rc;
+    const Call call(c, stream);
+    DISPATCH_BASE_FIELD(c, (fill_dev<F>(c, seed, first, n, out, call.st)));
 }
 int sr_count_noncanonical_dev(sr_ctx *c, const uint64_t *d, size_t n, uint64_t *host_count, void *stream) {
-    if (int rc = check(c, d, host_count)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    switch (c->ring) {
-        case SR_RING_GOLDILOCKS_POW2:
-        case SR_RING_GOLDILOCKS_24: return count_dev<sr::Goldilocks>(c, d, n, host_count, st);
-        case SR_RING_BABYBEAR_POW2:
-        case SR_RING_BABYBEAR_72: return count_dev<sr::BabyBear>(c, d, n, host_count, st);
-        case SR_RING_FROG_16: return count_dev<sr::Frog>(c, d, n, host_count, st);
-        default: return count_dev<sr::Stark>(c, d, n, host_count, st);
-    }
+    if (int rc = check(c, {d, host_count})) return rc;
+    const Call call(c, stream);
+    DISPATCH_BASE_FIELD(c, (count_dev<F>(c, d, n, host_count, call.st)));
 }
 
-// ---- host-buffer entry points: stage, run, copy back ----
-// Host-pointer batches: results = compute(a[, b]) element-wise over the batch, through device staging buffers.
-// Small batches: copy in, compute, copy out on the context's stream.  Large batches are cut into chunks (default 128 MiB per
-// operand, SR_HOST_CHUNK_MB) that alternate between two sets of staging buffers: the calling thread copies chunk i in and
-// launches it while a helper thread copies chunk i-1 out on a second stream, so the two PCIe directions overlap and the device
-// memory needed no longer grows with the batch.  compute(s0, s1, n, stream) works in place on s0 (n elements).
-extern "C++" {
-static int host_pipeline(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch,
-                         const std::function<int(uint64_t *, uint64_t *, size_t, hipStream_t)> &compute) {
-    const size_t elem_bytes = c->degree * c->limbs * 8;
-    const size_t bytes = batch * elem_bytes;
-    if (bytes == 0) return SR_OK;
-    // The caller's buffers are ordinary (pageable) host memory -- a Rust Vec -- and stay that way: round 3 registered them with the
-    // HIP runtime for the duration of the call (hipHostRegister), which measured inside the noise (69.8-78.3 against 66.9-73.0 GB/s:
-    // the pipeline is PCIe-bound either way) and had two lifetime hazards (a read-only operand shared by two contexts on two
-    // threads was unregistered by whichever call returned first while the other GPU's DMA still read it; an early error return
-    // unregistered pages under an in-flight copy).  Removed in round 4; SR_PLAN_NO_HOST_PIN is accepted and has no effect.
-    const size_t chunk_mb = c->plan.host_chunk_mb ? c->plan.host_chunk_mb : 128;
-    size_t chunk = (chunk_mb << 20) / elem_bytes;
-    if (chunk == 0) chunk = 1;
-    if (batch <= 2 * chunk) {  // one shot
-        if (int rc = grow(c, HOST_0, bytes)) return rc;
-        if (b)
-            if (int rc = grow(c, HOST_1, bytes)) return rc;
-        HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], a, bytes, hipMemcpyHostToDevice, c->stream));
-        if (b) HIP_TRY(hipMemcpyAsync(c->buf[HOST_1], b, bytes, hipMemcpyHostToDevice, c->stream));
-        if (int rc = compute((uint64_t *)c->buf[HOST_0], (uint64_t *)c->buf[HOST_1], batch, c->stream)) return rc;
-        HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_0], bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SR_OK;
-    }
-    const size_t chunk_bytes = chunk * elem_bytes;
-    for (int i = 0; i < 4; i++)
-        if (b || (i & 1) == 0)
-            if (int rc = grow(c, Buf(HOST_0 + i), chunk_bytes)) return rc;
-    hipEvent_t ready[2];
-    for (auto &e : ready) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    struct Job {
-        const void *src;
-        uint64_t *dst;
-        size_t bytes;
-    } jobs[2];
-    std::mutex m;
-    std::condition_variable cv;
-    size_t submitted = 0, done = 0;
-    bool stop = false;
-    hipError_t worker_err = hipSuccess;
-    const int device = c->device;
-    hipStream_t out_stream = c->out_stream;
-    std::thread worker([&] {
-        (void)hipSetDevice(device);
-        for (;;) {
-            Job j;
-            int lane;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv.wait(lk, [&] { return done < submitted || stop; });
-                if (done == submitted) return;
-                lane = (int)(done & 1);
-                j = jobs[lane];
-            }
-            hipError_t e = hipStreamWaitEvent(out_stream, ready[lane], 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(j.dst, j.src, j.bytes, hipMemcpyDeviceToHost, out_stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(out_stream);
-            {
-                std::lock_guard<std::mutex> lk(m);
-                if (e != hipSuccess && worker_err == hipSuccess) worker_err = e;
-                done++;
-            }
-            cv.notify_all();
-        }
-    });
-    int rc = SR_OK;
-    hipError_t main_err = hipSuccess;
-    const size_t nchunks = (batch + chunk - 1) / chunk;
-    for (size_t i = 0; i < nchunks && rc == SR_OK && main_err == hipSuccess; i++) {
-        const int lane = (int)(i & 1);
-        const size_t first = i * chunk, n = batch - first < chunk ? batch - first : chunk;
-        {
-            std::unique_lock<std::mutex> lk(m);  // the lane's buffers are free once chunk i - 2 has been copied out
-            cv.wait(lk, [&] { return i < 2 || done + 1 >= i; });
-        }
-        uint64_t *s0 = (uint64_t *)c->buf[HOST_0 + 2 * lane], *s1 = (uint64_t *)c->buf[HOST_1 + 2 * lane];
-        main_err = hipMemcpyAsync(s0, a + first * (elem_bytes / 8), n * elem_bytes, hipMemcpyHostToDevice, c->stream);
-        if (main_err == hipSuccess && b)
-            main_err = hipMemcpyAsync(s1, b + first * (elem_bytes / 8), n * elem_bytes, hipMemcpyHostToDevice, c->stream);
-        if (main_err != hipSuccess) break;
-        rc = compute(s0, s1, n, c->stream);
-        if (rc != SR_OK) break;
-        main_err = hipEventRecord(ready[lane], c->stream);
-        if (main_err != hipSuccess) break;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            jobs[lane] = Job{s0, out + first * (elem_bytes / 8), n * elem_bytes};
-            submitted++;
-        }
-        cv.notify_all();
-    }
-    {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return done == submitted; });
-        stop = true;
-    }
-    cv.notify_all();
-    worker.join();
-    (void)hipStreamSynchronize(c->stream);
-    for (auto &e : ready) (void)hipEventDestroy(e);
-    if (rc != SR_OK) return rc;
-    if (main_err != hipSuccess) return fail(SR_E_HIP, std::string("host pipeline: ") + hipGetErrorString(main_err));
-    if (worker_err != hipSuccess) return fail(SR_E_HIP, std::string("host pipeline (copy out): ") + hipGetErrorString(worker_err));
-    return SR_OK;
-}
-}  // extern "C++"
-static int host_inplace(sr_ctx *c, uint64_t *data, size_t batch, bool fwd) {
-    if (int rc = check(c, data)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return host_pipeline(c, data, data, nullptr, batch, [&](uint64_t *s0, uint64_t *, size_t n, hipStream_t st) {
-        return fwd ? dev_fwd(c, s0, n, st) : dev_inv(c, s0, n, st);
-    });
-}
-// the unary operators on host buffers: op 0 neg, 1 scale, 2 add scalar (coefficient form), 3 add scalar (NTT form)
-static int host_unary(sr_ctx *c, uint64_t *data, const uint64_t *scalar, size_t batch, int op) {
-    if (int rc = check(c, data, op ? (const void *)scalar : (const void *)1)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return host_pipeline(c, data, data, nullptr, batch, [&](uint64_t *s0, uint64_t *, size_t n, hipStream_t st) {
-        return op == 0 ? dev_neg(c, s0, n, st) : op == 1 ? dev_scale(c, s0, scalar, n, st) : dev_add_scalar(c, s0, scalar, op == 3, n, st);
-    });
-}
 int sr_neg_batch(sr_ctx *c, uint64_t *data, size_t batch) { return host_unary(c, data, nullptr, batch, 0); }
 int sr_scale_batch(sr_ctx *c, uint64_t *data, const uint64_t *scalar, size_t batch) { return host_unary(c, data, scalar, batch, 1); }
 int sr_add_scalar_batch(sr_ctx *c, uint64_t *data, const uint64_t *scalar, int ntt_form, size_t batch) {
@@ -2422,10 +2358,8 @@ int sr_add_scalar_batch(sr_ctx *c, uint64_t *data, const uint64_t *scalar, int n
 }
 // host buffers: the one element goes to ELEMENT, the batch through the staged pipeline
 int sr_mul_elem_batch(sr_ctx *c, uint64_t *data, const uint64_t *elem, size_t batch) {
-    if (int rc = check(c, data, elem)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    if (int rc = check(c, {data, elem}, batch)) return rc;
+    const Call call(c);
     const size_t bytes = (size_t)c->degree * c->limbs * 8;
     if (int rc = grow(c, ELEMENT, bytes)) return rc;
     const uint64_t *dr = (const uint64_t *)c->buf[ELEMENT];
@@ -2437,19 +2371,6 @@ int sr_mul_elem_batch(sr_ctx *c, uint64_t *data, const uint64_t *elem, size_t ba
 int sr_ntt_fwd_batch(sr_ctx *c, uint64_t *data, size_t batch) { return host_inplace(c, data, batch, true); }
 int sr_ntt_inv_batch(sr_ctx *c, uint64_t *data, size_t batch) { return host_inplace(c, data, batch, false); }
 
-enum { HB_POINTWISE = 0, HB_RING_MUL = 1, HB_ADD = 2, HB_SUB = 3, HB_RING_MUL_NTT_RHS = 4 };
-static int host_binary(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch, int op) {
-    if (int rc = check(c, out, a, b)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    return host_pipeline(c, out, a, b, batch, [&](uint64_t *s0, uint64_t *s1, size_t n, hipStream_t st) {
-        return op == HB_RING_MUL ? dev_ring_mul(c, s0, s0, s1, n, st)
-               : op == HB_RING_MUL_NTT_RHS ? dev_ring_mul_ntt_rhs(c, s0, s0, s1, n, st)
-               : op == HB_POINTWISE ? dev_pointwise(c, s0, s1, n, st)
-                                    : dev_addsub(c, s0, s1, n, op == HB_SUB, st);
-    });
-}
 int sr_pointwise_mul_batch(sr_ctx *c, uint64_t *lhs, const uint64_t *rhs, size_t batch) {
     return host_binary(c, lhs, lhs, rhs, batch, HB_POINTWISE);
 }
@@ -2462,92 +2383,16 @@ int sr_ring_mul_ntt_rhs_batch(sr_ctx *c, uint64_t *out, const uint64_t *a, const
     return host_binary(c, out, a, b_ntt, batch, HB_RING_MUL_NTT_RHS);
 }
 int sr_reduce_batch(sr_ctx *c, const uint64_t *in, size_t in_len, uint64_t *out, size_t batch) {
-    if (int rc = check(c, in, out)) return rc;
-    if (int rc = check_count(c, batch)) return rc;
+    if (int rc = check(c, {in, out}, batch)) return rc;
     if (in_len > 2 * c->degree) return fail(SR_E_INVALID, "reduce: in_len_per_elem > 2D");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    size_t in_bytes = batch * in_len * c->limbs * 8, out_bytes = batch * c->degree * c->limbs * 8;
+    const Call call(c);
+    const size_t in_bytes = batch * in_len * c->limbs * 8, out_bytes = batch * c->degree * c->limbs * 8;
     if (out_bytes == 0) return SR_OK;
-    if (int rc = grow(c, HOST_0, in_bytes)) return rc;
-    if (int rc = grow(c, HOST_1, out_bytes)) return rc;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(c->buf[HOST_0], in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_reduce(c, (const uint64_t *)c->buf[HOST_0], in_len, (uint64_t *)c->buf[HOST_1], batch, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    return staged(c, {{in, nullptr, in_bytes}, {nullptr, out, out_bytes}}, [&](void *const *d) {
+        return dev_reduce(c, (const uint64_t *)d[0], in_len, (uint64_t *)d[1], batch, c->stream);
+    });
 }
 
-// ---- host-side self-test hook: runs the SAME __host__ __device__ field routines the kernels use,
-// on the host, one scalar operation per call.  Lets the CPU test-suite check fields.hpp without a
-// GPU.  Not a compute path: no batch entry point routes through it.
-// op: 0 add, 1 sub, 2 mul_boundary (a*b*R_b^-1 on in-memory images), 3 mul_tw, 4 tw_from_u64(a[0])
-extern "C++" {
-template <class F>
-static int selftest_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out) {
-    using S = typename F::storage;
-    typename F::elem x = F::load(reinterpret_cast<const S *>(a)), y = F::load(reinterpret_cast<const S *>(b)), r;
-    switch (op) {
-        case 0: r = F::add(x, y); break;
-        case 1: r = F::sub(x, y); break;
-        case 2: r = F::mul_boundary(x, y); break;
-        case 3: r = F::mul_tw(x, y); break;
-        case 4: r = F::tw_from_u64(a[0]); break;
-        default: return fail(SR_E_INVALID, "selftest: unknown op");
-    }
-    F::store(reinterpret_cast<S *>(out), r);
-    return SR_OK;
-}
-// StarkL (stark_lazy.hpp): 0 add, 1 sub, 3 mul_tw, 4 table form, 5 a chain of six lazy additions and subtractions feeding
-// mul_tw and mul_data, 6 repeated quadrupling with weak reductions, 7 / 8 signed combinations -- results leave through the
-// canonicalising store
-static int selftest_lazy(int op, const uint64_t *a, const uint64_t *b, uint64_t *out) {
-    using F = sr::StarkL;
-    using S = F::storage;
-    F::elem x = F::load(reinterpret_cast<const S *>(a)), y = F::load(reinterpret_cast<const S *>(b)), r;
-    switch (op) {
-        case 0: r = F::add(x, y); break;
-        case 1: r = F::sub(x, y); break;
-        case 3: r = F::mul_tw(x, y); break;
-        case 4: r = F::tw_from_u64(a[0]); break;
-        case 5: {
-            F::elem s = x, d = x;
-            for (int i = 0; i < 6; i++) {
-                s = F::add(s, y);
-                d = F::sub(d, y);
-            }
-            r = F::add(F::mul_tw(s, y), F::mul_data(d, s));
-            break;
-        }
-        case 6: {
-            r = x;
-            for (int i = 0; i < 4; i++) r = F::weak_reduce(F::add(F::add(r, r), F::add(r, r)));  // 256 a, reduced weakly on the way
-            break;
-        }
-        case 7: {  // 3 a - 5 b and, case 8, 7 a - 2 b without any carry in between: canonical() on signed lazy states
-            r = F::sub(F::add(F::add(x, x), x), F::add(F::add(F::add(y, y), F::add(y, y)), y));
-            break;
-        }
-        case 8: {
-            F::elem x2 = F::add(x, x), x4 = F::add(x2, x2);
-            r = F::sub(F::add(F::add(x4, x2), x), F::add(y, y));
-            break;
-        }
-        default: return fail(SR_E_INVALID, "selftest: unknown op");
-    }
-    F::store(reinterpret_cast<S *>(out), r);
-    return SR_OK;
-}
-}  // extern "C++"
-// op 5, field 0: the compile-time shift product of the tuned Goldilocks path, gl::mul_pow2<E>(a[0]) with E = b[0] in [1, 95]
-extern "C++" {
-template <int... Es>
-static uint64_t mul_pow2_any(uint64_t x, int e, std::integer_sequence<int, Es...>) {
-    uint64_t r = 0;
-    ((e == Es + 1 ? (r = sr::gl::mul_pow2<Es + 1>(x), 0) : 0), ...);
-    return r;
-}
-}
 int sr_selftest_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out) {
     if (!a || !b || !out) return fail(SR_E_INVALID, "null argument");
     if (field == 0 && op == 5) {
@@ -2614,8 +2459,7 @@ int sr_ctx_profile_enable(sr_ctx *c, int on) {
 int sr_ctx_profile_read(sr_ctx *c, double *ms_total, uint64_t *launches) { return sr_ctx_profile_read_sampled(c, ms_total, launches, nullptr); }
 int sr_ctx_profile_read_sampled(sr_ctx *c, double *ms_total, uint64_t *launches, uint64_t *seen) {
     if (!c || !ms_total || !launches) return fail(SR_E_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard g(c->device);
+    const Call call(c);
     for (auto &p : c->prof.pending) {
         HIP_TRY(hipEventSynchronize(p.b));
         float ms = 0;
