@@ -13,8 +13,8 @@
 //         2^16 <= D <= 2^20: cols256_kernel, c = 8 in one launch, shift-only (see the comment at the kernel);
 //         2^13 .. 2^15 and 2^21, 2^22: strided_kernel<M> / strided256_kernel with table twiddles.
 //   rows: cyclic DFT_N2 out of shift-only radix-16 register passes (omega_16 = 2^156 = -2^60), 16 coefficients per lane,
-//       exchanges through a padded 34 KiB LDS tile: rows256_kernel (N2 = 256: 16 x 16), rows_kernel (N2 = 4096:
-//       16 x 16 x 16; 512..2048: leading stages skipped, several blocks per tile).
+//       exchanges through LDS: rows256_kernel (N2 = 256: 16 x 16, a 4.25 KiB region per wave: its exchange never leaves a wave),
+//       rows_kernel (N2 = 4096: 16 x 16 x 16 through a padded 34 KiB tile; 512..2048: leading stages skipped, several blocks per tile).
 //   D <= 4096: no column launch at all -- a tile holds 4096 / D whole ring elements and rows_kernel<.., TW = true>
 //       applies the twist itself (a compile-time shift per register slot and a column factor merged into its table).
 //   The fused ring product keeps fwd(a) in registers while fwd(b) runs, multiplies slot-wise
@@ -951,34 +951,79 @@ __device__ __forceinline__ void tile256_load(const u64 *__restrict__ src, const 
 #pragma unroll
     for (int j = 0; j < 16; j++) x[j] = ld_scratch(src + base2 + j * 16);
 }
+// The exchange of a 256-point row is a 16 x 16 transpose among the 16 lanes of one rho = t >> 4, and a wave holds four whole rows
+// (rho = 4 w .. 4 w + 3): NO access of these kernels crosses a wave.  So each wave owns a region of LDS for its 1 024 coefficients,
+// and the exchange needs no workgroup barrier, only the order of the wave's own LDS operations.  The region holds one 32-bit half
+// of the coefficients at a time (low words, then high words through the same memory): 1 024 + 64 words of padding = 4.25 KiB per
+// wave, 17 KiB + 4 KiB of tables per workgroup instead of 38 KiB, which is what lets a fifth workgroup share the CU.
+// Word p = 256 (rho & 3) + i of the wave lives at p + (p >> 4).  The three access patterns, each 16 instructions of one base
+// register + an immediate offset, are free of bank conflicts for ds_write_b32 / ds_read_b32 (32 lanes per LDS cycle, bank =
+// word address mod 32; tools/rows256_lds_planes.py checks all of them):
+//   strided   lane (r, i0) word 256 r + i0 + 16 s  -> 272 r + i0 + 17 s     (16 r + i0 mod 32: 32 lanes, 32 banks)
+//   own       lane l       word 16 l + j           -> 17 l + j              (17 odd)
+//   coalesced lane l       word 64 j + l           -> 68 j + l + (l >> 4)   (lanes 0 and 31 of a group share a bank: two-way on ONE
+//                                                                            bank; only the plain transforms and MODE 3's load use it)
+constexpr int kWaveWords = 1024 + 64;  // per wave: 1 088 32-bit words
+struct Wave256 {
+    unsigned *strided, *own, *coalesced;  // this lane's base address in its wave's region, per pattern
+    int gpos;                             // first tile position of the coalesced pattern: 1 024 w + lane (+ 64 j)
+    __device__ __forceinline__ Wave256(unsigned *xw, const int t) {
+        const int l = t & 63;
+        unsigned *reg = xw + (t >> 6) * kWaveWords;
+        strided = reg + 272 * (l >> 4) + (l & 15);
+        own = reg + 17 * l;
+        coalesced = reg + l + (l >> 4);
+        gpos = (t & ~63) * 16 + l;
+    }
+};
+// Orders the wave's LDS accesses before it against those behind it.  The hardware runs one wave's LDS operations in issue order, so
+// at wavefront scope the fence emits no wait of its own (the reads' results are waited for where they are used, as always); what it
+// does is stop the compiler from moving an LDS access across it.
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// x[0..15] out through pattern (wr, stride ws words), back in through pattern (rd, stride rs): low words, then high words.
+// The caller fences before the next exchange's writes.
+template <int WS, int RS>
+__device__ __forceinline__ void wave256_exchange(unsigned *wr, const unsigned *rd, u64 *x) {
+    unsigned lo[16], hi[16];
+#pragma unroll
+    for (int s = 0; s < 16; s++) wr[WS * s] = (unsigned)x[s];
+    wave_lds_fence();
+#pragma unroll
+    for (int j = 0; j < 16; j++) lo[j] = rd[RS * j];
+    wave_lds_fence();
+#pragma unroll
+    for (int s = 0; s < 16; s++) wr[WS * s] = (unsigned)(x[s] >> 32);
+    wave_lds_fence();
+#pragma unroll
+    for (int j = 0; j < 16; j++) hi[j] = rd[RS * j];
+    wave_lds_fence();
+#pragma unroll
+    for (int j = 0; j < 16; j++) x[j] = ((u64)hi[j] << 32) | lo[j];
+}
 // x holds the lane's 16 coefficients (tile256_load) on entry, its 16 consecutive NTT slots on return
 // CANON: the slots leave the library as they are (plain forward transform): the last network runs canonical butterflies
 template <bool CANON = false>
-__device__ __forceinline__ void tile256_fwd_regs(u64 *lds, const int t, const Tables &T, u64 *x) {
-    const int i0 = t & 15, base2 = (t >> 4) * 256 + i0;
+__device__ __forceinline__ void tile256_fwd_regs(const Wave256 &W, const int t, const Tables &T, u64 *x) {
+    const int i0 = t & 15;
     dft16_fwd_hot(x);
 #pragma unroll
     for (int s = 1; s < 16; s++) x[s] = G::mul(x[s], T.w2f[s * 16 + i0]);
-#pragma unroll
-    for (int s = 0; s < 16; s++) lds[pad(base2 + s * 16)] = x[s];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 16; j++) x[j] = lds[17 * t + j];
+    wave256_exchange<17, 1>(W.strided, W.own, x);
     dft16_fwd_hot<CANON>(x);
 }
 template <bool CANON = false>
-__device__ __forceinline__ void tile256_fwd(const u64 *__restrict__ src, u64 *lds, const int t, const Tables &T, u64 *x) {
+__device__ __forceinline__ void tile256_fwd(const u64 *__restrict__ src, const Wave256 &W, const int t, const Tables &T, u64 *x) {
     tile256_load(src, t, x);
-    tile256_fwd_regs<CANON>(lds, t, T, x);
+    tile256_fwd_regs<CANON>(W, t, T, x);
 }
-__device__ __forceinline__ void tile256_inv(u64 *x, u64 *lds, const int t, const Tables &T, u64 *__restrict__ dst) {
+__device__ __forceinline__ void tile256_inv(u64 *x, const Wave256 &W, const int t, const Tables &T, u64 *__restrict__ dst) {
     const int i0 = t & 15, base2 = (t >> 4) * 256 + i0;
     dft16_inv_hot(x);
-#pragma unroll
-    for (int j = 0; j < 16; j++) lds[17 * t + j] = x[j];
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 16; s++) x[s] = lds[pad(base2 + s * 16)];
+    wave256_exchange<1, 17>(W.own, W.strided, x);
 #pragma unroll
     for (int s = 1; s < 16; s++) x[s] = G::mul(x[s], T.w2i[s * 16 + i0]);
     // x[0] skips the table product (its factor is 1) but is slot i0 of ANOTHER lane's network, a lazy representative: the twiddle-1
@@ -988,57 +1033,55 @@ __device__ __forceinline__ void tile256_inv(u64 *x, u64 *lds, const int t, const
 #pragma unroll
     for (int j = 0; j < 16; j++) st_scratch(dst + base2 + j * 16, x[j]);
 }
+// xw: kWaveWords 32-bit words per wave of the workgroup
 template <int MODE>
-__device__ __forceinline__ void rows256_tile(const unsigned tile, u64 *a, const u64 *b, u64 *out, const Tables &T, u64 *lds) {
+__device__ __forceinline__ void rows256_tile(const unsigned tile, u64 *a, const u64 *b, u64 *out, const Tables &T, unsigned *xw) {
     const int t = threadIdx.x;
     const size_t base = (size_t)tile * kTile;
+    const Wave256 W(xw, t);
     u64 A[16];
     if (MODE == 1) {
-        // the inverse starts from 16 consecutive slots per lane: lane-contiguous load, one exchange
+        // the inverse starts from 16 consecutive slots per lane: the wave loads its 1 024 slots lane-contiguous (512-byte
+        // segments), one exchange
 #pragma unroll
-        for (int j = 0; j < 16; j++) lds[pad(j * 256 + t)] = a[base + j * 256 + t];
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 16; j++) A[j] = lds[17 * t + j];  // own slots from here on: no barrier before tile256_inv's writes
+        for (int j = 0; j < 16; j++) A[j] = a[base + W.gpos + j * 64];
+        wave256_exchange<68, 1>(W.coalesced, W.own, A);
     } else {
-        tile256_fwd<MODE == 0>(a + base, lds, t, T, A);
+        tile256_fwd<MODE == 0>(a + base, W, t, T, A);
         if (MODE == 0) {
+            wave256_exchange<1, 68>(W.own, W.coalesced, A);
 #pragma unroll
-            for (int j = 0; j < 16; j++) lds[17 * t + j] = A[j];  // own slots
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 16; j++) st_slots(a + base + j * 256 + t, lds[pad(j * 256 + t)]);
+            for (int j = 0; j < 16; j++) st_slots(a + base + W.gpos + j * 64, A[j]);
             return;
         }
         u64 B[16];
-        __syncthreads();  // every lane has read a's exchange before b's lands
         if (MODE == 3) {  // b already in NTT order (see rows_kernel)
 #pragma unroll
-            for (int j = 0; j < 16; j++) lds[pad(j * 256 + t)] = b[base + j * 256 + t];
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 16; j++) B[j] = lds[17 * t + j];
+            for (int j = 0; j < 16; j++) B[j] = b[base + W.gpos + j * 64];
+            wave256_exchange<68, 1>(W.coalesced, W.own, B);
         } else {
-            tile256_fwd(b + base, lds, t, T, B);
+            tile256_fwd(b + base, W, t, T, B);
         }
 #pragma unroll
         for (int j = 0; j < 16; j++) A[j] = G::mul(A[j], B[j]);
     }
-    tile256_inv(A, lds, t, T, out + base);
+    tile256_inv(A, W, t, T, out + base);
 }
 // The two 256-entry table layers (w2f, w2i: 45 of the fused product's 93 global loads per lane and tile, 24 GB of L2 reads per
-// config-2 batch) are copied into 4 KiB of LDS first: 38 KiB per workgroup, four still fit a CU; -0.9 % on the two-lane step
-// (harness, three alternations: 14.97 / 15.04 / 14.97 against 15.10 / 15.16 / 15.24 ms), 97 instead of 112 VGPRs.
+// config-2 batch) are copied into 4 KiB of LDS first (-0.9 % on the two-lane step, 97 instead of 112 VGPRs).  With the per-wave
+// exchange regions that is 21 KiB per workgroup; compiled for FIVE workgroups per CU (512 registers per SIMD lane in granules of 8:
+// <= 96 each; 160 KiB of LDS: <= 32 KiB each; tests/test_rows256_residency.py).  The barrier behind the table copy is the only
+// one: wl[] is shared by the four waves.
 template <int MODE>
-__global__ __launch_bounds__(256, 4) void rows256_kernel(u64 *a, const u64 *b, u64 *out, Tables T) {
-    __shared__ u64 lds[kLdsElems];
+__global__ __launch_bounds__(256, 5) void rows256_kernel(u64 *a, const u64 *b, u64 *out, Tables T) {
+    __shared__ unsigned xw[4 * kWaveWords];
     __shared__ u64 wl[512];
     wl[threadIdx.x] = T.w2f[threadIdx.x];
     wl[256 + threadIdx.x] = T.w2i[threadIdx.x];
     __syncthreads();
     T.w2f = wl;
     T.w2i = wl + 256;
-    rows256_tile<MODE>(blockIdx.x, a, b, out, T, lds);
+    rows256_tile<MODE>(blockIdx.x, a, b, out, T, xw);
 }
 
 

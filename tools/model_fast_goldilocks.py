@@ -506,6 +506,81 @@ def rows256_inv(row, T):
 
 
 # ------------------------------------------------------------------------------------------------
+# Index model of the rows256 kernels' exchange (ntt_goldilocks.hpp: Wave256 / wave256_exchange): lane t = 64 w + l of the 256-lane
+# workgroup holds 16 values; each WAVE has a memory of its own (1 088 words; the kernel passes the low and the high 32-bit halves
+# through it one after the other, which this model does not distinguish).  No lane reads a word another wave wrote: the dictionary
+# per wave below raises KeyError if one did.  Bank conflicts of the same patterns: tools/rows256_lds_planes.py.
+# ------------------------------------------------------------------------------------------------
+def _wave_strided(l, s):
+    return 272 * (l >> 4) + (l & 15) + 17 * s
+
+
+def _wave_own(l, j):
+    return 17 * l + j
+
+
+def _wave_coalesced(l, j):
+    return l + (l >> 4) + 68 * j
+
+
+def _wave_exchange(regs, wr, rd):
+    """regs[t][0..15] for t = 0..255 -> the same after one exchange; wave w only ever touches mem[w]"""
+    mem = [dict() for _ in range(4)]
+    for t in range(256):
+        for s_ in range(16):
+            assert wr(t & 63, s_) < 1088 and wr(t & 63, s_) not in mem[t >> 6]
+            mem[t >> 6][wr(t & 63, s_)] = regs[t][s_]
+    return [[mem[t >> 6][rd(t & 63, j)] for j in range(16)] for t in range(256)]
+
+
+def rows256_tile_fwd_wave_local(tile, T):
+    """MODE 0 of gl::rows256_kernel on a tile of 16 rows, lane by lane: load, DFT_16, table, exchange (strided -> own), DFT_16,
+    exchange (own -> coalesced), store at 1 024 w + 64 j + l"""
+    regs = []
+    for t in range(256):
+        rho, i0 = t >> 4, t & 15
+        x = dft16_fwd([tile[rho * 256 + i0 + 16 * j] for j in range(16)])
+        regs.append([x[s_] * T["W2f"][s_][i0] % p for s_ in range(16)])
+    regs = [dft16_fwd(x) for x in _wave_exchange(regs, _wave_strided, _wave_own)]
+    regs = _wave_exchange(regs, _wave_own, _wave_coalesced)
+    out = [None] * 4096
+    for t in range(256):
+        for j in range(16):
+            out[1024 * (t >> 6) + 64 * j + (t & 63)] = regs[t][j]
+    return out
+
+
+def rows256_tile_inv_wave_local(tile, T):
+    """MODE 1: coalesced load, exchange (coalesced -> own), DFT_16^-1, exchange (own -> strided), table, DFT_16^-1, store"""
+    regs = [[tile[1024 * (t >> 6) + 64 * j + (t & 63)] for j in range(16)] for t in range(256)]
+    regs = [dft16_inv(x) for x in _wave_exchange(regs, _wave_coalesced, _wave_own)]
+    regs = _wave_exchange(regs, _wave_own, _wave_strided)
+    out = [None] * 4096
+    for t in range(256):
+        rho, i0 = t >> 4, t & 15
+        x = dft16_inv([regs[t][s_] * T["W2i"][s_][i0] % p for s_ in range(16)])
+        for j in range(16):
+            out[rho * 256 + i0 + 16 * j] = x[j]
+    return out
+
+
+def check_rows256_wave_local(seed=11):
+    rng = random.Random(seed)
+    T = cols_tables(16)
+    tile = [rng.randrange(p) for _ in range(4096)]
+    want = []
+    for b in range(16):
+        want += rows256_fwd(tile[b * 256:(b + 1) * 256], T)
+    got = rows256_tile_fwd_wave_local(tile, T)
+    assert got == want, "rows256 wave-local forward tile mismatch"
+    back = []
+    for b in range(16):
+        back += rows256_inv(got[b * 256:(b + 1) * 256], T)
+    assert rows256_tile_inv_wave_local(got, T) == back, "rows256 wave-local inverse tile mismatch"
+    return True
+
+
+# ------------------------------------------------------------------------------------------------
 # Whole tiles on representatives, as the kernels run them (round 3): lazy networks, table products that SKIP index 0 (factor 1),
 # and G::canon on the one value per lane that reaches a network without a product in front of it although it is an arbitrary slot
 # of another lane's lazy network (inverse direction only: in the forward direction the skipped value is slot 0 of the lane's own
@@ -708,6 +783,8 @@ if __name__ == "__main__":
         print("small k=%d ok" % k)
     check_cols256(16)
     print("cols256 + rows256 k=16 ok")
+    check_rows256_wave_local()
+    print("rows256 wave-local exchange ok")
     check_lazy_networks()
     print("lazy DIT networks ok")
     check_lazy_tiles()

@@ -40,6 +40,11 @@ static inline unsigned keep_groups(size_t np) { size_t g = np / 8; if (g < 1) g 
     } while (0)
 #endif
 #define ROWS_KERNEL (rows256_kernel<2>)
+// -DROWS_LDS=<bytes>: unused dynamic LDS on the rows launches, to lower their residency without touching the kernel (the rows256
+// residency experiment, profiles/r06/occupancy_sensitivity.txt: 4096 on top of 38 KiB = three workgroups per CU instead of four)
+#ifndef ROWS_LDS
+#define ROWS_LDS 0
+#endif
 #ifdef COLS_W3
 // the plain column pass at three workgroups per CU (168 VGPRs): separates "fewer, fatter waves" from "factors kept in registers"
 using namespace sr::gl;
@@ -113,7 +118,7 @@ int main(int argc, char **argv) {
         CK(hipEventRecord(ev[1]));
         COLS(0, b, b, npoly, T.wcf, T.twist_f);
         CK(hipEventRecord(ev[2]));
-        hipLaunchKernelGGL(ROWS_KERNEL, dim3(blocks), dim3(256), 0, 0, a, b, a, T);
+        hipLaunchKernelGGL(ROWS_KERNEL, dim3(blocks), dim3(256), ROWS_LDS, 0, a, b, a, T);
         CK(hipEventRecord(ev[3]));
         COLS(1, a, a, npoly, T.wci, T.twist_i_mul);
         CK(hipEventRecord(ev[4]));
@@ -148,7 +153,7 @@ int main(int argc, char **argv) {
             COLS(0, sb, bc, np, T.wcf, T.twist_f);
 #endif
             CK(hipEventRecord(cev[c * 5 + 2]));
-            hipLaunchKernelGGL(ROWS_KERNEL, dim3((unsigned)(np << (k - 12))), dim3(256), 0, 0, sa, sb, sa, T);
+            hipLaunchKernelGGL(ROWS_KERNEL, dim3((unsigned)(np << (k - 12))), dim3(256), ROWS_LDS, 0, sa, sb, sa, T);
             CK(hipEventRecord(cev[c * 5 + 3]));
             COLS(1, ac, sa, np, T.wci, T.twist_i_mul);
             CK(hipEventRecord(cev[c * 5 + 4]));
@@ -208,7 +213,7 @@ int main(int argc, char **argv) {
                 hipLaunchKernelGGL((cols256_kernel<0, LCV>), dim3(cb), dim3(16 << LCV), 0, st[si], ia, ac, k, T.wcf, T.twist_f, grp);
                 hipLaunchKernelGGL((cols256_kernel<0, LCV>), dim3(cb), dim3(16 << LCV), 0, st[si], ssb[si], bc, k, T.wcf, T.twist_f, grp);
 #endif
-                hipLaunchKernelGGL(ROWS_KERNEL, dim3((unsigned)(np << (k - 12))), dim3(256), 0, st[si], ia, ssb[si], ia, T);
+                hipLaunchKernelGGL(ROWS_KERNEL, dim3((unsigned)(np << (k - 12))), dim3(256), ROWS_LDS, st[si], ia, ssb[si], ia, T);
 #if defined(KEEP)
                 KEEP_LAUNCH(1, st[si], ac, ia, np, T.wci, T.twist_i_mul);
 #else

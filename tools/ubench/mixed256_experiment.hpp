@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256, 4) void mixed256_kernel(MixedArgs m, int k, Ta
     switch (role) {
         case 0: cols256_tile<0, 4>(tile, m.fa_dst, m.fa_src, k, T.wcf, T.twist_f, lds); break;
         case 1: cols256_tile<0, 4>(tile, m.fb_dst, m.fb_src, k, T.wcf, T.twist_f, lds); break;
-        case 2: rows256_tile<2>(tile, m.rows_a, m.rows_b, m.rows_a, T, lds); break;
+        case 2: rows256_tile<2>(tile, m.rows_a, m.rows_b, m.rows_a, T, reinterpret_cast<unsigned *>(lds)); break;
         default: cols256_tile<1, 4>(tile, m.inv, m.inv, k, T.wci, twist_i, lds); break;
     }
 }
