@@ -26,6 +26,8 @@
 //     checked_mul_mat                    matrix.rs:148-166             checked_mul_mat -> std::optional
 //     MulAssign<&R> (Matrix, Sparse)     matrix.rs:207-211,            operator*=(const RqNTTVec &one_element): every entry times one ring element
 //                                        sparse_matrix.rs:303-307
+//   DenseMultilinearExtension<RqNTT>     crates/poly mle/dense.rs    class DenseMultilinearExtension: fix_variables, fixed_variables,
+//     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations
 //   GadgetDecompose / GadgetRecompose    balanced_decomposition/     gadget_decompose(const RqPolyVec&, b, k) / gadget_recompose(...)
 //     for &[R] / Vec<R>                  mod.rs:163-206                (digit j of element e = element e * k + j; throws where it panics)
 //   SparseMatrix<RqNTT>                  sparse_matrix.rs:17-22      class SparseMatrixNTT  (coeffs: rows of (element, column))
@@ -328,6 +330,73 @@ private:
         return &z;
     }
     CyclotomicConfig cfg_;
+    std::vector<uint64_t> w_;
+};
+
+// DenseMultilinearExtension<RqNTT> of crates/poly (src/mle/dense.rs): a table of 2^num_vars ring elements in CRT/NTT form, of which
+// only the first len() are stored -- the rest is zero (dense.rs:35-54, 397-407).  Host buffers over sr_mle_fix_variables /
+// sr_mul_elem_add_batch; `r * a` is the slot product of the ring.  Throws where the reference asserts.
+class DenseMultilinearExtension {
+public:
+    DenseMultilinearExtension(CyclotomicConfig cfg, size_t num_vars, std::vector<uint64_t> evaluation_words)
+        : cfg_(std::move(cfg)), nv_(num_vars), w_(std::move(evaluation_words)) {
+        if (w_.size() % cfg_.words_per_elem()) throw std::length_error("Should be of correct length");
+        if (nv_ >= 48 || len() > ((size_t)1 << nv_)) throw std::length_error("more evaluations than 2^num_vars");
+    }
+    // dense.rs:79-89: a shorter vector is padded with zeros -- implicitly here; to_evaluations() writes the padding out
+    static DenseMultilinearExtension from_evaluations_vec_padded(size_t num_vars, const RqNTTVec &evaluations) {
+        return DenseMultilinearExtension(evaluations.config(), num_vars, evaluations.words());
+    }
+    size_t num_vars() const { return nv_; }
+    size_t len() const { return w_.size() / cfg_.words_per_elem(); }  // stored evaluations
+    const std::vector<uint64_t> &words() const { return w_; }
+    const CyclotomicConfig &config() const { return cfg_; }
+
+    // dense.rs:171-199: partial_point[i] fixes variable i, the least significant index bit first
+    void fix_variables(const RqNTTVec &partial_point) { *this = fold(partial_point, SR_MLE_LEADING); }
+    DenseMultilinearExtension fixed_variables(const RqNTTVec &partial_point) const { return fold(partial_point, SR_MLE_LEADING); }  // :201-205
+    // polynomials/multilinear_polynomial.rs:227-286: the LAST len variables, partial_point[j] = variable num_vars - len + j
+    DenseMultilinearExtension fix_last_variables(const RqNTTVec &partial_point) const { return fold(partial_point, SR_MLE_TRAILING); }
+    // dense.rs:107-113: None on a point of the wrong length
+    std::optional<RqNTTVec> evaluate(const RqNTTVec &point) const {
+        if (point.len() != nv_) return std::nullopt;
+        return RqNTTVec(cfg_, fold(point, SR_MLE_LEADING).w_);
+    }
+    // dense.rs:288-317 `AddAssign<(R, &Self)>`: *this += r * other, r one ring element
+    DenseMultilinearExtension &add_assign_scaled(const RqNTTVec &r, const DenseMultilinearExtension &other) {
+        if (other.nv_ != nv_) throw std::length_error("trying to add two dense MLEs with different numbers of variables");  // dense.rs:291-294
+        if (r.len() != 1) throw std::length_error("add_assign_scaled: r is not one ring element");
+        if (w_.size() < other.w_.size()) w_.resize(other.w_.size(), 0);  // the implicit zeros of the shorter operand, written out
+        if (!other.w_.empty())
+            CyclotomicConfig::check(sr_mul_elem_add_batch(cfg_.raw(), w_.data(), other.w_.data(), r.words().data(), other.len()),
+                                    "DenseMultilinearExtension +=");
+        return *this;
+    }
+    RqNTTVec to_evaluations() const {  // all 2^num_vars elements
+        std::vector<uint64_t> all(w_);
+        all.resize(cfg_.words_per_elem() << nv_, 0);
+        return RqNTTVec(cfg_, std::move(all));
+    }
+    // sr_mle_plan of a fold of n_fixed of this table's variables: {workspace elements, kernel launches} of the device form
+    std::pair<size_t, int> plan(size_t n_fixed, int order, int log2_degree) const {
+        size_t work = 0;
+        int launches = 0;
+        CyclotomicConfig::check(sr_mle_plan(cfg_.ring(), log2_degree, nv_, n_fixed, order, &work, &launches), "sr_mle_plan");
+        return {work, launches};
+    }
+
+private:
+    DenseMultilinearExtension fold(const RqNTTVec &point, int order) const {
+        if (point.len() > nv_) throw std::length_error("too many partial points");  // dense.rs:172-175
+        std::vector<uint64_t> out(cfg_.words_per_elem() << (nv_ - point.len()));
+        const uint64_t dummy = 0;
+        CyclotomicConfig::check(sr_mle_fix_variables(cfg_.raw(), out.data(), w_.empty() ? &dummy : w_.data(), len(), nv_,
+                                                     point.len() ? point.words().data() : &dummy, point.len(), order),
+                                "sr_mle_fix_variables");
+        return DenseMultilinearExtension(cfg_, nv_ - point.len(), std::move(out));
+    }
+    CyclotomicConfig cfg_;
+    size_t nv_;
     std::vector<uint64_t> w_;
 };
 

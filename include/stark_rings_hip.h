@@ -193,6 +193,10 @@ int sr_mul_elem_batch(sr_ctx *ctx, uint64_t *data_inout, const uint64_t *elem, s
  * sr_ctx_reserve_scratch). */
 int sr_sum_batch(sr_ctx *ctx, uint64_t *out, const uint64_t *in, size_t n);
 int sr_product_batch(sr_ctx *ctx, uint64_t *out, const uint64_t *in_ntt, size_t n);
+/* acc[e] += r * x[e] for e < batch, `*` the slot product (CRT/NTT form): `AddAssign<(R, &Self)>` of DenseMultilinearExtension
+ * (crates/poly/src/mle/dense.rs:288-317) in one pass.  Every ring id.  r: one ring element outside acc and x; acc and x are the
+ * same buffer or disjoint. */
+int sr_mul_elem_add_batch(sr_ctx *ctx, uint64_t *acc_inout, const uint64_t *x, const uint64_t *r, size_t batch);
 /* RqPoly * RqPoly == icrt(crt(a) * crt(b)) (coeff_form.rs:250-258; identity tested at
  * stark_prime/mod.rs:161-177).  out may alias a.                                          */
 int sr_ring_mul_batch(sr_ctx *ctx, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch);
@@ -213,6 +217,32 @@ int sr_add_scalar_batch_dev(sr_ctx *ctx, uint64_t *d_data, const uint64_t *host_
 int sr_mul_elem_batch_dev(sr_ctx *ctx, uint64_t *d_data_inout, const uint64_t *d_elem, size_t batch, void *stream);
 int sr_sum_batch_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, size_t n, void *stream);
 int sr_product_batch_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_in_ntt, size_t n, void *stream);
+int sr_mul_elem_add_batch_dev(sr_ctx *ctx, uint64_t *d_acc_inout, const uint64_t *d_x, const uint64_t *d_r, size_t batch, void *stream);
+/* Dense multilinear extensions of crates/poly over ring elements in CRT/NTT form (a coefficient-form table goes through
+ * sr_ntt_fwd_batch_dev first): a table of 2^num_vars ring elements, folded one variable at a time with the slot product of the ring.
+ *   SR_MLE_LEADING   DenseMultilinearExtension::fix_variables (mle/dense.rs:171-199): point[i] fixes variable i, the least significant
+ *                    index bit first -- self[b] = self[2b] + point[i] * (self[2b+1] - self[2b]).
+ *   SR_MLE_TRAILING  fix_last_variables (polynomials/multilinear_polynomial.rs:227-286): point[j] fixes variable num_vars - n_fixed + j,
+ *                    the last entry first -- self[b] = self[b] + r * (self[b + half] - self[b]).
+ * d_evals: n_evals <= 2^num_vars elements; the elements from n_evals up to 2^num_vars are zero and are NOT read (the reference's
+ * truncated storage, dense.rs:35-54, 397-407); n_evals = 0 is the zero MLE.  d_point: n_fixed <= num_vars elements.  d_out receives all
+ * 2^(num_vars - n_fixed) elements, zeros included; n_fixed == num_vars is `evaluate` (dense.rs:107-113), n_fixed == 0 copies and
+ * zero-pads.  Canonical inputs give canonical results.  The table and the point are never written, with one exception:
+ * SR_MLE_TRAILING allows d_out == d_evals (the `&mut self` form; d_work is then ignored).  SR_MLE_LEADING cannot run in place (element b
+ * is an input of another workgroup), and every other overlap between d_out, d_evals, d_point and d_work is SR_E_INVALID.
+ * The library allocates nothing and touches no context scratch: intermediate tables between launches live in d_work (work_elems ring
+ * elements, at least what sr_mle_plan returns), so the call can be captured into a HIP graph on any stream without a warm-up.
+ * sr_mle_plan: pure host arithmetic, no device, no context -- how the library runs the fold: *launches kernel launches (a table with
+ * n_evals = 0 takes one) and *work_elems <= 3 * 2^num_vars / 4 elements of workspace, 0 whenever one launch suffices; a launch folds up
+ * to three variables (two for the Stark field and babybear72: registers).  num_vars < 48.
+ * The host-pointer form stages like sr_sum_batch: the whole table goes to a context-owned device temporary, is folded there and the
+ * result comes back; chunked staging of folds is not implemented. */
+enum { SR_MLE_LEADING = 0, SR_MLE_TRAILING = 1 };
+int sr_mle_plan(int ring, int log2_degree, size_t num_vars, size_t n_fixed, int order, size_t *work_elems, int *launches);
+int sr_mle_fix_variables_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_evals, size_t n_evals, size_t num_vars, const uint64_t *d_point,
+                             size_t n_fixed, int order, uint64_t *d_work, size_t work_elems, void *stream);
+int sr_mle_fix_variables(sr_ctx *ctx, uint64_t *out, const uint64_t *evals, size_t n_evals, size_t num_vars, const uint64_t *point,
+                         size_t n_fixed, int order);
 /* First "next" row: y = M * v for a dense nrows x ncols matrix of ring elements in CRT/NTT form
  * (row-major, each entry one ring element) and a vector of ncols elements -- Matrix<RqNTT>::checked_mul_vec,
  * crates/linear_algebra/src/matrix.rs:168-178 -- as one fused multiply-accumulate pass over M.  Every ring id: the fully

@@ -6,6 +6,7 @@ Layout:
   rings.py              host-side mirror of the reference interface (CyclotomicConfig / CRT / ICRT /
                         Flatten at batch granularity) on top of the C ABI
   wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix around the device codec
+  mle.py                DenseMultilinearExtension of crates/poly over a device-resident table (fix_variables, evaluate)
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
   sharding.py           batch sharding across the GPUs of one node (one process per GPU)
 """
@@ -15,6 +16,9 @@ from .rings import (  # noqa: F401
     GOLDILOCKS_24,
     GOLDILOCKS_POW2,
     STARK_POW2,
+    MLE_LEADING,
+    MLE_TRAILING,
     CyclotomicRing,
     RingError,
 )
+from .mle import DenseMultilinearExtension  # noqa: F401

@@ -38,6 +38,12 @@ SYMBOLS = {
     "sr_scale_batch_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, u64p, _c.c_size_t, _c.c_void_p]),
     "sr_mul_elem_batch": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t]),
     "sr_mul_elem_batch_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_mul_elem_add_batch": (_c.c_int, [_c.c_void_p, u64p, u64p, u64p, _c.c_size_t]),
+    "sr_mul_elem_add_batch_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_mle_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_size_t, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
+    "sr_mle_fix_variables_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_int,
+                                            _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_mle_fix_variables": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t, _c.c_size_t, u64p, _c.c_size_t, _c.c_int]),
     "sr_sum_batch": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t]),
     "sr_product_batch": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t]),
     "sr_sum_batch_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),

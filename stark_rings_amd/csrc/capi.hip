@@ -28,6 +28,7 @@
 #include "frog_ring.hpp"
 #include "ntt_stark.hpp"
 #include "packed32.hpp"
+#include "mle.hpp"
 
 namespace {
 
@@ -1499,6 +1500,88 @@ int dev_reduce(sr_ctx *c, const uint64_t *in, size_t in_len, uint64_t *out, size
     }
 }
 
+// ---- dense multilinear extensions (csrc/mle.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch -------------
+int mle_launch(sr_ctx *c, int j, uint64_t *out, const uint64_t *in, const uint64_t *pt, size_t n_out, size_t n_in, size_t sb, size_t st,
+               hipStream_t s) {
+    ProfScope ps(c, s, K_POINTWISE);
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: e = sr::mle::launch_fold<sr::Goldilocks>(j, out, in, pt, n_out, n_in, sb, st, c->k, s); break;
+        case SR_RING_BABYBEAR_POW2: e = sr::mle::launch_fold<sr::BabyBear>(j, out, in, pt, n_out, n_in, sb, st, c->k, s); break;
+        case SR_RING_STARK_POW2: e = sr::mle::launch_fold<sr::Stark>(j, out, in, pt, n_out, n_in, sb, st, c->k, s); break;
+        case SR_RING_GOLDILOCKS_24: e = sr::mle::launch_slot_fold<sr::SlotG24>(c->small, j, out, in, pt, n_out, n_in, sb, st, s); break;
+        case SR_RING_BABYBEAR_72: e = sr::mle::launch_slot_fold<sr::SlotB72>(c->small, j, out, in, pt, n_out, n_in, sb, st, s); break;
+        default: e = sr::mle::launch_slot_fold<sr::SlotFrog>(c->frog, j, out, in, pt, n_out, n_in, sb, st, s); break;
+    }
+    if (e != hipSuccess) return fail(SR_E_HIP, std::string("mle fold launch: ") + hipGetErrorString(e));
+    return SR_OK;
+}
+// The launches of sr::mle::plan, one after the other on `st`.  Trailing order: out == evals folds in place; otherwise the first
+// intermediate table goes to `work` and is folded there in place.  Leading order alternates between the two regions of `work`.
+// An intermediate launch writes only the elements that can be non-zero and hands their count on as the next launch's n_in; the
+// last launch writes every element of `out`.
+int dev_mle_fix(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t n_evals, size_t num_vars, const uint64_t *point, size_t n_fixed,
+                int order, uint64_t *work, hipStream_t st) {
+    sr::mle::Plan p;
+    if (!sr::mle::plan(c->ring, num_vars, n_fixed, order, &p)) return fail(SR_E_INVALID, "mle_fix_variables: no plan for these arguments");
+    const size_t w = (size_t)c->degree * c->limbs;
+    const bool trailing = order == sr::mle::ORDER_TRAILING, in_place = out == evals;
+    const uint64_t *src = evals;
+    size_t n_in = n_evals, m = num_vars, done = 0;
+    for (int l = 0; l < p.launches; l++) {
+        const int j = p.j[l];
+        const bool last = l == p.launches - 1;
+        const size_t table = (size_t)1 << (m - j);  // elements of this launch's output table
+        const size_t sb = trailing ? 1 : (size_t)1 << j, stride = trailing ? table : 1;
+        const size_t n_valid = trailing ? (n_in < table ? n_in : table) : (n_in + sb - 1) >> j;
+        // bit i of a group index is variable m - j + i (trailing: point entry m - j + i - (num_vars - n_fixed)) or done + i (leading)
+        const uint64_t *pt = point + (trailing ? m - j - (num_vars - n_fixed) : done) * w;
+        uint64_t *dst = last ? out : trailing ? (in_place ? out : work) : (l % 2 == 0 ? work : work + (((size_t)1 << (num_vars - p.j[0])) * w));
+        const size_t n_out = last ? table : n_valid;
+        if (n_out)
+            if (int rc = mle_launch(c, j, dst, src, j ? pt : nullptr, n_out, n_in, sb, stride, st)) return rc;
+        src = dst;
+        n_in = n_valid;
+        m -= j;
+        done += j;
+    }
+    return SR_OK;
+}
+// acc[e] += r x[e], e < batch
+int dev_mul_elem_add(sr_ctx *c, uint64_t *acc, const uint64_t *x, const uint64_t *r, size_t batch, hipStream_t st) {
+    if (batch == 0) return SR_OK;
+    ProfScope ps(c, st, K_POINTWISE);
+    if (!is_pow2_ring(c->ring)) DISPATCH_SLOT(c, (sr::mle::launch_slot_mul_elem_add<SL>(K, acc, x, r, batch, st) != hipSuccess));
+    DISPATCH_POW2(c, ([&] {
+                      using S = typename F::storage;
+                      const size_t n = batch << c->k;
+                      hipLaunchKernelGGL(sr::mle::mul_elem_add_kernel<F>, dim3(sr::stream_blocks<F>(n)), dim3(256), 0, st, reinterpret_cast<S *>(acc),
+                                         reinterpret_cast<const S *>(x), reinterpret_cast<const S *>(r), n, (size_t)c->degree - 1);
+                      return hipGetLastError() == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, "mul_elem_add launch failed");
+                  }()));
+}
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a_bytes && b_bytes && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+// the argument checks the two forms of sr_mle_fix_variables share; *out_elems = 2^(num_vars - n_fixed), *need = workspace elements
+int check_mle(sr_ctx *c, const void *out, const void *evals, size_t n_evals, size_t num_vars, const void *point, size_t n_fixed, int order,
+              size_t *out_elems, size_t *need) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) return fail(SR_E_INVALID, "mle_fix_variables: unknown order");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "mle_fix_variables: num_vars must be below 48");
+    if (n_fixed > num_vars) return fail(SR_E_INVALID, "mle_fix_variables: n_fixed exceeds num_vars");
+    if (n_evals > (size_t)1 << num_vars) return fail(SR_E_INVALID, "mle_fix_variables: n_evals exceeds 2^num_vars");
+    if (!out || (n_evals && !evals) || (n_fixed && !point)) return fail(SR_E_INVALID, "mle_fix_variables: null buffer");
+    *out_elems = (size_t)1 << (num_vars - n_fixed);
+    if (int rc = check_count(c, *out_elems)) return rc;
+    if (int rc = check_count(c, n_evals)) return rc;
+    sr::mle::Plan p;
+    sr::mle::plan(c->ring, num_vars, n_fixed, order, &p);
+    *need = p.work_elems;
+    return check_count(c, p.work_elems);
+}
+
 int check_fold(sr_ctx *c, const uint64_t *out, const uint64_t *in, size_t n) {
     if (int rc = check(c, {out, n ? (const void *)in : (const void *)1}, n)) return rc;
     const uintptr_t w = (uintptr_t)c->degree * c->limbs * 8, po = (uintptr_t)out, pi = (uintptr_t)in;
@@ -2003,6 +2086,69 @@ int sr_mul_elem_batch_dev(sr_ctx *c, uint64_t *d, const uint64_t *elem, size_t b
     if (pe + w > pd && pd + batch * w > pe) return fail(SR_E_INVALID, "mul_elem: the element must not lie inside the batch it multiplies");
     const Call call(c, stream);
     return dev_mul_elem(c, d, elem, batch, call.st);
+}
+int sr_mle_plan(int ring, int log2_degree, size_t num_vars, size_t n_fixed, int order, size_t *work_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "mle_plan: null result pointer");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "mle_plan: num_vars must be below 48");
+    sr::mle::Plan p;
+    if (!sr::mle::plan(ring, num_vars, n_fixed, order, &p))
+        return fail(SR_E_INVALID, n_fixed > num_vars ? "mle_plan: n_fixed exceeds num_vars" : "mle_plan: unknown order");
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_mle_fix_variables_dev(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t n_evals, size_t num_vars, const uint64_t *point,
+                             size_t n_fixed, int order, uint64_t *work, size_t work_elems, void *stream) {
+    size_t out_elems = 0, need = 0;
+    if (int rc = check_mle(c, out, evals, n_evals, num_vars, point, n_fixed, order, &out_elems, &need)) return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const bool in_place = order == SR_MLE_TRAILING && n_evals && out == evals;
+    if (in_place) need = 0;  // an in-place trailing fold keeps its intermediate tables where they are and ignores d_work
+    if (need && !work) return fail(SR_E_INVALID, "mle_fix_variables: null buffer");
+    if (work_elems < need)
+        return fail(SR_E_INVALID, "mle_fix_variables: workspace too small (sr_mle_plan asks for " + std::to_string(need) + " elements)");
+    if (!in_place && ranges_overlap(out, out_elems * w, evals, n_evals * w))
+        return fail(SR_E_INVALID, "mle_fix_variables: d_out overlaps d_evals (only a trailing-order fold may run in place, with d_out == d_evals)");
+    if (ranges_overlap(out, out_elems * w, point, n_fixed * w)) return fail(SR_E_INVALID, "mle_fix_variables: d_out overlaps d_point");
+    if (ranges_overlap(evals, n_evals * w, point, n_fixed * w)) return fail(SR_E_INVALID, "mle_fix_variables: d_evals overlaps d_point");
+    if (ranges_overlap(out, out_elems * w, work, need * w)) return fail(SR_E_INVALID, "mle_fix_variables: d_out overlaps d_work");
+    if (ranges_overlap(evals, n_evals * w, work, need * w)) return fail(SR_E_INVALID, "mle_fix_variables: d_evals overlaps d_work");
+    if (ranges_overlap(point, n_fixed * w, work, need * w)) return fail(SR_E_INVALID, "mle_fix_variables: d_point overlaps d_work");
+    const Call call(c, stream);
+    return dev_mle_fix(c, out, evals, n_evals, num_vars, point, n_fixed, order, work, call.st);
+}
+int sr_mle_fix_variables(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t n_evals, size_t num_vars, const uint64_t *point,
+                         size_t n_fixed, int order) {
+    size_t out_elems = 0, need = 0;
+    if (int rc = check_mle(c, out, evals, n_evals, num_vars, point, n_fixed, order, &out_elems, &need)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    return staged(c, {{evals, nullptr, n_evals * w}, {point, nullptr, n_fixed * w}, {nullptr, out, out_elems * w}, {nullptr, nullptr, need * w}},
+                  [&](void *const *d) {
+                      return dev_mle_fix(c, (uint64_t *)d[2], (const uint64_t *)d[0], n_evals, num_vars, (const uint64_t *)d[1], n_fixed, order,
+                                         (uint64_t *)d[3], c->stream);
+                  });
+}
+int sr_mul_elem_add_batch_dev(sr_ctx *c, uint64_t *acc, const uint64_t *x, const uint64_t *r, size_t batch, void *stream) {
+    if (int rc = check(c, {acc, x, r}, batch)) return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    if (batch && (ranges_overlap(r, w, acc, batch * w) || ranges_overlap(r, w, x, batch * w)))
+        return fail(SR_E_INVALID, "mul_elem_add: r must not lie inside acc or x");
+    if (acc != x && ranges_overlap(acc, batch * w, x, batch * w))
+        return fail(SR_E_INVALID, "mul_elem_add: acc and x must be the same buffer or disjoint");
+    const Call call(c, stream);
+    return dev_mul_elem_add(c, acc, x, r, batch, call.st);
+}
+int sr_mul_elem_add_batch(sr_ctx *c, uint64_t *acc, const uint64_t *x, const uint64_t *r, size_t batch) {
+    if (int rc = check(c, {acc, x, r}, batch)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const bool same = acc == x;
+    return staged(c, {{acc, acc, batch * w}, {r, nullptr, w}, {same ? nullptr : x, nullptr, same ? 0 : batch * w}}, [&](void *const *d) {
+        return dev_mul_elem_add(c, (uint64_t *)d[0], (const uint64_t *)(same ? d[0] : d[2]), (const uint64_t *)d[1], batch, c->stream);
+    });
 }
 int sr_sum_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, void *stream) {
     if (int rc = check_fold(c, out, in, n)) return rc;

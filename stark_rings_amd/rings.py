@@ -24,6 +24,7 @@ from . import _lib
 
 GOLDILOCKS_POW2, BABYBEAR_POW2, STARK_POW2, GOLDILOCKS_24, BABYBEAR_72, FROG_16 = 0, 1, 2, 3, 4, 5
 PROF_TAGS = ("fwd_cols", "rows", "inv_cols", "pointwise", "other")
+MLE_LEADING, MLE_TRAILING = 0, 1   # SR_MLE_LEADING / SR_MLE_TRAILING: which end of the index a fold starts from
 
 _RING_NAMES = {
     "goldilocks": GOLDILOCKS_POW2,
@@ -189,6 +190,28 @@ class CyclotomicRing:
         if data.size:
             self._check(self._lib.sr_mul_elem_batch(self._ctx, _np_ptr(data), _np_ptr(elem), self._batch_of(data.size)))
         return data
+
+    def mul_elem_add(self, acc, x, r):
+        """Host buffers: acc[e] += r * x[e] slot-wise (see mul_elem_add_dev), in place on acc."""
+        if acc.size != x.size:
+            raise RingError("operand lengths differ")
+        if r.size != self.words_per_elem:
+            raise RingError("mul_elem_add: the multiplier is not one ring element")
+        if acc.size:
+            self._check(self._lib.sr_mul_elem_add_batch(self._ctx, _np_ptr(acc), _np_ptr(x), _np_ptr(r), self._batch_of(acc.size)))
+        return acc
+
+    def mle_fix_variables(self, evals, num_vars, point, order=MLE_LEADING):
+        """Host buffers: sr_mle_fix_variables (see mle_fix_variables_dev); returns the 2^(num_vars - n_fixed) folded elements."""
+        n_fixed = self._batch_of(point.size)
+        if n_fixed > num_vars:
+            raise RingError("mle_fix_variables: the point has more entries than the table has variables")
+        out = np.empty(self.words_per_elem << (num_vars - n_fixed), dtype=np.uint64)
+        n_evals, n_fixed = self._mle_sizes(evals.size, num_vars, point.size, out.size)
+        z = np.zeros(1, dtype=np.uint64)
+        self._check(self._lib.sr_mle_fix_variables(self._ctx, _np_ptr(out), _np_ptr(evals if n_evals else z), n_evals, int(num_vars),
+                                                   _np_ptr(point if n_fixed else z), n_fixed, int(order)))
+        return out
 
     def add_scalar(self, data, scalar, ntt_form):
         """Add<primitive> (coeff_form.rs:652-700: coefficient 0 of every element; ntt_form.rs:427-505: component 0 of every slot);
@@ -549,6 +572,57 @@ class CyclotomicRing:
             raise RingError("mul_elem: the multiplier is not one ring element")
         self._check(self._lib.sr_mul_elem_batch_dev(self._ctx, p, pe, self._batch_of(n), self._stream(stream)))
         return t
+
+    def mul_elem_add_dev(self, acc, x, r, stream=None):
+        """acc[e] += r * x[e] slot-wise (CRT/NTT form): AddAssign<(R, &Self)> of the dense MLE (crates/poly mle/dense.rs:288-317).
+        r: one ring element outside acc and x; acc and x: the same tensor or disjoint."""
+        pa, n = self._dev(acc)
+        px, m = self._dev(x)
+        pr, nr = self._dev(r)
+        if n != m:
+            raise RingError("operand lengths differ")
+        if nr != self.words_per_elem:
+            raise RingError("mul_elem_add: the multiplier is not one ring element")
+        self._check(self._lib.sr_mul_elem_add_batch_dev(self._ctx, pa, px, pr, self._batch_of(n), self._stream(stream)))
+        return acc
+
+    def mle_plan(self, num_vars, n_fixed, order=MLE_LEADING):
+        """sr_mle_plan: (work_elems, launches) of a fold of n_fixed of num_vars variables on this ring -- host arithmetic only."""
+        work = ctypes.c_size_t()
+        launches = ctypes.c_int()
+        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
+        self._check(self._lib.sr_mle_plan(self.ring, k, int(num_vars), int(n_fixed), int(order), ctypes.byref(work), ctypes.byref(launches)))
+        return work.value, launches.value
+
+    def _mle_sizes(self, n_words, num_vars, point_words, out_words):
+        n_evals = self._batch_of(n_words)
+        n_fixed = self._batch_of(point_words)
+        if num_vars < 0 or num_vars >= 48 or n_fixed > num_vars:
+            raise RingError("mle_fix_variables: the point has more entries than the table has variables")
+        if n_evals > 1 << num_vars:
+            raise RingError("mle_fix_variables: more evaluations than 2^num_vars")
+        if out_words != self.words_per_elem << (num_vars - n_fixed):
+            raise RingError("mle_fix_variables: out must hold 2^(num_vars - n_fixed) elements")
+        return n_evals, n_fixed
+
+    def mle_fix_variables_dev(self, out, evals, num_vars, point, order=MLE_LEADING, work=None, stream=None):
+        """sr_mle_fix_variables_dev: out = the table `evals` (n_evals <= 2^num_vars elements, the rest zero) with the variables of
+        `point` fixed -- MLE_LEADING: DenseMultilinearExtension::fix_variables (mle/dense.rs:171-199); MLE_TRAILING:
+        fix_last_variables (multilinear_polynomial.rs:227-286), where out may be evals.  work: a tensor of at least mle_plan()[0]
+        elements (None only where the plan needs none)."""
+        po, no = self._dev(out)
+        n_ev = evals.numel()
+        pp, npt = (self._dev(point) if point is not None and point.numel() else (ctypes.c_void_p(0), 0))
+        n_evals, n_fixed = self._mle_sizes(n_ev, num_vars, npt, no)
+        pe = self._dev(evals)[0] if n_ev else ctypes.c_void_p(0)
+        if work is None:
+            pw, nw = ctypes.c_void_p(0), 0
+        else:
+            pw, nw = self._dev(work)
+            nw //= self.words_per_elem
+        self._check(self._lib.sr_mle_fix_variables_dev(self._ctx, po, pe, n_evals, int(num_vars), pp, n_fixed, int(order), pw, nw,
+                                                       self._stream(stream)))
+        return out
 
     def sum_dev(self, out, elems, stream=None):
         """Sum over a device-resident slice (see sum): out = one ring element, must not overlap elems."""
