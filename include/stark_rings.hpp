@@ -28,6 +28,9 @@
 //                                        sparse_matrix.rs:303-307
 //   DenseMultilinearExtension<RqNTT>     crates/poly mle/dense.rs    class DenseMultilinearExtension: fix_variables, fixed_variables,
 //     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations
+//   WithLinfNorm / WithL2Norm for [Fq]   crates/ring/src/traits.rs    RqPolyVec::linf_norm / l2_norm_squared (the flattened coefficients, as
+//     (of flatten_to_coeffs)             :6-36                         little-endian u64 words of the integer), *_per_element; sr_norm_plan,
+//                                                                      sr_norm_batch, and sr_norm_batch_dev through CyclotomicConfig::norm_dev
 //   GadgetDecompose / GadgetRecompose    balanced_decomposition/     gadget_decompose(const RqPolyVec&, b, k) / gadget_recompose(...)
 //     for &[R] / Vec<R>                  mod.rs:163-206                (digit j of element e = element e * k + j; throws where it panics)
 //   SparseMatrix<RqNTT>                  sparse_matrix.rs:17-22      class SparseMatrixNTT  (coeffs: rows of (element, column))
@@ -170,6 +173,21 @@ public:
     void gadget_recompose_dev(uint64_t *out, const uint64_t *in, unsigned __int128 b, size_t padding_size, size_t batch_out, void *stream) const {
         check(sr_recompose_batch_wide_dev(raw(), out, in, (uint64_t)b, (uint64_t)(b >> 64), padding_size, batch_out, stream), "gadget_recompose_dev");
     }
+    // norms of n_coeffs device-resident coefficients, one record per `group` of them (include/stark_rings_hip.h, sr_norm_batch_dev);
+    // norm_plan: {words per group, workspace words, launches}
+    struct NormPlan {
+        size_t words_per_group, work_words;
+        int launches;
+    };
+    NormPlan norm_plan(size_t n_coeffs, size_t group, int which) const {
+        NormPlan p{};
+        check(sr_norm_plan(ring_, n_coeffs, group, which, &p.words_per_group, &p.work_words, &p.launches), "sr_norm_plan");
+        return p;
+    }
+    void norm_dev(uint64_t *out, const uint64_t *coeffs, size_t n_coeffs, size_t group, int which, uint64_t *work, size_t work_words,
+                  void *stream) const {
+        check(sr_norm_batch_dev(raw(), out, coeffs, n_coeffs, group, which, work, work_words, stream), "norm_dev");
+    }
     // packed-u32 BabyBear boundary (the low half of the reference's Fp64 limb, babybear/mod.rs:18-26)
     void pack32_dev(uint32_t *out, const uint64_t *in, size_t batch, void *stream) const { check(sr_pack32_batch_dev(raw(), out, in, batch, stream), "pack32_dev"); }
     void unpack32_dev(uint64_t *out, const uint32_t *in, size_t batch, void *stream) const { check(sr_unpack32_batch_dev(raw(), out, in, batch, stream), "unpack32_dev"); }
@@ -250,9 +268,25 @@ public:
         return RqPolyVec(cfg_, std::move(out));
     }
     RqPolyVec product() const;  // impl Product<&Self> (coeff_form.rs:523-537); defined below RqNTTVec
+    // WithLinfNorm / WithL2Norm of the flattened coefficients (traits.rs:6-36): the integer as little-endian u64 words -- limbs() words
+    // for linf, 3 (one-limb fields) or 9 (Stark) for the squared l2 norm.  linf_norm of an empty vector throws (the reference panics).
+    std::vector<uint64_t> linf_norm() const { return norm(SR_NORM_LINF, w_.size() / cfg_.limbs()); }
+    std::vector<uint64_t> l2_norm_squared() const { return norm(SR_NORM_L2SQ, w_.size() / cfg_.limbs()); }
+    // the same per ring element: len() records one after the other
+    std::vector<uint64_t> linf_norm_per_element() const { return norm(SR_NORM_LINF, cfg_.dimension()); }
+    std::vector<uint64_t> l2_norm_squared_per_element() const { return norm(SR_NORM_L2SQ, cfg_.dimension()); }
     std::vector<uint64_t> into_words() && { return std::move(w_); }
 
 private:
+    std::vector<uint64_t> norm(int which, size_t group) const {
+        const size_t n = w_.size() / cfg_.limbs();
+        if (group == 0) group = 1;  // the empty vector as one slice
+        const CyclotomicConfig::NormPlan p = cfg_.norm_plan(n, group, which);
+        std::vector<uint64_t> out((n ? n / group : 1) * p.words_per_group);
+        const uint64_t dummy = 0;
+        CyclotomicConfig::check(sr_norm_batch(cfg_.raw(), out.data(), w_.empty() ? &dummy : w_.data(), n, group, which), "RqPoly norm");
+        return out;
+    }
     CyclotomicConfig cfg_;
     std::vector<uint64_t> w_;
 };

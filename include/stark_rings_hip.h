@@ -243,6 +243,38 @@ int sr_mle_fix_variables_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_eva
                              size_t n_fixed, int order, uint64_t *d_work, size_t work_elems, void *stream);
 int sr_mle_fix_variables(sr_ctx *ctx, uint64_t *out, const uint64_t *evals, size_t n_evals, size_t num_vars, const uint64_t *point,
                          size_t n_fixed, int order);
+/* Norms of a coefficient slice on the device: WithLinfNorm::linf_norm / WithL2Norm::l2_norm_squared over [Fq]
+ * (crates/ring/src/traits.rs:6-36; per element balanced_decomposition/convertible_ring.rs:49-66; the signed representative of
+ * fq_convertible.rs:20-34 and stark_prime/decomposition.rs:40-52).
+ * d_coeffs: n_coeffs base-field coefficients in the usual memory image (Montgomery form, canonical, `limbs` u64 words each: what
+ * Flatten::flatten_to_coeffs gives for a Vec of ring elements, for every ring id; the call neither knows nor uses D).  Per coefficient
+ * x = the standard-form integer, s = x if x <= (p - 1) / 2, else x - p; linf = max |s|, l2sq = sum s^2, exact non-negative integers.
+ * NTT-form data is accepted and meaningless, as in the reference.  Words >= p are outside the contract.
+ * Groups: the slice is n_coeffs / group consecutive groups of `group` coefficients (group >= 1, a divisor of n_coeffs, any value -- not
+ * only powers of two), one result each: group = n_coeffs is the reference's slice norm, group = D one norm per ring element,
+ * group = ncols * D one per matrix row.
+ * which: SR_NORM_LINF | SR_NORM_L2SQ; both = one pass over the data.  Output per group, standard-form (NOT Montgomery) little-endian
+ * u64 words: linf `limbs` words (1 or 4), then l2sq 3 words for the one-limb fields (s^2 < 2^126, at most 2^64 coefficients: the sum
+ * is below 2^190) or 9 words for Stark (|s| < 2^251, s^2 < 2^502: the sum is below 2^566).
+ * Empty slice: linf_norm of the reference panics (max().unwrap()), so n_coeffs == 0 with SR_NORM_LINF is SR_E_INVALID; l2sq of an empty
+ * slice is ONE record of zero words, whatever `group`.
+ * sr_norm_plan: pure host arithmetic, no device, no context: the words per group, the workspace in u64 words and the launches
+ * (1 or 2).  Groups below 1024 coefficients take one launch and no workspace (a fixed number of lanes per group inside a wave); wider
+ * groups are cut into spans of whole workgroups whose partial records go to the workspace and are combined by a second launch -- at
+ * most 2^15 partial records per call (1 MiB for a one-limb field, 3.25 MiB for Stark), none when the groups alone fill the device.
+ * sr_norm_batch_dev allocates nothing, touches no context scratch, writes every workspace word it later reads (the previous contents
+ * do not matter, nothing is accumulated across calls) and can be captured into a HIP graph without a warm-up and replayed on changed
+ * data.  d_coeffs needs 8-byte alignment only.  SR_E_INVALID: a null pointer, `which` outside 1..3, group == 0, n_coeffs % group != 0,
+ * n_coeffs == 0 with SR_NORM_LINF, work_words below the plan's, d_out overlapping d_coeffs or d_work.  The result does not depend on
+ * the grid or on scheduling: integer max and integer sums only.
+ * sr_norm_batch (host pointers) streams the slice through the chunked staging pipeline (sr_plan.host_chunk_mb) and combines the
+ * per-chunk partial records on the host with max / add-with-carry; a group may straddle chunks. */
+#define SR_NORM_LINF 1
+#define SR_NORM_L2SQ 2
+int sr_norm_plan(int ring, size_t n_coeffs, size_t group, int which, size_t *out_words_per_group, size_t *work_words, int *launches);
+int sr_norm_batch_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_coeffs, size_t n_coeffs, size_t group, int which, uint64_t *d_work,
+                      size_t work_words, void *stream);
+int sr_norm_batch(sr_ctx *ctx, uint64_t *out, const uint64_t *coeffs, size_t n_coeffs, size_t group, int which);
 /* First "next" row: y = M * v for a dense nrows x ncols matrix of ring elements in CRT/NTT form
  * (row-major, each entry one ring element) and a vector of ncols elements -- Matrix<RqNTT>::checked_mul_vec,
  * crates/linear_algebra/src/matrix.rs:168-178 -- as one fused multiply-accumulate pass over M.  Every ring id: the fully

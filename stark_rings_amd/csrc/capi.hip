@@ -29,6 +29,7 @@
 #include "ntt_stark.hpp"
 #include "packed32.hpp"
 #include "mle.hpp"
+#include "norms.hpp"
 
 namespace {
 
@@ -1582,6 +1583,41 @@ int check_mle(sr_ctx *c, const void *out, const void *evals, size_t n_evals, siz
     return check_count(c, p.work_elems);
 }
 
+// ---- norms of coefficient slices (csrc/norms.hpp): nothing allocated, no context scratch ------------------------------------------------
+template <class F>
+int norm_launch(sr_ctx *c, const sr::norms::Plan &p, int which, uint64_t *out, const uint64_t *coeffs, uint64_t *work, hipStream_t st) {
+    ProfScope ps(c, st, K_OTHER);
+    const hipError_t e = sr::norms::launch<F>(p, which, out, coeffs, work, st);
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("norm launch: ") + hipGetErrorString(e));
+}
+int dev_norm(sr_ctx *c, const sr::norms::Plan &p, int which, uint64_t *out, const uint64_t *coeffs, uint64_t *work, hipStream_t st) {
+    DISPATCH_BASE_FIELD(c, (norm_launch<F>(c, p, which, out, coeffs, work, st)));
+}
+// the argument checks sr_norm_plan and the two forms of sr_norm_batch share (limbs: 1 or 4 words per coefficient)
+int check_norm(int limbs, size_t n_coeffs, size_t group, int which, sr::norms::Plan *p) {
+    if (which < 1 || which > 3) return fail(SR_E_INVALID, "norm: `which` must be SR_NORM_LINF, SR_NORM_L2SQ or both");
+    if (group == 0) return fail(SR_E_INVALID, "norm: group must be at least 1");
+    if (n_coeffs % group != 0) return fail(SR_E_INVALID, "norm: group must divide n_coeffs");
+    if (n_coeffs == 0 && (which & SR_NORM_LINF)) return fail(SR_E_INVALID, "norm: linf of an empty slice is undefined (the reference panics)");
+    if (n_coeffs > ((size_t)1 << 46) / ((size_t)limbs * 8)) return fail(SR_E_INVALID, "norm: coefficient count too large");
+    if (!sr::norms::plan(limbs, n_coeffs, group, which, p)) return fail(SR_E_INVALID, "norm: no plan for these arguments");
+    return SR_OK;
+}
+// dst (+)= src on the host: max of the linf words, sum with carry of the l2sq words
+void norm_combine_host(uint64_t *dst, const uint64_t *src, int nl, int ns) {
+    for (int i = nl - 1; i >= 0; i--)
+        if (src[i] != dst[i]) {
+            if (src[i] > dst[i]) memcpy(dst, src, (size_t)nl * 8);
+            break;
+        }
+    uint64_t carry = 0;
+    for (int i = nl; i < nl + ns; i++) {
+        const uint64_t t = dst[i] + carry, u = t + src[i];
+        carry = (uint64_t)(t < carry) + (uint64_t)(u < t);
+        dst[i] = u;
+    }
+}
+
 int check_fold(sr_ctx *c, const uint64_t *out, const uint64_t *in, size_t n) {
     if (int rc = check(c, {out, n ? (const void *)in : (const void *)1}, n)) return rc;
     const uintptr_t w = (uintptr_t)c->degree * c->limbs * 8, po = (uintptr_t)out, pi = (uintptr_t)in;
@@ -1639,9 +1675,11 @@ int host_fold(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, bool mul) 
 // operand, SR_HOST_CHUNK_MB) that alternate between two sets of staging buffers: the calling thread copies chunk i in and
 // launches it while a helper thread copies chunk i-1 out on a second stream, so the two PCIe directions overlap and the device
 // memory needed no longer grows with the batch.  compute(s0, s1, n, stream) works in place on s0 (n elements).
+// unit_bytes != 0: the batch counts units of that many bytes instead of ring elements (the norms count coefficients).  out == nullptr:
+// a read-only pass -- nothing is copied back, compute() keeps what it needs, and a lane's buffer is free for chunk i + 2 by stream order.
 int host_pipeline(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b, size_t batch,
-                  const std::function<int(uint64_t *, uint64_t *, size_t, hipStream_t)> &compute) {
-    const size_t elem_bytes = c->degree * c->limbs * 8;
+                  const std::function<int(uint64_t *, uint64_t *, size_t, hipStream_t)> &compute, size_t unit_bytes = 0) {
+    const size_t elem_bytes = unit_bytes ? unit_bytes : c->degree * c->limbs * 8;
     const size_t bytes = batch * elem_bytes;
     if (bytes == 0) return SR_OK;
     // The caller's buffers are ordinary (pageable) host memory -- a Rust Vec -- and stay that way: round 3 registered them with the
@@ -1703,7 +1741,7 @@ int host_pipeline(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b
     for (size_t i = 0; i < nchunks && rc == SR_OK && main_err == hipSuccess; i++) {
         const int lane = (int)(i & 1);
         const size_t first = i * chunk, n = batch - first < chunk ? batch - first : chunk;
-        {
+        if (out) {
             std::unique_lock<std::mutex> lk(m);  // the lane's buffers are free once chunk i - 2 has been copied out
             cv.wait(lk, [&] { return i < 2 || done + 1 >= i; });
         }
@@ -1714,6 +1752,7 @@ int host_pipeline(sr_ctx *c, uint64_t *out, const uint64_t *a, const uint64_t *b
         if (main_err != hipSuccess) break;
         rc = compute(s0, s1, n, c->stream);
         if (rc != SR_OK) break;
+        if (!out) continue;
         main_err = hipEventRecord(ready[lane], c->stream);
         if (main_err != hipSuccess) break;
         {
@@ -2130,6 +2169,96 @@ int sr_mle_fix_variables(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t
                       return dev_mle_fix(c, (uint64_t *)d[2], (const uint64_t *)d[0], n_evals, num_vars, (const uint64_t *)d[1], n_fixed, order,
                                          (uint64_t *)d[3], c->stream);
                   });
+}
+int sr_norm_plan(int ring, size_t n_coeffs, size_t group, int which, size_t *out_words_per_group, size_t *work_words, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (!out_words_per_group || !work_words || !launches) return fail(SR_E_INVALID, "norm_plan: null result pointer");
+    sr::norms::Plan p;
+    if (int rc = check_norm(ring == SR_RING_STARK_POW2 ? 4 : 1, n_coeffs, group, which, &p)) return rc;
+    *out_words_per_group = p.words_per_group;
+    *work_words = p.work_words;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_norm_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *coeffs, size_t n_coeffs, size_t group, int which, uint64_t *work,
+                      size_t work_words, void *stream) {
+    if (int rc = check(c, {out, n_coeffs ? (const void *)coeffs : (const void *)1})) return rc;
+    sr::norms::Plan p;
+    if (int rc = check_norm(c->limbs, n_coeffs, group, which, &p)) return rc;
+    if (p.work_words && !work) return fail(SR_E_INVALID, "norm: null buffer");
+    if (work_words < p.work_words)
+        return fail(SR_E_INVALID, "norm: workspace too small (sr_norm_plan asks for " + std::to_string(p.work_words) + " words)");
+    const size_t out_bytes = p.n_groups * p.words_per_group * 8;
+    if (ranges_overlap(out, out_bytes, coeffs, n_coeffs * c->limbs * 8)) return fail(SR_E_INVALID, "norm: d_out overlaps d_coeffs");
+    if (ranges_overlap(out, out_bytes, work, p.work_words * 8)) return fail(SR_E_INVALID, "norm: d_out overlaps d_work");
+    if (ranges_overlap(coeffs, n_coeffs * c->limbs * 8, work, p.work_words * 8)) return fail(SR_E_INVALID, "norm: d_coeffs overlaps d_work");
+    const Call call(c, stream);
+    return dev_norm(c, p, which, out, coeffs, work, call.st);
+}
+// Host pointers: the slice goes through host_pipeline in chunks of coefficients.  A chunk is [the rest of a group the previous chunk
+// began][whole groups][the beginning of a group]: up to three device calls whose records are copied back and combined here.
+int sr_norm_batch(sr_ctx *c, uint64_t *out, const uint64_t *coeffs, size_t n_coeffs, size_t group, int which) {
+    if (int rc = check(c, {out, n_coeffs ? (const void *)coeffs : (const void *)1})) return rc;
+    sr::norms::Plan whole;
+    if (int rc = check_norm(c->limbs, n_coeffs, group, which, &whole)) return rc;
+    const size_t wpg = whole.words_per_group, limbs = (size_t)c->limbs;
+    const int nl = (which & SR_NORM_LINF) ? c->limbs : 0, ns = (int)wpg - nl;
+    memset(out, 0, whole.n_groups * wpg * 8);
+    if (n_coeffs == 0) return SR_OK;
+    const Call call(c);
+    // the chunk host_pipeline will use, hence the most records one chunk leaves; one workspace serves the calls of a chunk in turn
+    const size_t chunk_mb = c->plan.host_chunk_mb ? c->plan.host_chunk_mb : 128;
+    size_t chunk = (chunk_mb << 20) / (limbs * 8);
+    if (chunk == 0) chunk = 1;
+    const size_t largest = n_coeffs <= 2 * chunk ? n_coeffs : chunk, max_records = largest / group + 2;
+    if (int rc = grow(c, HOST_1, max_records * wpg * 8)) return rc;
+    if (int rc = grow(c, HOST_3, sr::norms::kMaxParts * wpg * 8)) return rc;
+    uint64_t *d_rec = (uint64_t *)c->buf[HOST_1], *d_work = (uint64_t *)c->buf[HOST_3];
+    struct Part {  // the records one chunk left: those of piece i belong to the groups g0[i] .. g0[i] + count[i] - 1
+        size_t g0[3], count[3];
+        int pieces;
+        std::vector<uint64_t> words;
+    };
+    std::vector<Part> parts;
+    size_t first = 0;  // of the next chunk: compute() is called once per chunk, in order
+    const int rc = host_pipeline(
+        c, nullptr, coeffs, nullptr, n_coeffs,
+        [&](uint64_t *s0, uint64_t *, size_t n, hipStream_t st) {
+            const size_t end = first + n;
+            size_t pos = first, records = 0;
+            Part pt{};
+            auto piece = [&](size_t len, size_t grp) {
+                sr::norms::Plan p;
+                if (!sr::norms::plan(c->limbs, len, grp, which, &p)) return fail(SR_E_INVALID, "norm: no plan for a chunk");
+                if (int r = dev_norm(c, p, which, d_rec + records * wpg, s0 + (pos - first) * limbs, d_work, st)) return r;
+                pt.g0[pt.pieces] = pos / group;
+                pt.count[pt.pieces++] = p.n_groups;
+                records += p.n_groups;
+                pos += len;
+                return (int)SR_OK;
+            };
+            if (pos % group) {  // the rest of the group the previous chunk began, or as much of it as this chunk holds
+                const size_t rest = group - pos % group, len = rest < end - pos ? rest : end - pos;
+                if (int r = piece(len, len)) return r;
+            }
+            if ((end - pos) / group)
+                if (int r = piece((end - pos) / group * group, group)) return r;
+            if (pos < end)
+                if (int r = piece(end - pos, end - pos)) return r;
+            pt.words.resize(records * wpg);
+            parts.push_back(std::move(pt));
+            HIP_TRY(hipMemcpyAsync(parts.back().words.data(), d_rec, records * wpg * 8, hipMemcpyDeviceToHost, st));
+            first = end;
+            return (int)SR_OK;
+        },
+        limbs * 8);
+    if (rc) return rc;
+    for (const Part &pt : parts) {  // host_pipeline has synchronised the stream: the records are here
+        const uint64_t *src = pt.words.data();
+        for (int i = 0; i < pt.pieces; i++)
+            for (size_t r = 0; r < pt.count[i]; r++, src += wpg) norm_combine_host(out + (pt.g0[i] + r) * wpg, src, nl, ns);
+    }
+    return SR_OK;
 }
 int sr_mul_elem_add_batch_dev(sr_ctx *c, uint64_t *acc, const uint64_t *x, const uint64_t *r, size_t batch, void *stream) {
     if (int rc = check(c, {acc, x, r}, batch)) return rc;

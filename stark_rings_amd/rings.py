@@ -25,6 +25,7 @@ from . import _lib
 GOLDILOCKS_POW2, BABYBEAR_POW2, STARK_POW2, GOLDILOCKS_24, BABYBEAR_72, FROG_16 = 0, 1, 2, 3, 4, 5
 PROF_TAGS = ("fwd_cols", "rows", "inv_cols", "pointwise", "other")
 MLE_LEADING, MLE_TRAILING = 0, 1   # SR_MLE_LEADING / SR_MLE_TRAILING: which end of the index a fold starts from
+NORM_LINF, NORM_L2SQ = 1, 2        # SR_NORM_LINF / SR_NORM_L2SQ: the mask of sr_norm_batch*
 
 _RING_NAMES = {
     "goldilocks": GOLDILOCKS_POW2,
@@ -212,6 +213,56 @@ class CyclotomicRing:
         self._check(self._lib.sr_mle_fix_variables(self._ctx, _np_ptr(out), _np_ptr(evals if n_evals else z), n_evals, int(num_vars),
                                                    _np_ptr(point if n_fixed else z), n_fixed, int(order)))
         return out
+
+    # -- norms of coefficient slices (traits.rs:6-36: WithLinfNorm / WithL2Norm over [Fq]) ---------------------------------------
+    def norm_plan(self, n_coeffs, group=None, which=NORM_LINF | NORM_L2SQ):
+        """sr_norm_plan: (words per group, workspace words, launches) -- host arithmetic only.  group None = the whole slice."""
+        wpg, work, launches = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+        self._check(self._lib.sr_norm_plan(self.ring, int(n_coeffs), self._norm_group(n_coeffs, group), int(which), ctypes.byref(wpg),
+                                           ctypes.byref(work), ctypes.byref(launches)))
+        return wpg.value, work.value, launches.value
+
+    def _norm_group(self, n_coeffs, group):
+        return int(group) if group is not None else max(int(n_coeffs), 1)
+
+    def _norm_coeffs(self, n_words):
+        if n_words % self.limbs:
+            raise RingError("buffer length %d is not a multiple of the %d words of a coefficient" % (n_words, self.limbs))
+        return n_words // self.limbs
+
+    def _norm_ints(self, words, which, whole):
+        """the records of sr_norm_batch* as Python integers: linf, l2sq or (linf, l2sq) per group; one value for the whole slice"""
+        nl = self.limbs if which & NORM_LINF else 0
+        ns = (3 if self.limbs == 1 else 9) if which & NORM_L2SQ else 0
+        recs = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, nl + ns)
+        val = lambda ws: int.from_bytes(ws.astype("<u8").tobytes(), "little")
+        res = []
+        for r in recs:
+            parts = ([val(r[:nl])] if nl else []) + ([val(r[nl:])] if ns else [])
+            res.append(parts[0] if len(parts) == 1 else tuple(parts))
+        return res[0] if whole else res
+
+    def _norm_host(self, coeffs, group, which):
+        n = self._norm_coeffs(coeffs.size)
+        wpg = self.norm_plan(n, group, which)[0]
+        g = self._norm_group(n, group)
+        out = np.empty(max(n // g, 1) * wpg, dtype=np.uint64)
+        src = coeffs if n else np.zeros(1, dtype=np.uint64)
+        self._check(self._lib.sr_norm_batch(self._ctx, _np_ptr(out), _np_ptr(src), n, g, int(which)))
+        return self._norm_ints(out, which, group is None)
+
+    def linf_norm(self, coeffs, group=None):
+        """Host buffer of coefficients (flatten_to_coeffs): max |signed representative| as a Python int; group = g: a list, one per g
+        consecutive coefficients.  An empty slice is refused (the reference panics)."""
+        return self._norm_host(coeffs, group, NORM_LINF)
+
+    def l2_norm_squared(self, coeffs, group=None):
+        """Host buffer: the sum of the squared signed representatives, exact (see linf_norm)."""
+        return self._norm_host(coeffs, group, NORM_L2SQ)
+
+    def norms(self, coeffs, group=None):
+        """Host buffer: (linf, l2sq) from one pass over the data; a list of such pairs with group = g."""
+        return self._norm_host(coeffs, group, NORM_LINF | NORM_L2SQ)
 
     def add_scalar(self, data, scalar, ntt_form):
         """Add<primitive> (coeff_form.rs:652-700: coefficient 0 of every element; ntt_form.rs:427-505: component 0 of every slot);
@@ -623,6 +674,43 @@ class CyclotomicRing:
         self._check(self._lib.sr_mle_fix_variables_dev(self._ctx, po, pe, n_evals, int(num_vars), pp, n_fixed, int(order), pw, nw,
                                                        self._stream(stream)))
         return out
+
+    def norm_batch_dev(self, out, coeffs, group=None, which=NORM_LINF | NORM_L2SQ, work=None, stream=None):
+        """sr_norm_batch_dev: out = the records (norm_plan()[0] words per group: linf words, then l2sq words; standard-form integers)
+        of the device-resident coefficients.  work: a tensor of at least norm_plan()[1] words (None only where the plan needs none).
+        Allocates nothing; capturable."""
+        po, no = self._dev(out)
+        n = self._norm_coeffs(coeffs.numel())
+        g = self._norm_group(n, group)
+        if g and n % g == 0 and no != max(n // g, 1) * self.norm_plan(n, g, which)[0]:
+            raise RingError("norm: out must hold norm_plan()[0] words per group")
+        pc = self._dev(coeffs)[0] if n else ctypes.c_void_p(0)
+        pw, nw = self._dev(work) if work is not None else (ctypes.c_void_p(0), 0)
+        self._check(self._lib.sr_norm_batch_dev(self._ctx, po, pc, n, g, int(which), pw, nw, self._stream(stream)))
+        return out
+
+    def _norm_dev(self, coeffs, group, which, work, stream):
+        import torch
+
+        n = self._norm_coeffs(coeffs.numel())
+        g = self._norm_group(n, group)
+        wpg, need, _ = self.norm_plan(n, g, which)
+        out = torch.empty(max(n // g, 1) * wpg, dtype=torch.int64, device=coeffs.device)
+        if work is None and need:
+            work = torch.empty(need, dtype=torch.int64, device=coeffs.device)
+        self.norm_batch_dev(out, coeffs, g, which, work, stream)
+        return self._norm_ints(out.cpu().numpy().view(np.uint64), which, group is None)  # the copy synchronises
+
+    def linf_norm_dev(self, coeffs, group=None, work=None, stream=None):
+        """linf_norm of a device tensor of coefficients, as Python int(s); work: an optional caller workspace (norm_plan()[1] words)."""
+        return self._norm_dev(coeffs, group, NORM_LINF, work, stream)
+
+    def l2_norm_squared_dev(self, coeffs, group=None, work=None, stream=None):
+        return self._norm_dev(coeffs, group, NORM_L2SQ, work, stream)
+
+    def norms_dev(self, coeffs, group=None, work=None, stream=None):
+        """(linf, l2sq) of a device tensor from one pass (see norms)."""
+        return self._norm_dev(coeffs, group, NORM_LINF | NORM_L2SQ, work, stream)
 
     def sum_dev(self, out, elems, stream=None):
         """Sum over a device-resident slice (see sum): out = one ring element, must not overlap elems."""
