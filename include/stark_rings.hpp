@@ -28,6 +28,9 @@
 //                                        sparse_matrix.rs:303-307
 //   DenseMultilinearExtension<RqNTT>     crates/poly mle/dense.rs    class DenseMultilinearExtension: fix_variables, fixed_variables,
 //     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations
+//   SparseMultilinearExtension<RqNTT>    crates/poly mle/sparse.rs   class SparseMultilinearExtension: from_slice, from_matrix, fix_variables,
+//     precompute_eq                      sparse.rs:381-394             fixed_variables, evaluate, to_evaluations; eq_table(point); device
+//                                                                      pointers: CyclotomicConfig::eq_table_dev / smle_plan / smle_fix_variables_dev
 //   WithLinfNorm / WithL2Norm for [Fq]   crates/ring/src/traits.rs    RqPolyVec::linf_norm / l2_norm_squared (the flattened coefficients, as
 //     (of flatten_to_coeffs)             :6-36                         little-endian u64 words of the integer), *_per_element; sr_norm_plan,
 //                                                                      sr_norm_batch, and sr_norm_batch_dev through CyclotomicConfig::norm_dev
@@ -187,6 +190,21 @@ public:
     void norm_dev(uint64_t *out, const uint64_t *coeffs, size_t n_coeffs, size_t group, int which, uint64_t *work, size_t work_words,
                   void *stream) const {
         check(sr_norm_batch_dev(raw(), out, coeffs, n_coeffs, group, which, work, work_words, stream), "norm_dev");
+    }
+    // sparse multilinear extensions on device pointers (include/stark_rings_hip.h: sr_eq_table_dev, sr_smle_plan, sr_smle_fix_variables_dev);
+    // smle_plan: {workspace elements, stream operations}; log2_degree as given to the constructor (0 for the reference's own rings)
+    void eq_table_dev(uint64_t *out, const uint64_t *point, size_t n_vars, void *stream) const {
+        check(sr_eq_table_dev(raw(), out, point, n_vars, stream), "eq_table_dev");
+    }
+    std::pair<size_t, int> smle_plan(int log2_degree, size_t nnz, size_t n_out, size_t n_fixed) const {
+        size_t work = 0;
+        int launches = 0;
+        check(sr_smle_plan(ring_, log2_degree, nnz, n_out, n_fixed, &work, &launches), "sr_smle_plan");
+        return {work, launches};
+    }
+    void smle_fix_variables_dev(uint64_t *out_vals, const uint64_t *vals, const uint64_t *idx, size_t nnz, const uint64_t *seg_ptr, size_t n_out,
+                                const uint64_t *point, size_t n_fixed, uint64_t *work, size_t work_elems, void *stream) const {
+        check(sr_smle_fix_variables_dev(raw(), out_vals, vals, idx, nnz, seg_ptr, n_out, point, n_fixed, work, work_elems, stream), "smle_fix_variables_dev");
     }
     // packed-u32 BabyBear boundary (the low half of the reference's Fp64 limb, babybear/mod.rs:18-26)
     void pack32_dev(uint32_t *out, const uint64_t *in, size_t batch, void *stream) const { check(sr_pack32_batch_dev(raw(), out, in, batch, stream), "pack32_dev"); }
@@ -432,6 +450,83 @@ private:
     CyclotomicConfig cfg_;
     size_t nv_;
     std::vector<uint64_t> w_;
+};
+
+// precompute_eq (crates/poly mle/sparse.rs:381-394): the 2^len eq(point, .) elements, bit 0 of the index <-> point[0]
+inline RqNTTVec eq_table(const RqNTTVec &point) {
+    const CyclotomicConfig &cfg = point.config();
+    if (point.len() >= 48) throw std::length_error("eq_table: too many variables");
+    std::vector<uint64_t> out(cfg.words_per_elem() << point.len());
+    const uint64_t dummy = 0;
+    CyclotomicConfig::check(sr_eq_table(cfg.raw(), out.data(), point.len() ? point.words().data() : &dummy, point.len()), "sr_eq_table");
+    return RqNTTVec(cfg, std::move(out));
+}
+
+// SparseMultilinearExtension<RqNTT> of crates/poly (src/mle/sparse.rs): the stored evaluations as ascending indices and their values
+// in CRT/NTT form, the iteration order of the reference's BTreeMap.  Stored zeros are kept.  Host buffers over sr_smle_fix_variables;
+// rand, relabel, Add / Sub of two sparse MLEs and ark-serialize are not mirrored.  Throws where the reference asserts.
+class SparseMultilinearExtension {
+public:
+    SparseMultilinearExtension(CyclotomicConfig cfg, size_t num_vars, std::vector<uint64_t> indices, std::vector<uint64_t> value_words)
+        : cfg_(std::move(cfg)), nv_(num_vars), idx_(std::move(indices)), w_(std::move(value_words)) {
+        if (w_.size() != idx_.size() * cfg_.words_per_elem()) throw std::length_error("one value per index");
+        std::vector<uint64_t> keys(idx_.size()), seg(idx_.size() + 1);
+        size_t n = 0;
+        CyclotomicConfig::check(sr_smle_fix_pattern(idx_.data(), idx_.size(), nv_, 0, keys.data(), seg.data(), &n), "SparseMultilinearExtension");
+    }
+    // sparse.rs:125-134: a dense slice, entry i at index i
+    static SparseMultilinearExtension from_slice(size_t num_vars, const RqNTTVec &v) {
+        std::vector<uint64_t> idx(v.len());
+        for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+        return SparseMultilinearExtension(v.config(), num_vars, std::move(idx), v.words());
+    }
+    // sparse.rs:97-115 on a CSR triple with ascending columns in every row: index = row * next_pow2(ncols) + col
+    static SparseMultilinearExtension from_matrix(const RqNTTVec &vals, const std::vector<uint32_t> &cols, const std::vector<uint64_t> &row_ptr,
+                                                  size_t nrows, size_t ncols) {
+        auto np2 = [](size_t n) { size_t p = 1; while (p < n) p <<= 1; return p; };
+        const size_t n_cols = np2(ncols);
+        size_t nv = 0;
+        while (((size_t)1 << nv) < np2(nrows) * n_cols) nv++;
+        std::vector<uint64_t> idx;
+        for (size_t r = 0; r < nrows; r++)
+            for (uint64_t j = row_ptr[r]; j < row_ptr[r + 1]; j++) idx.push_back(r * n_cols + cols[j]);
+        return SparseMultilinearExtension(vals.config(), nv, std::move(idx), vals.words());
+    }
+    size_t num_vars() const { return nv_; }
+    size_t len() const { return idx_.size(); }
+    const std::vector<uint64_t> &indices() const { return idx_; }
+    const std::vector<uint64_t> &words() const { return w_; }
+
+    void fix_variables(const RqNTTVec &partial_point) { *this = fixed_variables(partial_point); }  // sparse.rs:170-207
+    SparseMultilinearExtension fixed_variables(const RqNTTVec &partial_point) const {               // sparse.rs:209-213
+        if (partial_point.len() > nv_) throw std::length_error("invalid partial point dimension");
+        std::vector<uint64_t> out(w_.size()), keys(idx_.size());
+        size_t n = 0;
+        const uint64_t dummy = 0;
+        CyclotomicConfig::check(sr_smle_fix_variables(cfg_.raw(), out.data(), keys.data(), &n, w_.data(), idx_.data(), idx_.size(), nv_,
+                                                      partial_point.len() ? partial_point.words().data() : &dummy, partial_point.len()),
+                                "sr_smle_fix_variables");
+        out.resize(n * cfg_.words_per_elem());
+        keys.resize(n);
+        return SparseMultilinearExtension(cfg_, nv_ - partial_point.len(), std::move(keys), std::move(out));
+    }
+    // sparse.rs:53-56; an MLE with no stored entry evaluates to zero() (sparse.rs:359-365)
+    RqNTTVec evaluate(const RqNTTVec &point) const {
+        if (point.len() != nv_) throw std::length_error("evaluate: the point must have num_vars entries");
+        SparseMultilinearExtension f = fixed_variables(point);
+        return RqNTTVec(cfg_, f.len() ? f.w_ : std::vector<uint64_t>(cfg_.words_per_elem(), 0));
+    }
+    RqNTTVec to_evaluations() const {  // all 2^num_vars elements, the stored ones scattered
+        const size_t w = cfg_.words_per_elem();
+        std::vector<uint64_t> all(w << nv_, 0);
+        for (size_t j = 0; j < idx_.size(); j++) std::copy(w_.begin() + j * w, w_.begin() + (j + 1) * w, all.begin() + idx_[j] * w);
+        return RqNTTVec(cfg_, std::move(all));
+    }
+
+private:
+    CyclotomicConfig cfg_;
+    size_t nv_;
+    std::vector<uint64_t> idx_, w_;
 };
 
 // `iter.fold(Self::one(), |acc, x| acc * x)` with the ring product = icrt(product(crt(x_i))): the CRT is a ring isomorphism

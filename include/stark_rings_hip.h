@@ -243,6 +243,54 @@ int sr_mle_fix_variables_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_eva
                              size_t n_fixed, int order, uint64_t *d_work, size_t work_elems, void *stream);
 int sr_mle_fix_variables(sr_ctx *ctx, uint64_t *out, const uint64_t *evals, size_t n_evals, size_t num_vars, const uint64_t *point,
                          size_t n_fixed, int order);
+/* Sparse multilinear extensions: the arithmetic of crates/poly's SparseMultilinearExtension (mle/sparse.rs) on device-resident
+ * values.  Elements are ring elements in CRT / NTT form in the usual flat layout, canonical in and canonical out, for every ring id.
+ *
+ * sr_eq_table: out[b] = prod_i (bit i of b ? point[i] : one() - point[i]) for b < 2^n_vars, bit 0 <-> point[0]: precompute_eq
+ * (sparse.rs:381-394), bit-identical to its doubling recurrence (exact arithmetic on canonical values; the factors commute).
+ * n_vars = 0 gives the single element one().  sum_b out[b] f[b] = f(point) for a dense table f.  One launch, no workspace, no
+ * context scratch; d_out overlapping d_point is SR_E_INVALID.
+ *
+ * A sparse MLE is (num_vars < 64; idx: nnz u64 indices, strictly ascending, each < 2^num_vars -- the BTreeMap's iteration order;
+ * vals: nnz ring elements in the same order).  Stored zeros are legal and are kept.  Fixing the first n_fixed variables
+ * (fix_variables, sparse.rs:170-207) sends entry j to key idx[j] >> n_fixed; idx ascends, so equal keys are contiguous RUNS and
+ *     out_vals[s] = sum over the entries j of run s of eq(point, idx[j] & (2^n_fixed - 1)) * vals[j],
+ * one output per distinct key, in ascending key order; an output whose sum is zero stays (the reference's map keeps it too).
+ *   n_fixed == num_vars is `evaluate` (sparse.rs:53-56): n_out is 1 when nnz > 0.
+ *   nnz == 0 gives n_out == 0 and touches nothing (the value of an empty MLE is zero(), sparse.rs:359-365: the mirrors return it).
+ *   n_fixed == 0 copies.
+ * sr_smle_fix_pattern: host arithmetic, no device, no context.  Validates idx and writes the n_out distinct keys to out_idx (room for
+ * nnz) and the run boundaries to seg_ptr (room for nnz + 1): run s is the entries seg_ptr[s] .. seg_ptr[s + 1] - 1,
+ * seg_ptr[n_out] = nnz.  SR_E_INVALID: num_vars >= 64, n_fixed > num_vars, indices not strictly ascending or >= 2^num_vars, null
+ * pointers.
+ * sr_smle_plan: host arithmetic: the workspace in ring elements and the stream operations (at least 1) of a fold of nnz entries in
+ * n_out runs.  The plan depends on nnz and n_out only, never on the run lengths:
+ *   - the entries are cut into spans of consecutive entries, at most nnz / 2 of them; a run that crosses a span boundary leaves
+ *     partial elements in the workspace (two per span at most) which a second launch adds.  n_out == nnz (every run is one entry)
+ *     cannot cross one and takes no such launch;
+ *   - nnz >= SR_SMLE_TABLE_MIN_NNZ with n_fixed >= 2: eq(point, x) is taken as a product over windows of SR_SMLE_WINDOW_BITS
+ *     variables, whose eq tables one more launch builds in the workspace (ceil(n_fixed / window) tables of 2^window elements);
+ *     below, point[i] or one() - point[i] are multiplied in on the fly and no table exists.
+ *   work_elems <= nnz + SR_SMLE_MAX_TABLE_ELEMS, and work_elems == 0 whenever launches == 1.
+ * sr_smle_fix_variables_dev: d_idx and d_seg_ptr are device copies of what sr_smle_fix_pattern saw and wrote; they are NOT validated
+ * (corrupt arrays give wrong values, never an access outside the buffers).  SR_E_INVALID: null pointers, n_fixed >= 64, n_out > nnz,
+ * work_elems below the plan, d_out_vals overlapping d_vals, d_point or d_work.  Nothing is allocated, no context scratch is touched and
+ * every workspace word that is read was written by the same call: the call can sit in a captured graph (one stream, a linear chain)
+ * and be replayed on changed values and points.
+ * sr_smle_fix_variables (host pointers): validates, runs the pattern itself (out_idx: room for nnz keys, out_vals: room for nnz
+ * elements; *n_out of each are written) and stages like sr_mle_fix_variables. */
+#define SR_SMLE_WINDOW_BITS 8
+#define SR_SMLE_TABLE_MIN_NNZ 1024
+#define SR_SMLE_MAX_TABLE_ELEMS 2048 /* ceil(63 / SR_SMLE_WINDOW_BITS) << SR_SMLE_WINDOW_BITS */
+int sr_eq_table_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_point, size_t n_vars, void *stream);
+int sr_eq_table(sr_ctx *ctx, uint64_t *out, const uint64_t *point, size_t n_vars);
+int sr_smle_fix_pattern(const uint64_t *idx, size_t nnz, size_t num_vars, size_t n_fixed, uint64_t *out_idx, uint64_t *seg_ptr, size_t *n_out);
+int sr_smle_plan(int ring, int log2_degree, size_t nnz, size_t n_out, size_t n_fixed, size_t *work_elems, int *launches);
+int sr_smle_fix_variables_dev(sr_ctx *ctx, uint64_t *d_out_vals, const uint64_t *d_vals, const uint64_t *d_idx, size_t nnz,
+                              const uint64_t *d_seg_ptr, size_t n_out, const uint64_t *d_point, size_t n_fixed, uint64_t *d_work,
+                              size_t work_elems, void *stream);
+int sr_smle_fix_variables(sr_ctx *ctx, uint64_t *out_vals, uint64_t *out_idx, size_t *n_out, const uint64_t *vals, const uint64_t *idx,
+                          size_t nnz, size_t num_vars, const uint64_t *point, size_t n_fixed);
 /* Norms of a coefficient slice on the device: WithLinfNorm::linf_norm / WithL2Norm::l2_norm_squared over [Fq]
  * (crates/ring/src/traits.rs:6-36; per element balanced_decomposition/convertible_ring.rs:49-66; the signed representative of
  * fq_convertible.rs:20-34 and stark_prime/decomposition.rs:40-52).

@@ -6,7 +6,7 @@ Layout:
   rings.py              host-side mirror of the reference interface (CyclotomicConfig / CRT / ICRT /
                         Flatten at batch granularity) on top of the C ABI
   wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix around the device codec
-  mle.py                DenseMultilinearExtension of crates/poly over a device-resident table (fix_variables, evaluate)
+  mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
   sharding.py           batch sharding across the GPUs of one node (one process per GPU)
 """
@@ -21,4 +21,4 @@ from .rings import (  # noqa: F401
     CyclotomicRing,
     RingError,
 )
-from .mle import DenseMultilinearExtension  # noqa: F401
+from .mle import DenseMultilinearExtension, SparseMultilinearExtension  # noqa: F401

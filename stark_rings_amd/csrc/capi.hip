@@ -30,6 +30,7 @@
 #include "packed32.hpp"
 #include "mle.hpp"
 #include "norms.hpp"
+#include "sparse_mle.hpp"
 
 namespace {
 
@@ -1583,6 +1584,84 @@ int check_mle(sr_ctx *c, const void *out, const void *evals, size_t n_evals, siz
     return check_count(c, p.work_elems);
 }
 
+// ---- sparse multilinear extensions (csrc/sparse_mle.hpp): nothing allocated, no context scratch ----------------------------------
+sr::smle::One smle_one(const sr_ctx *c) {
+    sr::smle::One one;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: case SR_RING_GOLDILOCKS_24: mont_one_image<sr::Goldilocks>(one.w); break;
+        case SR_RING_BABYBEAR_POW2: case SR_RING_BABYBEAR_72: mont_one_image<sr::BabyBear>(one.w); break;
+        case SR_RING_FROG_16: mont_one_image<sr::Frog>(one.w); break;
+        default: mont_one_image<sr::Stark>(one.w); break;
+    }
+    return one;
+}
+extern "C++" {
+template <class O, int J> struct SmleKind {
+    using Ops = O;
+    static constexpr int kJ = J;
+};
+// fn(kind, constants, log2 of the units per element) for the unit the context's ring and these buffers allow; `aligned`: every
+// buffer of the call starts on a 16-byte boundary
+template <class Fn>
+int smle_dispatch(sr_ctx *c, bool aligned, Fn fn) {
+    namespace sm = sr::smle;
+    const bool pair = aligned && c->k >= 1;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2:
+            return pair ? fn(SmleKind<sm::PowOps<sr::Goldilocks, sr::Goldilocks, 2>, sm::kEqJ<sr::Goldilocks>>{}, 0, c->k - 1)
+                        : fn(SmleKind<sm::PowOps<sr::Goldilocks, sr::Goldilocks, 1>, sm::kEqJ<sr::Goldilocks>>{}, 0, c->k);
+        case SR_RING_BABYBEAR_POW2:
+            return pair ? fn(SmleKind<sm::PowOps<sr::BabyBear, sr::BabyBear, 2>, sm::kEqJ<sr::BabyBear>>{}, 0, c->k - 1)
+                        : fn(SmleKind<sm::PowOps<sr::BabyBear, sr::BabyBear, 1>, sm::kEqJ<sr::BabyBear>>{}, 0, c->k);
+        case SR_RING_STARK_POW2:  // the sums of products run on 28-bit lazy limbs where the context's transforms do (stark_lazy.hpp)
+            return on_stark_lazy(c->path) ? fn(SmleKind<sm::PowOps<sr::Stark, sr::StarkL, 4>, sm::kEqJ<sr::Stark>>{}, 0, c->k)
+                                          : fn(SmleKind<sm::PowOps<sr::Stark, sr::Stark, 4>, sm::kEqJ<sr::Stark>>{}, 0, c->k);
+        case SR_RING_GOLDILOCKS_24: return fn(SmleKind<sm::SlotOps<sr::SlotG24>, sm::kSlotEqJ<sr::SlotG24>>{}, c->small, 3);
+        case SR_RING_BABYBEAR_72: return fn(SmleKind<sm::SlotOps<sr::SlotB72>, sm::kSlotEqJ<sr::SlotB72>>{}, c->small, 3);
+        default: return fn(SmleKind<sm::SlotOps<sr::SlotFrog>, sm::kSlotEqJ<sr::SlotFrog>>{}, c->frog, 2);
+    }
+}
+}  // extern "C++"
+bool aligned16(std::initializer_list<const void *> ps) {
+    uintptr_t x = 0;
+    for (const void *p : ps) x |= (uintptr_t)p;
+    return (x & 15u) == 0;
+}
+int dev_eq_table(sr_ctx *c, uint64_t *out, const uint64_t *point, size_t n_vars, hipStream_t st) {
+    ProfScope ps(c, st, K_POINTWISE);
+    const sr::smle::One one = smle_one(c);
+    return smle_dispatch(c, aligned16({out, point}), [&](auto kind, const auto &k, int lu) {
+        using Kind = decltype(kind);
+        const hipError_t e = sr::smle::launch_eq<typename Kind::Ops, Kind::kJ>(k, one, out, point, (unsigned)n_vars, (unsigned)n_vars, 1, lu, st);
+        return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("eq table launch: ") + hipGetErrorString(e));
+    });
+}
+// the fold of a checked call (nnz >= 1, p from smle_plan_for)
+int dev_smle_fix(sr_ctx *c, const sr::smle::Plan &p, uint64_t *out, const uint64_t *vals, const uint64_t *idx, size_t nnz, const uint64_t *seg,
+                 size_t n_out, const uint64_t *point, size_t n_fixed, uint64_t *work, hipStream_t st) {
+    const size_t w = (size_t)c->degree * c->limbs;
+    if (p.copy) {
+        HIP_TRY(hipMemcpyAsync(out, vals, nnz * w * 8, hipMemcpyDeviceToDevice, st));
+        return SR_OK;
+    }
+    ProfScope ps(c, st, K_POINTWISE);
+    const sr::smle::One one = smle_one(c);
+    return smle_dispatch(c, aligned16({out, vals, point, work}), [&](auto kind, const auto &k, int lu) {
+        using Kind = decltype(kind);
+        const hipError_t e = sr::smle::launch_fold<typename Kind::Ops, Kind::kJ>(k, one, p, out, vals, idx, seg, n_out, nnz, point, (unsigned)n_fixed,
+                                                                               work, lu, w, st);
+        return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("sparse mle launch: ") + hipGetErrorString(e));
+    });
+}
+// the shape checks sr_smle_plan and the two forms of sr_smle_fix_variables share
+int smle_plan_for(int ring, int k, size_t nnz, size_t n_out, size_t n_fixed, sr::smle::Plan *p) {
+    if (n_fixed >= 64) return fail(SR_E_INVALID, "smle: n_fixed must be below 64");
+    if (n_out > nnz) return fail(SR_E_INVALID, "smle: n_out exceeds nnz");
+    if (nnz && !n_out) return fail(SR_E_INVALID, "smle: n_out is zero but entries are stored");
+    if (!sr::smle::plan(ring, k, nnz, n_out, n_fixed, p)) return fail(SR_E_INVALID, "smle: no plan for these arguments");
+    return SR_OK;
+}
+
 // ---- norms of coefficient slices (csrc/norms.hpp): nothing allocated, no context scratch ------------------------------------------------
 template <class F>
 int norm_launch(sr_ctx *c, const sr::norms::Plan &p, int which, uint64_t *out, const uint64_t *coeffs, uint64_t *work, hipStream_t st) {
@@ -2168,6 +2247,93 @@ int sr_mle_fix_variables(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t
                   [&](void *const *d) {
                       return dev_mle_fix(c, (uint64_t *)d[2], (const uint64_t *)d[0], n_evals, num_vars, (const uint64_t *)d[1], n_fixed, order,
                                          (uint64_t *)d[3], c->stream);
+                  });
+}
+int sr_eq_table_dev(sr_ctx *c, uint64_t *out, const uint64_t *point, size_t n_vars, void *stream) {
+    if (int rc = check(c, {out, n_vars ? (const void *)point : (const void *)1})) return rc;
+    if (n_vars >= 48) return fail(SR_E_INVALID, "eq_table: n_vars must be below 48");
+    if (int rc = check_count(c, (size_t)1 << n_vars)) return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    if (ranges_overlap(out, w << n_vars, point, n_vars * w)) return fail(SR_E_INVALID, "eq_table: d_out overlaps d_point");
+    const Call call(c, stream);
+    return dev_eq_table(c, out, point, n_vars, call.st);
+}
+int sr_eq_table(sr_ctx *c, uint64_t *out, const uint64_t *point, size_t n_vars) {
+    if (int rc = check(c, {out, n_vars ? (const void *)point : (const void *)1})) return rc;
+    if (n_vars >= 48) return fail(SR_E_INVALID, "eq_table: n_vars must be below 48");
+    if (int rc = check_count(c, (size_t)1 << n_vars)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    return staged(c, {{point, nullptr, n_vars * w}, {nullptr, out, w << n_vars}},
+                  [&](void *const *d) { return dev_eq_table(c, (uint64_t *)d[1], (const uint64_t *)d[0], n_vars, c->stream); });
+}
+int sr_smle_fix_pattern(const uint64_t *idx, size_t nnz, size_t num_vars, size_t n_fixed, uint64_t *out_idx, uint64_t *seg_ptr, size_t *n_out) {
+    if (num_vars >= 64) return fail(SR_E_INVALID, "smle: num_vars must be below 64");
+    if (n_fixed > num_vars) return fail(SR_E_INVALID, "smle: n_fixed exceeds num_vars");
+    if (!n_out || !seg_ptr || (nnz && (!idx || !out_idx))) return fail(SR_E_INVALID, "smle: null buffer");
+    const uint64_t limit = (uint64_t)1 << num_vars;
+    size_t n = 0;
+    for (size_t j = 0; j < nnz; j++) {
+        if (idx[j] >= limit) return fail(SR_E_INVALID, "smle: index " + std::to_string(j) + " is not below 2^num_vars");
+        if (j && idx[j] <= idx[j - 1]) return fail(SR_E_INVALID, "smle: indices must be strictly ascending (entry " + std::to_string(j) + ")");
+        const uint64_t key = idx[j] >> n_fixed;
+        if (!n || key != out_idx[n - 1]) {
+            out_idx[n] = key;
+            seg_ptr[n++] = j;
+        }
+    }
+    seg_ptr[n] = nnz;
+    *n_out = n;
+    return SR_OK;
+}
+int sr_smle_plan(int ring, int log2_degree, size_t nnz, size_t n_out, size_t n_fixed, size_t *work_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "smle_plan: null result pointer");
+    sr::smle::Plan p;
+    if (int rc = smle_plan_for(ring, log2_degree, nnz, n_out, n_fixed, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_smle_fix_variables_dev(sr_ctx *c, uint64_t *out, const uint64_t *vals, const uint64_t *idx, size_t nnz, const uint64_t *seg, size_t n_out,
+                              const uint64_t *point, size_t n_fixed, uint64_t *work, size_t work_elems, void *stream) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    sr::smle::Plan p;
+    if (int rc = smle_plan_for(c->ring, c->k, nnz, n_out, n_fixed, &p)) return rc;
+    if (nnz == 0) return SR_OK;
+    if (!out || !vals || !idx || !seg || (n_fixed && !point) || (p.work_elems && !work)) return fail(SR_E_INVALID, "smle: null buffer");
+    if (int rc = check_count(c, nnz)) return rc;
+    if (int rc = check_count(c, p.work_elems)) return rc;
+    if (work_elems < p.work_elems)
+        return fail(SR_E_INVALID, "smle: workspace too small (sr_smle_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    if (ranges_overlap(out, n_out * w, vals, nnz * w)) return fail(SR_E_INVALID, "smle: d_out_vals overlaps d_vals");
+    if (ranges_overlap(out, n_out * w, point, n_fixed * w)) return fail(SR_E_INVALID, "smle: d_out_vals overlaps d_point");
+    if (ranges_overlap(out, n_out * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "smle: d_out_vals overlaps d_work");
+    const Call call(c, stream);
+    return dev_smle_fix(c, p, out, vals, idx, nnz, seg, n_out, point, n_fixed, work, call.st);
+}
+int sr_smle_fix_variables(sr_ctx *c, uint64_t *out_vals, uint64_t *out_idx, size_t *n_out, const uint64_t *vals, const uint64_t *idx, size_t nnz,
+                          size_t num_vars, const uint64_t *point, size_t n_fixed) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!n_out || (nnz && (!out_vals || !out_idx || !vals || !idx)) || (nnz && n_fixed && !point)) return fail(SR_E_INVALID, "smle: null buffer");
+    if (int rc = check_count(c, nnz)) return rc;
+    std::vector<uint64_t> meta(2 * nnz + 1);  // [idx | seg_ptr]: one staged operand
+    if (int rc = sr_smle_fix_pattern(idx, nnz, num_vars, n_fixed, out_idx, meta.data() + nnz, n_out)) return rc;
+    if (nnz == 0) return SR_OK;
+    memcpy(meta.data(), idx, nnz * 8);
+    sr::smle::Plan p;
+    if (int rc = smle_plan_for(c->ring, c->k, nnz, *n_out, n_fixed, &p)) return rc;
+    if (int rc = check_count(c, p.work_elems)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8, no = *n_out;
+    return staged(c, {{vals, nullptr, nnz * w}, {meta.data(), nullptr, (nnz + no + 1) * 8}, {point, nullptr, n_fixed * w}, {nullptr, out_vals, no * w},
+                      {nullptr, nullptr, p.work_elems * w}},
+                  [&](void *const *d) {
+                      const uint64_t *dm = (const uint64_t *)d[1];
+                      return dev_smle_fix(c, p, (uint64_t *)d[3], (const uint64_t *)d[0], dm, nnz, dm + nnz, no, (const uint64_t *)d[2], n_fixed,
+                                          (uint64_t *)d[4], c->stream);
                   });
 }
 int sr_norm_plan(int ring, size_t n_coeffs, size_t group, int which, size_t *out_words_per_group, size_t *work_words, int *launches) {

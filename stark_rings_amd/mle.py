@@ -1,11 +1,14 @@
-"""DenseMultilinearExtension of crates/poly (src/mle/dense.rs) over a device-resident table of ring elements in CRT/NTT form.
+"""DenseMultilinearExtension (src/mle/dense.rs) and, at the end of the file, SparseMultilinearExtension (src/mle/sparse.rs) of
+crates/poly.  The dense class: DenseMultilinearExtension (src/mle/dense.rs) over a device-resident table of ring elements in CRT/NTT form.
 
 The evaluations live in one torch CUDA tensor of 8-byte integers in the flat layout of every other call (element-major, D
 coefficients per element, N u64 limbs each, Montgomery residues).  Like the reference's constructor (dense.rs:35-54) the object may
 hold fewer than 2^num_vars elements: the missing tail is zero and is never read.  Folds run through sr_mle_fix_variables_dev
 (include/stark_rings_hip.h); `r * a` is the slot product of the ring.
 """
-from .rings import MLE_LEADING, MLE_TRAILING, RingError
+import numpy as np
+
+from .rings import MLE_LEADING, MLE_TRAILING, RingError, smle_fix_pattern
 
 
 class DenseMultilinearExtension:
@@ -26,6 +29,17 @@ class DenseMultilinearExtension:
         """dense.rs:79-89 `from_evaluations_vec_padded`: a vector shorter than 2^num_vars is padded with zeros -- here the padding
         stays implicit (the zero tail is never stored or read); to_evaluations writes it out."""
         return cls(ring, num_vars, evaluations)
+
+    @classmethod
+    def eq(cls, ring, point, stream=None):
+        """The table b -> eq(point, b) = prod_i (b_i ? point[i] : 1 - point[i]) as a dense MLE of len(point) variables
+        (precompute_eq, sparse.rs:381-394): sum_b eq[b] f[b] = f(point)."""
+        import torch
+
+        n = ring._batch_of(point.numel())
+        out = torch.empty(ring.words_per_elem << n, dtype=point.dtype, device=point.device)
+        ring.eq_table_dev(out, point, stream)
+        return cls(ring, n, out)
 
     @property
     def num_vars(self):
@@ -93,4 +107,142 @@ class DenseMultilinearExtension:
             return self.evaluations.clone()
         out = torch.zeros(full, dtype=self.evaluations.dtype, device=self.evaluations.device)
         out[:self.evaluations.numel()] = self.evaluations
+        return out
+
+
+def _next_pow2(n):
+    return 1 if n <= 1 else 1 << (n - 1).bit_length()
+
+
+class SparseMultilinearExtension:
+    """mle/sparse.rs: the evaluations that are stored, as (indices, values) in ascending index order -- the iteration order of the
+    reference's BTreeMap.  indices: a host numpy uint64 array; values: one CUDA tensor of len(indices) ring elements in CRT/NTT
+    form.  Stored zeros are legal and are kept, as from_evaluations and fix_variables keep them.  rand / rand_with_config, relabel,
+    Add / Sub of two sparse MLEs and ark-serialize of the map are not mirrored (index-set merging and host bookkeeping)."""
+
+    def __init__(self, ring, num_vars, indices, values):
+        indices = np.ascontiguousarray(indices, dtype=np.uint64)
+        if not 0 <= num_vars < 64:
+            raise RingError("SparseMultilinearExtension: num_vars must be below 64")
+        if ring._batch_of(values.numel()) != indices.size:
+            raise RingError("SparseMultilinearExtension: one value per index")
+        smle_fix_pattern(indices, num_vars, 0)  # ascending, below 2^num_vars
+        if indices.size:
+            ring._dev(values)
+        self.ring = ring
+        self._num_vars = int(num_vars)
+        self.indices = indices
+        self.values = values
+        self._work = None
+
+    @classmethod
+    def from_evaluations(cls, ring, num_vars, indices, values):
+        """sparse.rs:33-51: any order of distinct indices; the values are gathered into ascending index order only if needed."""
+        import torch
+
+        indices = np.ascontiguousarray(indices, dtype=np.uint64)
+        if indices.size > 1 and not np.all(indices[1:] > indices[:-1]):
+            order = np.argsort(indices, kind="stable")
+            indices = indices[order]
+            if np.any(indices[1:] == indices[:-1]):
+                raise RingError("SparseMultilinearExtension: an index is stored twice")
+            perm = torch.from_numpy(order.astype(np.int64)).to(values.device)
+            values = values.view(-1, ring.words_per_elem)[perm].reshape(-1).contiguous()
+        return cls(ring, num_vars, indices, values)
+
+    from_sparse_slice = from_evaluations  # sparse.rs:117-123
+
+    @classmethod
+    def from_slice(cls, ring, num_vars, values):
+        """sparse.rs:125-134: a dense slice, entry i at index i (zeros are stored too)."""
+        return cls(ring, num_vars, np.arange(ring._batch_of(values.numel()), dtype=np.uint64), values)
+
+    @staticmethod
+    def matrix_indices(cols, row_ptr, nrows, ncols):
+        """sparse.rs:97-115: (num_vars, index of every stored entry) of an nrows x ncols CSR matrix: row * next_pow2(ncols) + col."""
+        cols, row_ptr = np.asarray(cols, dtype=np.uint64), np.asarray(row_ptr, dtype=np.uint64)
+        n_rows, n_cols = _next_pow2(nrows), _next_pow2(ncols)
+        rows = np.repeat(np.arange(nrows, dtype=np.uint64), np.diff(row_ptr).astype(np.int64))
+        return (n_rows * n_cols).bit_length() - 1, rows * np.uint64(n_cols) + cols
+
+    @classmethod
+    def from_matrix(cls, ring, vals, cols, row_ptr, nrows, ncols):
+        """from_matrix on the CSR triple of spmv_ntt_dev (vals: a CUDA tensor, used where it lies; cols, row_ptr: host arrays or
+        tensors).  The values are gathered by a permutation only if the columns of some row are not ascending."""
+        to_np = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        num_vars, idx = cls.matrix_indices(to_np(cols), to_np(row_ptr), nrows, ncols)
+        return cls.from_evaluations(ring, num_vars, idx, vals)
+
+    @property
+    def num_vars(self):
+        return self._num_vars
+
+    def __len__(self):
+        return self.indices.size
+
+    def _fold(self, point, stream):
+        import torch
+
+        ring = self.ring
+        n_fixed = ring._batch_of(point.numel()) if point is not None else 0
+        if n_fixed > self._num_vars:
+            raise RingError("fix_variables: invalid partial point dimension")  # sparse.rs:172 asserts
+        out_idx, seg = smle_fix_pattern(self.indices, self._num_vars, n_fixed)
+        dev = self.values.device
+        out = torch.empty(out_idx.size * ring.words_per_elem, dtype=self.values.dtype, device=dev)
+        if out_idx.size:
+            need = ring.smle_plan(self.indices.size, out_idx.size, n_fixed)[0]
+            if need and (self._work is None or self._work.numel() < need * ring.words_per_elem):
+                self._work = torch.empty(need * ring.words_per_elem, dtype=self.values.dtype, device=dev)
+            d_idx = torch.from_numpy(self.indices.view(np.int64)).to(dev)
+            d_seg = torch.from_numpy(seg.view(np.int64)).to(dev)
+            ring.smle_fix_variables_dev(out, self.values, d_idx, d_seg, point, self._work if need else None, stream)
+        return out_idx, out, self._num_vars - n_fixed
+
+    def fix_variables(self, partial_point, stream=None):
+        """sparse.rs:170-207: fixes variables 0 .. len(partial_point) - 1 and rebinds this object to the result."""
+        self.indices, self.values, self._num_vars = self._fold(partial_point, stream)
+        return self
+
+    def fixed_variables(self, partial_point, stream=None):
+        """sparse.rs:209-213: the same as a new object."""
+        idx, vals, nv = self._fold(partial_point, stream)
+        return SparseMultilinearExtension(self.ring, nv, idx, vals)
+
+    def _zero(self):
+        import torch
+
+        return torch.zeros(self.ring.words_per_elem, dtype=self.values.dtype, device=self.values.device)
+
+    def evaluate(self, point, stream=None):
+        """sparse.rs:53-56: the value at `point` (one ring element); an MLE with no stored entry evaluates to zero()."""
+        if self.ring._batch_of(point.numel()) != self._num_vars:
+            raise RingError("evaluate: the point must have num_vars entries")  # sparse.rs:54 asserts
+        idx, vals, _ = self._fold(point, stream)
+        return vals if idx.size else self._zero()
+
+    def __getitem__(self, index):
+        """sparse.rs:346-365 `Index`: the stored evaluation at `index`, zero() where none is stored."""
+        j = int(np.searchsorted(self.indices, np.uint64(index)))
+        if j < self.indices.size and int(self.indices[j]) == int(index):
+            w = self.ring.words_per_elem
+            return self.values[j * w:(j + 1) * w]
+        return self._zero()
+
+    def neg(self, stream=None):
+        """sparse.rs `Neg`: every stored value negated (sr_neg_batch_dev), as a new object."""
+        vals = self.values.clone()
+        if self.indices.size:
+            self.ring.neg_dev(vals, stream)
+        return SparseMultilinearExtension(self.ring, self._num_vars, self.indices.copy(), vals)
+
+    def to_evaluations(self):
+        """sparse.rs:136-145 `to_dense_multilinear_extension`'s table: all 2^num_vars elements, the stored ones scattered."""
+        import torch
+
+        w = self.ring.words_per_elem
+        out = torch.zeros(w << self._num_vars, dtype=self.values.dtype, device=self.values.device)
+        if self.indices.size:
+            rows = torch.from_numpy(self.indices.view(np.int64)).to(self.values.device)
+            out.view(-1, w)[rows] = self.values.view(-1, w)
         return out

@@ -56,6 +56,37 @@ def _np_ptr(a):
     return a.ctypes.data_as(_lib.u64p)
 
 
+# SR_SMLE_WINDOW_BITS / SR_SMLE_TABLE_MIN_NNZ / SR_SMLE_MAX_TABLE_ELEMS: the published constants of the sparse-MLE plan
+SMLE_WINDOW_BITS, SMLE_TABLE_MIN_NNZ, SMLE_MAX_TABLE_ELEMS = 8, 1024, 2048
+
+
+def smle_plan(ring, log2_degree, nnz, n_out, n_fixed):
+    """sr_smle_plan: (work_elems, launches) of a sparse fold of nnz entries in n_out runs -- host arithmetic, no device, no context."""
+    if isinstance(ring, str):
+        ring = _RING_NAMES[ring]
+    work, launches = ctypes.c_size_t(), ctypes.c_int()
+    rc = _lib.load().sr_smle_plan(int(ring), int(log2_degree), int(nnz), int(n_out), int(n_fixed), ctypes.byref(work), ctypes.byref(launches))
+    if rc != 0:
+        raise RingError("sr_smle_plan failed (%d): %s" % (rc, _lib.last_error()))
+    return work.value, launches.value
+
+
+def smle_fix_pattern(idx, num_vars, n_fixed):
+    """sr_smle_fix_pattern: (out_idx, seg_ptr) -- the distinct keys idx >> n_fixed in ascending order and the run boundaries
+    (len(out_idx) + 1 entries) of a strictly ascending uint64 index array; validates idx.  Host arithmetic, no device, no context."""
+    idx = np.ascontiguousarray(idx, dtype=np.uint64)
+    nnz = idx.size
+    out_idx, seg = np.empty(max(nnz, 1), dtype=np.uint64), np.empty(nnz + 1, dtype=np.uint64)
+    n_out = ctypes.c_size_t()
+    if num_vars < 0 or n_fixed < 0:
+        raise RingError("smle: negative count")
+    rc = _lib.load().sr_smle_fix_pattern(_np_ptr(idx if nnz else out_idx), nnz, int(num_vars), int(n_fixed), _np_ptr(out_idx), _np_ptr(seg),
+                                         ctypes.byref(n_out))
+    if rc != 0:
+        raise RingError("sr_smle_fix_pattern failed (%d): %s" % (rc, _lib.last_error()))
+    return out_idx[:n_out.value].copy(), seg[:n_out.value + 1].copy()
+
+
 def _basis_words(basis, decompose):
     """(lo, hi) 64-bit words of a decomposition basis (the reference takes b: u128, balanced_decomposition/mod.rs:62).  Anything
     outside [0, 2^128) is refused instead of being truncated by ctypes.  decompose_balanced_in_place casts `b as i128` (mod.rs:73),
@@ -213,6 +244,28 @@ class CyclotomicRing:
         self._check(self._lib.sr_mle_fix_variables(self._ctx, _np_ptr(out), _np_ptr(evals if n_evals else z), n_evals, int(num_vars),
                                                    _np_ptr(point if n_fixed else z), n_fixed, int(order)))
         return out
+
+    # -- sparse multilinear extensions (crates/poly mle/sparse.rs) ---------------------------------------------------------------------
+    def eq_table(self, point):
+        """Host buffers: sr_eq_table -- the 2^n eq(point, .) elements of an n-element point (precompute_eq, sparse.rs:381-394)."""
+        n = self._batch_of(point.size)
+        out = np.empty(self.words_per_elem << n, dtype=np.uint64)
+        self._check(self._lib.sr_eq_table(self._ctx, _np_ptr(out), _np_ptr(point if n else out), n))
+        return out
+
+    def smle_fix_variables(self, vals, idx, num_vars, point):
+        """Host buffers: sr_smle_fix_variables -- (out_vals, out_idx) of the sparse MLE (idx ascending, vals in the same order) with
+        the first len(point) variables fixed (see smle_fix_variables_dev)."""
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        nnz, n_fixed = idx.size, self._batch_of(point.size)
+        if self._batch_of(vals.size) != nnz:
+            raise RingError("smle_fix_variables: one value per index")
+        out_vals, out_idx = np.empty(max(nnz, 1) * self.words_per_elem, dtype=np.uint64), np.empty(max(nnz, 1), dtype=np.uint64)
+        n_out = ctypes.c_size_t()
+        z = np.zeros(1, dtype=np.uint64)
+        self._check(self._lib.sr_smle_fix_variables(self._ctx, _np_ptr(out_vals), _np_ptr(out_idx), ctypes.byref(n_out), _np_ptr(vals if nnz else z),
+                                                    _np_ptr(idx if nnz else z), nnz, int(num_vars), _np_ptr(point if n_fixed else z), n_fixed))
+        return out_vals[:n_out.value * self.words_per_elem].copy(), out_idx[:n_out.value].copy()
 
     # -- norms of coefficient slices (traits.rs:6-36: WithLinfNorm / WithL2Norm over [Fq]) ---------------------------------------
     def norm_plan(self, n_coeffs, group=None, which=NORM_LINF | NORM_L2SQ):
@@ -674,6 +727,39 @@ class CyclotomicRing:
         self._check(self._lib.sr_mle_fix_variables_dev(self._ctx, po, pe, n_evals, int(num_vars), pp, n_fixed, int(order), pw, nw,
                                                        self._stream(stream)))
         return out
+
+    def eq_table_dev(self, out, point, stream=None):
+        """sr_eq_table_dev: out[b] = prod_i (bit i of b ? point[i] : 1 - point[i]) for the n = len(point) elements of `point`
+        (None or empty: out is the single element one()); out holds 2^n elements.  One launch, no workspace; capturable."""
+        po, no = self._dev(out)
+        pp, npt = (self._dev(point) if point is not None and point.numel() else (ctypes.c_void_p(0), 0))
+        n = self._batch_of(npt)
+        if n >= 48 or no != self.words_per_elem << n:
+            raise RingError("eq_table: out must hold 2^len(point) elements")
+        self._check(self._lib.sr_eq_table_dev(self._ctx, po, pp, n, self._stream(stream)))
+        return out
+
+    def smle_plan(self, nnz, n_out, n_fixed):
+        """sr_smle_plan for this ring: (work_elems, launches)."""
+        return smle_plan(self.ring, self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0, nnz, n_out, n_fixed)
+
+    smle_fix_pattern = staticmethod(smle_fix_pattern)
+
+    def smle_fix_variables_dev(self, out_vals, vals, idx, seg_ptr, point, work=None, stream=None):
+        """sr_smle_fix_variables_dev: out_vals[s] = sum over run s of eq(point, idx[j] & (2^n_fixed - 1)) * vals[j].  idx (nnz) and
+        seg_ptr (n_out + 1) are int64 / uint64 CUDA tensors holding what smle_fix_pattern saw and returned; out_vals holds n_out
+        elements.  work: a tensor of at least smle_plan()[0] elements (None only where the plan needs none).  Allocates nothing."""
+        nnz = idx.numel()
+        n_out = seg_ptr.numel() - 1
+        if n_out < 0 or self._batch_of(vals.numel()) != nnz or self._batch_of(out_vals.numel()) != n_out:
+            raise RingError("smle_fix_variables: one value per index and one output element per run")
+        null = ctypes.c_void_p(0)
+        pp, npt = (self._dev(point) if point is not None and point.numel() else (null, 0))
+        pw, nw = (self._dev(work) if work is not None and work.numel() else (null, 0))
+        self._check(self._lib.sr_smle_fix_variables_dev(self._ctx, self._dev(out_vals)[0] if n_out else null, self._dev(vals)[0] if nnz else null,
+                                                        self._dev(idx)[0] if nnz else null, nnz, self._dev(seg_ptr)[0], n_out, pp,
+                                                        self._batch_of(npt), pw, nw // self.words_per_elem, self._stream(stream)))
+        return out_vals
 
     def norm_batch_dev(self, out, coeffs, group=None, which=NORM_LINF | NORM_L2SQ, work=None, stream=None):
         """sr_norm_batch_dev: out = the records (norm_plan()[0] words per group: linf words, then l2sq words; standard-form integers)
