@@ -31,6 +31,10 @@
 //   SparseMultilinearExtension<RqNTT>    crates/poly mle/sparse.rs   class SparseMultilinearExtension: from_slice, from_matrix, fix_variables,
 //     precompute_eq                      sparse.rs:381-394             fixed_variables, evaluate, to_evaluations; eq_table(point); device
 //                                                                      pointers: CyclotomicConfig::eq_table_dev / smle_plan / smle_fix_variables_dev
+//   SymmetricMatrix<RqNTT>               linear_algebra/src/         class SymmetricMatrixNTT (packed: entry (i, j), j <= i, is element i (i + 1) / 2 + j):
+//     from_par_fn(n, |i, j| <s_i, s_j>)  symmetric_matrix.rs:14-92     size, at, diag, rows, zero, from_rows (throws where From asserts), gram
+//   recompose_left_right_symmetric_      balanced_decomposition/     recompose_left_right_symmetric_matrix(mat, powers) / .recompose_left_right;
+//     matrix                             mod.rs:354-386                sr_gram_ntt, sr_symm_recompose (device pointers: the *_dev C calls)
 //   WithLinfNorm / WithL2Norm for [Fq]   crates/ring/src/traits.rs    RqPolyVec::linf_norm / l2_norm_squared (the flattened coefficients, as
 //     (of flatten_to_coeffs)             :6-36                         little-endian u64 words of the integer), *_per_element; sr_norm_plan,
 //                                                                      sr_norm_batch, and sr_norm_batch_dev through CyclotomicConfig::norm_dev
@@ -816,6 +820,96 @@ private:
 };
 
 // ---- CanonicalSerialize / CanonicalDeserialize (ark-serialize; Compress and Validate make no difference for these types) ----
+// SymmetricMatrix<RqNTT> (crates/linear_algebra/src/symmetric_matrix.rs:14-92), packed: the reference's Vec<Vec<F>> rows (row i has
+// i + 1 entries) flattened, entry (i, j) with j <= i is ring element i (i + 1) / 2 + j.  Host buffers over sr_gram_ntt /
+// sr_symm_recompose; throws where the reference asserts.
+class SymmetricMatrixNTT {
+public:
+    SymmetricMatrixNTT(CyclotomicConfig cfg, size_t n, std::vector<uint64_t> packed_words) : cfg_(std::move(cfg)), n_(n), w_(std::move(packed_words)) {
+        if (w_.size() != n_ * (n_ + 1) / 2 * cfg_.words_per_elem()) throw std::length_error("SymmetricMatrixNTT: not n (n + 1) / 2 ring elements");
+    }
+    static SymmetricMatrixNTT zero(const CyclotomicConfig &cfg, size_t n) {  // symmetric_matrix.rs:24-28
+        return SymmetricMatrixNTT(cfg, n, std::vector<uint64_t>(n * (n + 1) / 2 * cfg.words_per_elem(), 0));
+    }
+    // From<Vec<Vec<F>>> (symmetric_matrix.rs:17-22): row i must hold i + 1 elements
+    static SymmetricMatrixNTT from_rows(const CyclotomicConfig &cfg, const std::vector<RqNTTVec> &rows) {
+        std::vector<uint64_t> w;
+        for (size_t i = 0; i < rows.size(); i++) {
+            if (rows[i].len() != i + 1)
+                throw std::length_error("cannot convert value: Vec<Vec<F>> to SymmetricMatrix<F>, row has wrong number of entries");
+            w.insert(w.end(), rows[i].words().begin(), rows[i].words().end());
+        }
+        return SymmetricMatrixNTT(cfg, rows.size(), std::move(w));
+    }
+    // from_par_fn(n, |i, j| sum_t a[i][t] * a[j][t]) (symmetric_matrix.rs:76-90) for the n rows of m elements of `a` (row-major); the
+    // inner-product closure is the caller's, not the reference's
+    static SymmetricMatrixNTT gram(const RqNTTVec &a, size_t n, size_t m) {
+        const CyclotomicConfig &cfg = a.config();
+        if (a.len() != n * m) throw std::length_error("gram: the matrix does not hold n * m elements");
+        std::vector<uint64_t> out(n * (n + 1) / 2 * cfg.words_per_elem());
+        const uint64_t dummy = 0;
+        uint64_t sink = 0;
+        CyclotomicConfig::check(sr_gram_ntt(cfg.raw(), out.empty() ? &sink : out.data(), a.words().empty() ? &dummy : a.words().data(), n, m), "sr_gram_ntt");
+        return SymmetricMatrixNTT(cfg, n, std::move(out));
+    }
+    size_t size() const { return n_; }                            // :31-34
+    static size_t packed_index(size_t i, size_t j) { return j <= i ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+    RqNTTVec at(size_t i, size_t j) const {                       // :36-44: (i, j) with j > i reads (j, i)
+        if (i >= n_ || j >= n_) throw std::out_of_range("SymmetricMatrixNTT::at");
+        const size_t w = cfg_.words_per_elem(), e = packed_index(i, j);
+        return RqNTTVec(cfg_, std::vector<uint64_t>(w_.begin() + e * w, w_.begin() + (e + 1) * w));
+    }
+    RqNTTVec diag() const {                                       // :56-58: the n diagonal elements as one vector
+        std::vector<uint64_t> d;
+        for (size_t i = 0; i < n_; i++) {
+            const RqNTTVec e = at(i, i);
+            d.insert(d.end(), e.words().begin(), e.words().end());
+        }
+        return RqNTTVec(cfg_, std::move(d));
+    }
+    std::vector<RqNTTVec> rows() const {                          // :60-62
+        std::vector<RqNTTVec> r;
+        const size_t w = cfg_.words_per_elem();
+        for (size_t i = 0; i < n_; i++) r.emplace_back(cfg_, std::vector<uint64_t>(w_.begin() + i * (i + 1) / 2 * w, w_.begin() + (i + 1) * (i + 2) / 2 * w));
+        return r;
+    }
+    const std::vector<uint64_t> &words() const { return w_; }
+    const CyclotomicConfig &config() const { return cfg_; }
+    // balanced_decomposition/mod.rs:354-386: G^T * this * G for G = I_n (x) powers_of_basis
+    SymmetricMatrixNTT recompose_left_right(const RqNTTVec &powers_of_basis) const {
+        const size_t d = powers_of_basis.len();
+        if (d == 0 || n_ % d) throw std::length_error("recompose_left_right_symmetric_matrix: the number of powers must divide the size");  // :365
+        const size_t n = n_ / d;
+        std::vector<uint64_t> out(n * (n + 1) / 2 * cfg_.words_per_elem());
+        uint64_t sink = 0;
+        CyclotomicConfig::check(sr_symm_recompose(cfg_.raw(), out.empty() ? &sink : out.data(), w_.empty() ? &sink : w_.data(), n, d,
+                                                  powers_of_basis.words().data()),
+                                "sr_symm_recompose");
+        return SymmetricMatrixNTT(cfg_, n, std::move(out));
+    }
+    // {workspace elements, kernel launches} of the device forms (sr_gram_plan / sr_symm_recompose_plan)
+    static std::pair<size_t, int> gram_plan(sr_ring ring, int log2_degree, size_t n, size_t m) {
+        size_t work = 0;
+        int launches = 0;
+        CyclotomicConfig::check(sr_gram_plan(ring, log2_degree, n, m, &work, &launches), "sr_gram_plan");
+        return {work, launches};
+    }
+    static std::pair<size_t, int> recompose_plan(sr_ring ring, int log2_degree, size_t n, size_t d) {
+        size_t work = 0;
+        int launches = 0;
+        CyclotomicConfig::check(sr_symm_recompose_plan(ring, log2_degree, n, d, &work, &launches), "sr_symm_recompose_plan");
+        return {work, launches};
+    }
+
+private:
+    CyclotomicConfig cfg_;
+    size_t n_;
+    std::vector<uint64_t> w_;
+};
+inline SymmetricMatrixNTT recompose_left_right_symmetric_matrix(const SymmetricMatrixNTT &mat, const RqNTTVec &powers_of_basis) {
+    return mat.recompose_left_right(powers_of_basis);
+}
+
 namespace wire_detail {
 inline void put_u64(std::vector<uint8_t> &out, uint64_t v) {
     for (int i = 0; i < 8; i++) out.push_back((uint8_t)(v >> (8 * i)));

@@ -345,6 +345,36 @@ int sr_matvec_ntt(sr_ctx *ctx, uint64_t *y, const uint64_t *m, const uint64_t *v
 int sr_spmv_ntt(sr_ctx *ctx, uint64_t *y, const uint64_t *vals, const uint32_t *cols, const uint64_t *row_ptr, const uint64_t *v,
                 size_t nrows, size_t ncols);
 int sr_matmul_ntt(sr_ctx *ctx, uint64_t *y, const uint64_t *a, const uint64_t *b, size_t n, size_t m, size_t p);
+/* Symmetric matrices (csrc/symmetric.hpp): SymmetricMatrix<F>, crates/linear_algebra/src/symmetric_matrix.rs:14-92, over ring elements in
+ * CRT/NTT form, every ring id, canonical in and canonical out.  A symmetric matrix of size n is PACKED: n (n + 1) / 2 ring elements,
+ * entry (i, j) with j <= i is element i (i + 1) / 2 + j -- the reference's Vec<Vec<F>> rows (row i has i + 1 entries), flattened.
+ * sr_gram_ntt[_dev]: d_a is a dense row-major n x m matrix, out[i (i + 1) / 2 + j] = sum_{t < m} a[i][t] * a[j][t] with `*` the slot
+ * product of the ring.  This is what SymmetricMatrix::from_par_fn(n, |i, j| <s_i, s_j>) (symmetric_matrix.rs:76-90) yields for the
+ * inner-product closure over n vectors of m ring elements; that closure is the caller's and is not in the reference.  m == 0 gives
+ * all zero(); n == 0 writes nothing.  The sums are exact modular integers: any summation order gives the reference's bits.  Only the
+ * lower triangle is computed, both operands are rows of A (no transposed copy exists), and a short, wide A (few tiles over a long
+ * inner dimension) is cut into spans of the inner dimension whose partial packed matrices go to d_work and are added by a second
+ * launch.
+ * sr_symm_recompose[_dev]: recompose_left_right_symmetric_matrix (crates/ring/src/balanced_decomposition/mod.rs:354-386), G^T M G for
+ * the gadget matrix G = I_n (x) powers.  d_mat is a packed matrix of size n * d, d_powers holds d ring elements (powers_of_basis: ring
+ * elements in the reference too), out is packed of size n: out(i, j) = sum_{a, b < d} mat[(i d + a, j d + b)] * (powers[a] * powers[b]),
+ * where mat[(k, l)] is the symmetric lookup (l > k reads (l, k)).  d == 0 is the reference's division by zero: SR_E_INVALID.  n == 0
+ * writes nothing.  The first launch writes the d^2 weights powers[a] * powers[b] to d_work, the second streams d_mat once.
+ * sr_gram_plan / sr_symm_recompose_plan: pure host arithmetic, no device, no context: the workspace in ring elements and the number
+ * of launches (Gram: 1 without workspace, or 2 with nsplit * n (n + 1) / 2 elements; recompose: 2 with d^2 elements; 0 and 0 for
+ * n == 0).  The Gram's split depends on the shape alone: fewer than 1024 workgroups of tiles, at least 64 inner indices per span (32
+ * for Goldilocks-24 and BabyBear-72), at most 64 spans.
+ * The _dev calls allocate nothing, touch no context scratch, write every workspace word they later read and can be captured into a
+ * HIP graph without a warm-up.  SR_E_INVALID: a null pointer where something would be read or written, work_elems below the plan's,
+ * the output overlapping an input or the workspace, n (n + 1) / 2 or n * d overflowing size_t, a grid past one launch's limit.  The
+ * host-pointer forms stage whole operands in context-owned temporaries. */
+int sr_gram_plan(int ring, int log2_degree, size_t n, size_t m, size_t *work_elems, int *launches);
+int sr_gram_ntt_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_a, size_t n, size_t m, uint64_t *d_work, size_t work_elems, void *stream);
+int sr_gram_ntt(sr_ctx *ctx, uint64_t *out, const uint64_t *a, size_t n, size_t m);
+int sr_symm_recompose_plan(int ring, int log2_degree, size_t n, size_t d, size_t *work_elems, int *launches);
+int sr_symm_recompose_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_mat, size_t n, size_t d, const uint64_t *d_powers, uint64_t *d_work,
+                          size_t work_elems, void *stream);
+int sr_symm_recompose(sr_ctx *ctx, uint64_t *out, const uint64_t *mat, size_t n, size_t d, const uint64_t *powers);
 /* Cyclotomic::rot (crates/ring/src/traits.rs:54-66): every ring element of the batch (COEFFICIENT form) times X, modulo X^D + 1
  * (stark_prime/mod.rs:87-95, frog_ring/mod.rs:126-134 and the power-of-two rings) or X^D - X^(D/2) + 1 (goldilocks/mod.rs:138-149,
  * babybear/mod.rs:150-161).  The device form is out of place (d_out must not alias d_in); the host form works in place. */

@@ -5,8 +5,9 @@ Layout:
   _lib.py               ctypes loader of libstarkrings_hip.so
   rings.py              host-side mirror of the reference interface (CyclotomicConfig / CRT / ICRT /
                         Flatten at batch granularity) on top of the C ABI
-  wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix around the device codec
+  wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix / SymmetricMatrix around the device codec
   mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values
+  symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
   sharding.py           batch sharding across the GPUs of one node (one process per GPU)
 """
@@ -22,3 +23,4 @@ from .rings import (  # noqa: F401
     RingError,
 )
 from .mle import DenseMultilinearExtension, SparseMultilinearExtension  # noqa: F401
+from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401

@@ -74,6 +74,12 @@ SYMBOLS = {
     "sr_matvec_ntt": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_size_t] * 2),
     "sr_spmv_ntt": (_c.c_int, [_c.c_void_p] * 6 + [_c.c_size_t] * 2),
     "sr_matmul_ntt": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_size_t] * 3),
+    "sr_gram_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_size_t, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
+    "sr_gram_ntt_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_gram_ntt": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t, _c.c_size_t]),
+    "sr_symm_recompose_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_size_t, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
+    "sr_symm_recompose_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_symm_recompose": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t, _c.c_size_t, u64p]),
     "sr_decompose_balanced_batch_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_uint64, _c.c_size_t, _c.c_size_t, _c.c_void_p]),
     "sr_decompose_overflow_count": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_ulonglong), _c.c_void_p]),
     "sr_recompose_batch_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_uint64, _c.c_size_t, _c.c_size_t, _c.c_void_p]),

@@ -31,6 +31,7 @@
 #include "mle.hpp"
 #include "norms.hpp"
 #include "sparse_mle.hpp"
+#include "symmetric.hpp"
 
 namespace {
 
@@ -1697,6 +1698,75 @@ void norm_combine_host(uint64_t *dst, const uint64_t *src, int nl, int ns) {
     }
 }
 
+// ---- symmetric matrices (csrc/symmetric.hpp): nothing allocated, no context scratch --------------------------------------------------
+int dev_gram(sr_ctx *c, const sr::symm::GramPlan &p, uint64_t *out, const uint64_t *a, size_t n, size_t m, uint64_t *work, hipStream_t st) {
+    namespace sy = sr::symm;
+    ProfScope ps(c, st, K_OTHER);
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: e = sy::launch_gram<sr::Goldilocks, sr::Goldilocks>(p, out, a, n, m, c->k, work, st); break;
+        case SR_RING_BABYBEAR_POW2: e = sy::launch_gram<sr::BabyBear, sr::BabyBear>(p, out, a, n, m, c->k, work, st); break;
+        case SR_RING_STARK_POW2:  // sums of products on 28-bit lazy limbs where the context's transforms run on them (stark_lazy.hpp)
+            e = on_stark_lazy(c->path) ? sy::launch_gram<sr::Stark, sr::StarkL>(p, out, a, n, m, c->k, work, st)
+                                       : sy::launch_gram<sr::Stark, sr::Stark>(p, out, a, n, m, c->k, work, st);
+            break;
+        case SR_RING_GOLDILOCKS_24: e = sy::launch_slot_gram<sr::SlotG24>(c->small, p, out, a, n, m, work, st); break;
+        case SR_RING_BABYBEAR_72: e = sy::launch_slot_gram<sr::SlotB72>(c->small, p, out, a, n, m, work, st); break;
+        default: e = sy::launch_slot_gram<sr::SlotFrog>(c->frog, p, out, a, n, m, work, st); break;
+    }
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("gram launch: ") + hipGetErrorString(e));
+}
+int dev_symm_recompose(sr_ctx *c, const sr::symm::RecomposePlan &p, uint64_t *out, const uint64_t *mat, const uint64_t *powers, size_t n, size_t d,
+                       uint64_t *work, hipStream_t st) {
+    namespace sy = sr::symm;
+    ProfScope ps(c, st, K_OTHER);
+    const bool al = aligned16({out, mat, work});
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: e = sy::launch_recompose<sr::Goldilocks, sr::Goldilocks>(p, out, mat, powers, n, d, c->k, work, al, st); break;
+        case SR_RING_BABYBEAR_POW2: e = sy::launch_recompose<sr::BabyBear, sr::BabyBear>(p, out, mat, powers, n, d, c->k, work, al, st); break;
+        case SR_RING_STARK_POW2:
+            e = on_stark_lazy(c->path) ? sy::launch_recompose<sr::Stark, sr::StarkL>(p, out, mat, powers, n, d, c->k, work, al, st)
+                                       : sy::launch_recompose<sr::Stark, sr::Stark>(p, out, mat, powers, n, d, c->k, work, al, st);
+            break;
+        case SR_RING_GOLDILOCKS_24: e = sy::launch_slot_recompose<sr::SlotG24>(c->small, p, out, mat, powers, n, d, work, st); break;
+        case SR_RING_BABYBEAR_72: e = sy::launch_slot_recompose<sr::SlotB72>(c->small, p, out, mat, powers, n, d, work, st); break;
+        default: e = sy::launch_slot_recompose<sr::SlotFrog>(c->frog, p, out, mat, powers, n, d, work, st); break;
+    }
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("symmetric recompose launch: ") + hipGetErrorString(e));
+}
+// the ring and degree checks of the two plan entry points
+int check_plan_ring(int ring, int log2_degree) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    return SR_OK;
+}
+int gram_plan_for(int ring, int k, size_t n, size_t m, sr::symm::GramPlan *p) {
+    if (!sr::symm::gram_plan(ring, k, n, m, p)) return fail(SR_E_INVALID, "gram: n (n + 1) / 2 overflows or the grid exceeds one launch");
+    return SR_OK;
+}
+int recompose_plan_for(int ring, int k, size_t n, size_t d, sr::symm::RecomposePlan *p) {
+    if (d == 0) return fail(SR_E_INVALID, "symm_recompose: d == 0 (the reference divides by the number of powers)");
+    if (!sr::symm::recompose_plan(ring, k, n, d, p)) return fail(SR_E_INVALID, "symm_recompose: a size overflows or the grid exceeds one launch");
+    return SR_OK;
+}
+// the argument checks the two forms of sr_gram_ntt share
+int check_gram(sr_ctx *c, const void *out, const void *a, size_t n, size_t m, sr::symm::GramPlan *p) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (int rc = gram_plan_for(c->ring, c->k, n, m, p)) return rc;
+    if (n && (!out || (m && !a))) return fail(SR_E_INVALID, "gram: null buffer");
+    if (int rc = check_count(c, p->packed)) return rc;
+    if (int rc = check_count(c, n, m)) return rc;
+    return check_count(c, p->work_elems);
+}
+int check_symm_recompose(sr_ctx *c, const void *out, const void *mat, size_t n, size_t d, const void *powers, sr::symm::RecomposePlan *p) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (int rc = recompose_plan_for(c->ring, c->k, n, d, p)) return rc;
+    if (n && (!out || !mat || !powers)) return fail(SR_E_INVALID, "symm_recompose: null buffer");
+    if (int rc = check_count(c, p->packed_in)) return rc;
+    return check_count(c, p->work_elems);
+}
+
 int check_fold(sr_ctx *c, const uint64_t *out, const uint64_t *in, size_t n) {
     if (int rc = check(c, {out, n ? (const void *)in : (const void *)1}, n)) return rc;
     const uintptr_t w = (uintptr_t)c->degree * c->limbs * 8, po = (uintptr_t)out, pi = (uintptr_t)in;
@@ -2606,6 +2676,77 @@ int sr_spmv_ntt(sr_ctx *c, uint64_t *y, const uint64_t *vals, const uint32_t *co
         return dev_spmv(c, (uint64_t *)d[4], (const uint64_t *)d[0], (const uint32_t *)d[1], (const uint64_t *)d[2], (const uint64_t *)d[3],
                         nrows, ncols, c->stream);
     });
+}
+int sr_gram_plan(int ring, int log2_degree, size_t n, size_t m, size_t *work_elems, int *launches) {
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "gram_plan: null result pointer");
+    sr::symm::GramPlan p;
+    if (int rc = gram_plan_for(ring, log2_degree, n, m, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_gram_ntt_dev(sr_ctx *c, uint64_t *out, const uint64_t *a, size_t n, size_t m, uint64_t *work, size_t work_elems, void *stream) {
+    sr::symm::GramPlan p;
+    if (int rc = check_gram(c, out, a, n, m, &p)) return rc;
+    if (n == 0) return SR_OK;
+    if (p.work_elems && !work) return fail(SR_E_INVALID, "gram: null buffer");
+    if (work_elems < p.work_elems)
+        return fail(SR_E_INVALID, "gram: workspace too small (sr_gram_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    if (ranges_overlap(out, p.packed * w, a, n * m * w)) return fail(SR_E_INVALID, "gram: d_out overlaps d_a");
+    if (ranges_overlap(out, p.packed * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "gram: d_out overlaps d_work");
+    if (ranges_overlap(a, n * m * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "gram: d_a overlaps d_work");
+    const Call call(c, stream);
+    return dev_gram(c, p, out, a, n, m, work, call.st);
+}
+int sr_gram_ntt(sr_ctx *c, uint64_t *out, const uint64_t *a, size_t n, size_t m) {
+    sr::symm::GramPlan p;
+    if (int rc = check_gram(c, out, a, n, m, &p)) return rc;
+    if (n == 0) return SR_OK;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    return staged(c, {{a, nullptr, n * m * w}, {nullptr, out, p.packed * w}, {nullptr, nullptr, p.work_elems * w}}, [&](void *const *d) {
+        return dev_gram(c, p, (uint64_t *)d[1], (const uint64_t *)d[0], n, m, (uint64_t *)d[2], c->stream);
+    });
+}
+int sr_symm_recompose_plan(int ring, int log2_degree, size_t n, size_t d, size_t *work_elems, int *launches) {
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "symm_recompose_plan: null result pointer");
+    sr::symm::RecomposePlan p;
+    if (int rc = recompose_plan_for(ring, log2_degree, n, d, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_symm_recompose_dev(sr_ctx *c, uint64_t *out, const uint64_t *mat, size_t n, size_t d, const uint64_t *powers, uint64_t *work,
+                          size_t work_elems, void *stream) {
+    sr::symm::RecomposePlan p;
+    if (int rc = check_symm_recompose(c, out, mat, n, d, powers, &p)) return rc;
+    if (n == 0) return SR_OK;
+    if (!work) return fail(SR_E_INVALID, "symm_recompose: null buffer");
+    if (work_elems < p.work_elems)
+        return fail(SR_E_INVALID, "symm_recompose: workspace too small (sr_symm_recompose_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    if (ranges_overlap(out, p.packed_out * w, mat, p.packed_in * w)) return fail(SR_E_INVALID, "symm_recompose: d_out overlaps d_mat");
+    if (ranges_overlap(out, p.packed_out * w, powers, d * w)) return fail(SR_E_INVALID, "symm_recompose: d_out overlaps d_powers");
+    if (ranges_overlap(out, p.packed_out * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "symm_recompose: d_out overlaps d_work");
+    if (ranges_overlap(mat, p.packed_in * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "symm_recompose: d_mat overlaps d_work");
+    if (ranges_overlap(powers, d * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "symm_recompose: d_powers overlaps d_work");
+    const Call call(c, stream);
+    return dev_symm_recompose(c, p, out, mat, powers, n, d, work, call.st);
+}
+int sr_symm_recompose(sr_ctx *c, uint64_t *out, const uint64_t *mat, size_t n, size_t d, const uint64_t *powers) {
+    sr::symm::RecomposePlan p;
+    if (int rc = check_symm_recompose(c, out, mat, n, d, powers, &p)) return rc;
+    if (n == 0) return SR_OK;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    return staged(c, {{mat, nullptr, p.packed_in * w}, {powers, nullptr, d * w}, {nullptr, out, p.packed_out * w}, {nullptr, nullptr, p.work_elems * w}},
+                  [&](void *const *dv) {
+                      return dev_symm_recompose(c, p, (uint64_t *)dv[2], (const uint64_t *)dv[0], (const uint64_t *)dv[1], n, d, (uint64_t *)dv[3],
+                                                c->stream);
+                  });
 }
 int sr_sum_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n) { return host_fold(c, out, in, n, false); }
 int sr_product_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n) { return host_fold(c, out, in, n, true); }

@@ -87,6 +87,37 @@ def smle_fix_pattern(idx, num_vars, n_fixed):
     return out_idx[:n_out.value].copy(), seg[:n_out.value + 1].copy()
 
 
+def _log2_degree_arg(ring, log2_degree):
+    return int(log2_degree) if ring <= STARK_POW2 else 0
+
+
+def gram_plan(ring, log2_degree, n, m):
+    """sr_gram_plan: (work_elems, launches) of the Gram matrix of an n x m matrix -- host arithmetic, no device, no context."""
+    if isinstance(ring, str):
+        ring = _RING_NAMES[ring]
+    if n < 0 or m < 0:
+        raise RingError("gram: negative count")
+    work, launches = ctypes.c_size_t(), ctypes.c_int()
+    rc = _lib.load().sr_gram_plan(int(ring), _log2_degree_arg(ring, log2_degree), int(n), int(m), ctypes.byref(work), ctypes.byref(launches))
+    if rc != 0:
+        raise RingError("sr_gram_plan failed (%d): %s" % (rc, _lib.last_error()))
+    return work.value, launches.value
+
+
+def symm_recompose_plan(ring, log2_degree, n, d):
+    """sr_symm_recompose_plan: (work_elems, launches) of G^T M G for a packed matrix of size n * d -- host arithmetic only."""
+    if isinstance(ring, str):
+        ring = _RING_NAMES[ring]
+    if n < 0 or d < 0:
+        raise RingError("symm_recompose: negative count")
+    work, launches = ctypes.c_size_t(), ctypes.c_int()
+    rc = _lib.load().sr_symm_recompose_plan(int(ring), _log2_degree_arg(ring, log2_degree), int(n), int(d), ctypes.byref(work),
+                                            ctypes.byref(launches))
+    if rc != 0:
+        raise RingError("sr_symm_recompose_plan failed (%d): %s" % (rc, _lib.last_error()))
+    return work.value, launches.value
+
+
 def _basis_words(basis, decompose):
     """(lo, hi) 64-bit words of a decomposition basis (the reference takes b: u128, balanced_decomposition/mod.rs:62).  Anything
     outside [0, 2^128) is refused instead of being truncated by ctypes.  decompose_balanced_in_place casts `b as i128` (mod.rs:73),
@@ -402,6 +433,27 @@ class CyclotomicRing:
         self._check(self._lib.sr_matmul_ntt(self._ctx, _np_ptr(y), _np_ptr(a) if a.size else _np_ptr(z),
                                             _np_ptr(b) if b.size else _np_ptr(z), n, m, p))
         return y[:n * p * w]
+
+    # -- symmetric matrices (linear_algebra/src/symmetric_matrix.rs; packed: entry (i, j), j <= i, is element i (i + 1) / 2 + j) ----
+    def gram_ntt(self, a, n, m):
+        """Host buffers: sr_gram_ntt -- the packed Gram matrix out(i, j) = sum_t a[i][t] * a[j][t] of a dense n x m matrix."""
+        w = self.words_per_elem
+        if n < 0 or m < 0 or a.size != n * m * w:
+            raise RingError("gram: DifferentLengths")
+        out = np.empty(max(n * (n + 1) // 2 * w, 1), dtype=np.uint64)
+        self._check(self._lib.sr_gram_ntt(self._ctx, _np_ptr(out), _np_ptr(a if a.size else out), n, m))
+        return out[:n * (n + 1) // 2 * w]
+
+    def symm_recompose(self, mat, n, d, powers):
+        """Host buffers: sr_symm_recompose -- recompose_left_right_symmetric_matrix (balanced_decomposition/mod.rs:354-386) of a
+        packed matrix of size n * d with the d ring elements `powers`; returns the packed matrix of size n."""
+        w = self.words_per_elem
+        if n < 0 or d < 0 or powers.size != d * w or mat.size != (n * d) * (n * d + 1) // 2 * w:
+            raise RingError("symm_recompose: DifferentLengths")
+        out = np.empty(max(n * (n + 1) // 2 * w, 1), dtype=np.uint64)
+        self._check(self._lib.sr_symm_recompose(self._ctx, _np_ptr(out), _np_ptr(mat if mat.size else out), n, d,
+                                                _np_ptr(powers if powers.size else out)))
+        return out[:n * (n + 1) // 2 * w]
 
     def rot(self, data):
         """Cyclotomic::rot (traits.rs:54-66) of every element of the batch, in place: coefficients times X modulo the ring."""
@@ -877,6 +929,42 @@ class CyclotomicRing:
             raise RingError("matmul: DifferentLengths")
         self._check(self._lib.sr_matmul_ntt_dev(self._ctx, py, pa, pb, n, m, p, self._stream(stream)))
         return y
+
+    def gram_plan(self, n, m):
+        """sr_gram_plan for this ring: (work_elems, launches)."""
+        return gram_plan(self.ring, self.degree.bit_length() - 1, n, m)
+
+    def symm_recompose_plan(self, n, d):
+        """sr_symm_recompose_plan for this ring: (work_elems, launches)."""
+        return symm_recompose_plan(self.ring, self.degree.bit_length() - 1, n, d)
+
+    def _dev_or_null(self, t):
+        return self._dev(t) if t is not None and t.numel() else (ctypes.c_void_p(0), 0)
+
+    def gram_ntt_dev(self, out, a, n, m, work=None, stream=None):
+        """sr_gram_ntt_dev: out (packed, n (n + 1) / 2 elements) = the Gram matrix of the rows of the dense n x m matrix a.  work: a
+        tensor of at least gram_plan()[0] elements (None where the plan needs none).  Allocates nothing; capturable."""
+        w = self.words_per_elem
+        po, no = self._dev_or_null(out)
+        pa, na = self._dev_or_null(a)
+        pw, nw = self._dev_or_null(work)
+        if n < 0 or m < 0 or na != n * m * w or no != n * (n + 1) // 2 * w:
+            raise RingError("gram: DifferentLengths")
+        self._check(self._lib.sr_gram_ntt_dev(self._ctx, po, pa, n, m, pw, nw // w, self._stream(stream)))
+        return out
+
+    def symm_recompose_dev(self, out, mat, n, d, powers, work, stream=None):
+        """sr_symm_recompose_dev: out (packed, size n) = G^T mat G for the packed matrix mat of size n * d and the d elements
+        `powers`.  work: a tensor of at least symm_recompose_plan()[0] elements.  Allocates nothing; capturable."""
+        w = self.words_per_elem
+        po, no = self._dev_or_null(out)
+        pm, nm = self._dev_or_null(mat)
+        pp, npw = self._dev_or_null(powers)
+        pw, nw = self._dev_or_null(work)
+        if n < 0 or d < 0 or npw != d * w or nm != (n * d) * (n * d + 1) // 2 * w or no != n * (n + 1) // 2 * w:
+            raise RingError("symm_recompose: DifferentLengths")
+        self._check(self._lib.sr_symm_recompose_dev(self._ctx, po, pm, n, d, pp, pw, nw // w, self._stream(stream)))
+        return out
 
     def rot_dev(self, out, a, stream=None):
         po, n = self._dev(out)

@@ -7,6 +7,7 @@ module adds what the reference's containers add around them:
   Matrix<R>         its Vec<Vec<R>>                                        crates/linear_algebra/src/matrix.rs:111-145
   SparseMatrix<R>   nrows u64, ncols u64, then Vec<Vec<(R, usize)>>        crates/linear_algebra/src/sparse_matrix.rs:158-200
                     (a pair is its members in order; usize travels as u64)
+  SymmetricMatrix<R>  its Vec<Vec<R>> (row i has i + 1 entries)           crates/linear_algebra/src/symmetric_matrix.rs:116-154
 
 Ring elements are numpy uint64 words in the reference's memory image (rings.py); wire data is numpy uint8.  Errors the
 reference reports as SerializationError (short input, a coefficient >= p) raise RingError.
@@ -80,6 +81,44 @@ def deserialize_matrix(ring, wire):
         pos += n * eb
     flat = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.uint8)
     return ring.deserialize(flat), nrows, ncols
+
+
+def serialize_symmetric(ring, mat):
+    """SymmetricMatrix<R> (symmetric_matrix.rs:116-132 hands its Vec<Vec<R>> to the derived framing): a u64 row count, then per row
+    a u64 length and the row's elements.  mat: a SymmetricMatrixNTT on host words, or the rows themselves (one flat uint64 array of
+    whole elements per row, of any length: what deserialize_symmetric returns)."""
+    rows = mat.rows() if hasattr(mat, "rows") else list(mat)
+    parts = [_u64(len(rows))]
+    for row in rows:
+        row = np.ascontiguousarray(row, dtype=np.uint64)
+        n = ring._batch_of(row.size)
+        parts.append(_u64(n))
+        if n:
+            parts.append(ring.serialize(row))
+    return np.concatenate(parts)
+
+
+def deserialize_symmetric(ring, wire):
+    """-> the rows, one flat uint64 array per row.  The reference's deserialize is `Vec::<Vec<F>>::deserialize(..).map(Self)`
+    (symmetric_matrix.rs:142-154): it does NOT run the row-length assertion of From<Vec<Vec<F>>>, so a row i whose length is not
+    i + 1 is accepted there and is accepted here; SymmetricMatrixNTT.from_rows(ring, rows) applies the assertion."""
+    wire = np.ascontiguousarray(wire, dtype=np.uint8)
+    nrows, pos = _read_u64(wire, 0)
+    eb = elem_bytes(ring)
+    chunks, lens = [], []
+    for _ in range(nrows):
+        n, pos = _read_u64(wire, pos)
+        if pos + n * eb > wire.size:
+            raise RingError("deserialize: unexpected end of input")
+        chunks.append(wire[pos:pos + n * eb])
+        lens.append(n)
+        pos += n * eb
+    flat = ring.deserialize(np.concatenate(chunks)) if sum(lens) else np.zeros(0, dtype=np.uint64)
+    w, rows, j = ring.words_per_elem, [], 0
+    for n in lens:
+        rows.append(flat[j * w:(j + n) * w])
+        j += n
+    return rows
 
 
 def serialize_sparse(ring, nrows, ncols, rows):
