@@ -27,7 +27,8 @@
 //     MulAssign<&R> (Matrix, Sparse)     matrix.rs:207-211,            operator*=(const RqNTTVec &one_element): every entry times one ring element
 //                                        sparse_matrix.rs:303-307
 //   DenseMultilinearExtension<RqNTT>     crates/poly mle/dense.rs    class DenseMultilinearExtension: fix_variables, fixed_variables,
-//     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations
+//     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations;
+//                                                                      round_evals / product_sum: a sum-check round's message (sr_mle_round_evals)
 //   SparseMultilinearExtension<RqNTT>    crates/poly mle/sparse.rs   class SparseMultilinearExtension: from_slice, from_matrix, fix_variables,
 //     precompute_eq                      sparse.rs:381-394             fixed_variables, evaluate, to_evaluations; eq_table(point); device
 //                                                                      pointers: CyclotomicConfig::eq_table_dev / smle_plan / smle_fix_variables_dev
@@ -433,6 +434,16 @@ public:
         all.resize(cfg_.words_per_elem() << nv_, 0);
         return RqNTTVec(cfg_, std::move(all));
     }
+    // The prover's message of one sum-check round over the product of `tables` (1 .. 4 MLEs of one ring and one num_vars >= 1; the
+    // same MLE may appear twice): the d + 1 elements p(t) = sum_b prod_j f_j(t, b), t = 0 .. d, the variable being the one
+    // fix_variables (SR_MLE_LEADING) or fix_last_variables (SR_MLE_TRAILING) fixes next.  Throws where sr_mle_round_evals refuses.
+    static RqNTTVec round_evals(const std::vector<const DenseMultilinearExtension *> &tables, int order = SR_MLE_LEADING) {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("round_evals: unknown order");
+        return round(tables, order);
+    }
+    // sum_b prod_j f_j[b] over the hypercube: the claimed sum of a sum-check (the `sum` of random_mle_list,
+    // polynomials/multilinear_polynomial.rs:19-49), one ring element
+    static RqNTTVec product_sum(const std::vector<const DenseMultilinearExtension *> &tables) { return round(tables, SR_MLE_ROUND_SUM); }
     // sr_mle_plan of a fold of n_fixed of this table's variables: {workspace elements, kernel launches} of the device form
     std::pair<size_t, int> plan(size_t n_fixed, int order, int log2_degree) const {
         size_t work = 0;
@@ -442,6 +453,21 @@ public:
     }
 
 private:
+    static RqNTTVec round(const std::vector<const DenseMultilinearExtension *> &tables, int mode) {
+        if (tables.empty() || tables.size() > SR_MLE_ROUND_MAX_TABLES) throw std::length_error("round_evals: 1 .. 4 tables");
+        const DenseMultilinearExtension &first = *tables[0];
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        for (const DenseMultilinearExtension *t : tables) {
+            if (t->cfg_.raw() != first.cfg_.raw() || t->nv_ != first.nv_) throw std::length_error("round_evals: the tables differ in ring or num_vars");
+            ptrs.push_back(t->w_.empty() ? nullptr : t->w_.data());
+            sizes.push_back(t->len());
+        }
+        std::vector<uint64_t> out(first.cfg_.words_per_elem() * (mode == SR_MLE_ROUND_SUM ? 1 : tables.size() + 1));
+        CyclotomicConfig::check(sr_mle_round_evals(first.cfg_.raw(), out.data(), ptrs.data(), sizes.data(), (int)tables.size(), first.nv_, mode),
+                                "sr_mle_round_evals");
+        return RqNTTVec(first.cfg_, std::move(out));
+    }
     DenseMultilinearExtension fold(const RqNTTVec &point, int order) const {
         if (point.len() > nv_) throw std::length_error("too many partial points");  // dense.rs:172-175
         std::vector<uint64_t> out(cfg_.words_per_elem() << (nv_ - point.len()));

@@ -243,6 +243,43 @@ int sr_mle_fix_variables_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_eva
                              size_t n_fixed, int order, uint64_t *d_work, size_t work_elems, void *stream);
 int sr_mle_fix_variables(sr_ctx *ctx, uint64_t *out, const uint64_t *evals, size_t n_evals, size_t num_vars, const uint64_t *point,
                          size_t n_fixed, int order);
+/* The prover's message of a sum-check round over a product of dense MLEs (csrc/sumcheck.hpp): one pass that reads every table once.
+ * d_tables: a HOST array of n_tables (1 .. SR_MLE_ROUND_MAX_TABLES) device pointers, n_evals: a HOST array; both are consumed at call
+ * time (they reach the kernels by value: a captured graph holds no host pointer).  Table j is an MLE in num_vars variables in CRT/NTT
+ * form of which the first n_evals[j] <= 2^num_vars elements are stored; the rest are zero and are NEVER read (the truncated-storage
+ * contract of sr_mle_fix_variables).  `*` is the slot product of the ring, t the ring constant R::from(t), half = 2^(num_vars - 1),
+ * d = n_tables:
+ *   SR_MLE_LEADING    d_out[t] = sum_{b < half} prod_j ( f_j[2b] + t * (f_j[2b+1] - f_j[2b]) ) for t = 0 .. d: d + 1 ring elements; the
+ *                     summand is fix_variables with the point [R::from(t)] (mle/dense.rs:171-199)
+ *   SR_MLE_TRAILING   the same with the pair (f_j[b], f_j[b + half]) (fix_last_variables, multilinear_polynomial.rs:251-286)
+ *   SR_MLE_ROUND_SUM  d_out[0] = sum_{b < 2^num_vars} prod_j f_j[b]: one element, the claimed sum (the `sum` of random_mle_list,
+ *                     multilinear_polynomial.rs:19-49); num_vars = 0 is allowed here, the two round modes need num_vars >= 1
+ * Canonical in, canonical out.  All sums are exact modular integers on canonical values, so the result does not depend on the grid,
+ * on how the plan splits the pairs, or on scheduling.  A pair or index beyond the stored part of ANY table contributes zero and is
+ * skipped without a load; if any n_evals[j] == 0 every output is zero(): one launch that loads no table.
+ * The call allocates nothing and touches no context scratch: partial results live in d_work (work_elems ring elements, at least what
+ * sr_mle_round_plan returns) and every workspace word that is read was written by the same call, so it can be captured into a HIP graph
+ * on any stream without a warm-up, as one linear chain of launches.  Tables are never written and may alias each other (f * f).
+ * SR_E_INVALID: a null pointer, n_tables outside 1 .. 4, an unknown mode, num_vars >= 48, num_vars == 0 in a round mode,
+ * n_evals[j] > 2^num_vars, work_elems below the plan's, d_out or d_work overlapping a table or each other.
+ * sr_mle_round_plan: pure host arithmetic, no device, no context; it depends on the shape only.  *launches >= 1; *work_elems == 0
+ * whenever one launch suffices, and never more than SR_MLE_ROUND_MAX_GROUPS * (n_tables + 1) elements: a shape whose degree alone
+ * does not fill the device takes its pairs in up to SR_MLE_ROUND_MAX_GROUPS records -- a workgroup of 256 lanes each, whatever the
+ * degree (the lane-groups of a workgroup meet in LDS), so 1024 records are four workgroups on each of 256 compute units -- and each
+ * record leaves d + 1 partial elements that a last launch adds.  Some shapes take the d + 1 points in several launches (registers),
+ * reading the tables once per launch: Stark at d = 4 (2 + 2 + 1 points), goldilocks24 at d = 3 (2 + 2) and d = 4 (3 + 2), babybear72
+ * at d = 3 (2 + 2) and d = 4 (2 + 2 + 1), frog16 at d = 2 (2 + 1), d = 3 (2 + 2) and d = 4 (one point per launch); such a plan always
+ * uses the workspace.  The one-limb fields read every table exactly once for every d <= 4.
+ * The host-pointer form stages like sr_mle_fix_variables: the whole tables go to context-owned device temporaries, the message is
+ * computed there and the d + 1 elements come back; chunked staging is not implemented. */
+#define SR_MLE_ROUND_MAX_TABLES 4
+#define SR_MLE_ROUND_MAX_GROUPS 1024
+enum { SR_MLE_ROUND_SUM = 2 }; /* beside SR_MLE_LEADING = 0, SR_MLE_TRAILING = 1 */
+int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches);
+int sr_mle_round_evals_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *const *d_tables, const size_t *n_evals, int n_tables,
+                           size_t num_vars, int mode, uint64_t *d_work, size_t work_elems, void *stream);
+int sr_mle_round_evals(sr_ctx *ctx, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars,
+                       int mode);
 /* Sparse multilinear extensions: the arithmetic of crates/poly's SparseMultilinearExtension (mle/sparse.rs) on device-resident
  * values.  Elements are ring elements in CRT / NTT form in the usual flat layout, canonical in and canonical out, for every ring id.
  *

@@ -6,7 +6,8 @@ Layout:
   rings.py              host-side mirror of the reference interface (CyclotomicConfig / CRT / ICRT /
                         Flatten at batch granularity) on top of the C ABI
   wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix / SymmetricMatrix around the device codec
-  mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values
+  mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values,
+                        with the round message of a sum-check over a product of dense MLEs
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
   sharding.py           batch sharding across the GPUs of one node (one process per GPU)
@@ -18,6 +19,7 @@ from .rings import (  # noqa: F401
     GOLDILOCKS_POW2,
     STARK_POW2,
     MLE_LEADING,
+    MLE_ROUND_SUM,
     MLE_TRAILING,
     CyclotomicRing,
     RingError,

@@ -32,6 +32,7 @@
 #include "norms.hpp"
 #include "sparse_mle.hpp"
 #include "symmetric.hpp"
+#include "sumcheck.hpp"
 
 namespace {
 
@@ -1585,6 +1586,53 @@ int check_mle(sr_ctx *c, const void *out, const void *evals, size_t n_evals, siz
     return check_count(c, p.work_elems);
 }
 
+// ---- sum-check round messages (csrc/sumcheck.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch -----------
+int dev_mle_round(sr_ctx *c, const sr::sumcheck::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
+                  int n_tables, size_t num_vars, uint64_t *work, hipStream_t st) {
+    namespace sc = sr::sumcheck;
+    ProfScope ps(c, st, K_POINTWISE);
+    sc::Tables tb{};
+    uintptr_t bits = (uintptr_t)out | (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int j = 0; j < n_tables; j++) {
+        tb.p[j] = tables[j];
+        tb.n[j] = n_evals[j];
+        bits |= (uintptr_t)tables[j];
+    }
+    const bool al = (bits & 15u) == 0;
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: e = sc::launch<sr::Goldilocks>(p, mode, out, tb, n_tables, num_vars, n_evals, c->k, al, work, st); break;
+        case SR_RING_BABYBEAR_POW2: e = sc::launch<sr::BabyBear>(p, mode, out, tb, n_tables, num_vars, n_evals, c->k, al, work, st); break;
+        case SR_RING_STARK_POW2: e = sc::launch<sr::Stark>(p, mode, out, tb, n_tables, num_vars, n_evals, c->k, al, work, st); break;
+        case SR_RING_GOLDILOCKS_24: e = sc::launch_slot<sr::SlotG24>(c->small, p, mode, out, tb, n_tables, num_vars, n_evals, work, st); break;
+        case SR_RING_BABYBEAR_72: e = sc::launch_slot<sr::SlotB72>(c->small, p, mode, out, tb, n_tables, num_vars, n_evals, work, st); break;
+        default: e = sc::launch_slot<sr::SlotFrog>(c->frog, p, mode, out, tb, n_tables, num_vars, n_evals, work, st); break;
+    }
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("mle round launch: ") + hipGetErrorString(e));
+}
+// the shape checks sr_mle_round_plan and the two forms of sr_mle_round_evals share
+int round_plan_for(int ring, int k, size_t num_vars, int n_tables, int mode, sr::sumcheck::Plan *p) {
+    if (n_tables < 1 || n_tables > SR_MLE_ROUND_MAX_TABLES) return fail(SR_E_INVALID, "mle_round: n_tables must be 1 .. 4");
+    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && mode != SR_MLE_ROUND_SUM) return fail(SR_E_INVALID, "mle_round: unknown mode");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "mle_round: num_vars must be below 48");
+    if (num_vars == 0 && mode != SR_MLE_ROUND_SUM) return fail(SR_E_INVALID, "mle_round: a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
+    if (!sr::sumcheck::plan(ring, k, num_vars, n_tables, mode, p)) return fail(SR_E_INVALID, "mle_round: no plan for these arguments");
+    return SR_OK;
+}
+// the argument checks the two forms of sr_mle_round_evals share
+int check_mle_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, int mode,
+                    sr::sumcheck::Plan *p) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!out || !tables || !n_evals) return fail(SR_E_INVALID, "mle_round: null pointer");
+    if (int rc = round_plan_for(c->ring, c->k, num_vars, n_tables, mode, p)) return rc;
+    for (int j = 0; j < n_tables; j++) {
+        if (n_evals[j] > (size_t)1 << num_vars) return fail(SR_E_INVALID, "mle_round: n_evals exceeds 2^num_vars");
+        if (n_evals[j] && !tables[j]) return fail(SR_E_INVALID, "mle_round: null pointer (a table)");
+        if (int rc = check_count(c, n_evals[j])) return rc;
+    }
+    return SR_OK;
+}
+
 // ---- sparse multilinear extensions (csrc/sparse_mle.hpp): nothing allocated, no context scratch ----------------------------------
 sr::smle::One smle_one(const sr_ctx *c) {
     sr::smle::One one;
@@ -2318,6 +2366,59 @@ int sr_mle_fix_variables(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t
                       return dev_mle_fix(c, (uint64_t *)d[2], (const uint64_t *)d[0], n_evals, num_vars, (const uint64_t *)d[1], n_fixed, order,
                                          (uint64_t *)d[3], c->stream);
                   });
+}
+int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "mle_round_plan: null result pointer");
+    sr::sumcheck::Plan p;
+    if (int rc = round_plan_for(ring, log2_degree, num_vars, n_tables, mode, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_mle_round_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars,
+                           int mode, uint64_t *work, size_t work_elems, void *stream) {
+    sr::sumcheck::Plan p;
+    if (int rc = check_mle_round(c, out, tables, n_evals, n_tables, num_vars, mode, &p)) return rc;
+    if (p.work_elems && !work) return fail(SR_E_INVALID, "mle_round: null pointer (d_work)");
+    if (work_elems < p.work_elems)
+        return fail(SR_E_INVALID, "mle_round: workspace too small (sr_mle_round_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    for (int j = 0; j < n_tables; j++) {
+        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round: d_out overlaps a table");
+        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round: d_work overlaps a table");
+    }
+    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "mle_round: d_out overlaps d_work");
+    const Call call(c, stream);
+    return dev_mle_round(c, p, mode, out, tables, n_evals, n_tables, num_vars, work, call.st);
+}
+int sr_mle_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, int mode) {
+    sr::sumcheck::Plan p;
+    if (int rc = check_mle_round(c, out, tables, n_evals, n_tables, num_vars, mode, &p)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    // HOST_0: the tables one behind the other, each on a 16-byte boundary; HOST_1: the result; HOST_2: the workspace
+    size_t off[SR_MLE_ROUND_MAX_TABLES], total = 0;
+    for (int j = 0; j < n_tables; j++) {
+        off[j] = total;
+        total += (n_evals[j] * w + 15) & ~(size_t)15;
+    }
+    if (int rc = grow(c, HOST_0, total)) return rc;
+    if (int rc = grow(c, HOST_1, p.np_total * w)) return rc;
+    if (int rc = grow(c, HOST_2, p.work_elems * w)) return rc;
+    const uint64_t *dt[SR_MLE_ROUND_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) {
+        dt[j] = (const uint64_t *)((char *)c->buf[HOST_0] + off[j]);
+        if (n_evals[j]) HIP_TRY(hipMemcpyAsync((void *)dt[j], tables[j], n_evals[j] * w, hipMemcpyHostToDevice, c->stream));
+    }
+    if (int rc = dev_mle_round(c, p, mode, (uint64_t *)c->buf[HOST_1], dt, n_evals, n_tables, num_vars, (uint64_t *)c->buf[HOST_2], c->stream)) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], p.np_total * w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SR_OK;
 }
 int sr_eq_table_dev(sr_ctx *c, uint64_t *out, const uint64_t *point, size_t n_vars, void *stream) {
     if (int rc = check(c, {out, n_vars ? (const void *)point : (const void *)1})) return rc;

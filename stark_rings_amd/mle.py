@@ -8,7 +8,7 @@ hold fewer than 2^num_vars elements: the missing tail is zero and is never read.
 """
 import numpy as np
 
-from .rings import MLE_LEADING, MLE_TRAILING, RingError, smle_fix_pattern
+from .rings import MLE_LEADING, MLE_ROUND_SUM, MLE_TRAILING, RingError, smle_fix_pattern
 
 
 class DenseMultilinearExtension:
@@ -97,6 +97,41 @@ class DenseMultilinearExtension:
             raise RingError("add_assign_scaled: the operands differ in num_vars or stored length (see to_evaluations)")
         self.ring.mul_elem_add_dev(self.evaluations, other.evaluations, r, stream)
         return self
+
+    @staticmethod
+    def _round(tables, mode, stream):
+        import torch
+
+        if not 1 <= len(tables) <= 4:
+            raise RingError("round_evals: 1 .. 4 tables")
+        first = tables[0]
+        ring, nv = first.ring, first.num_vars
+        if any(t.ring is not ring or t.num_vars != nv for t in tables):
+            raise RingError("round_evals: the tables must share one ring and one num_vars")
+        n_out = 1 if mode == MLE_ROUND_SUM else len(tables) + 1
+        out = torch.empty(n_out * ring.words_per_elem, dtype=first.evaluations.dtype, device=first.evaluations.device)
+        # a workspace of its own per call (a few records of d + 1 elements): the folds of tables[0] may run on another stream
+        need = ring.mle_round_plan(nv, len(tables), mode)[0]
+        work = torch.empty(need * ring.words_per_elem, dtype=first.evaluations.dtype, device=first.evaluations.device) if need else None
+        if work is not None and stream is not None:
+            work.record_stream(stream)  # not handed out again before the launches on `stream` are done
+        ring.mle_round_evals_dev(out, [t.evaluations for t in tables], nv, mode, work, stream)
+        return out
+
+    @staticmethod
+    def round_evals(tables, order=MLE_LEADING, stream=None):
+        """The prover's message of one sum-check round over the product of `tables` (a list of 1 .. 4 MLEs of one ring and one
+        num_vars >= 1; an MLE may appear twice): the d + 1 elements p(t) = sum_b prod_j f_j(t, b), t = 0 .. d, the variable being
+        the one fix_variables (MLE_LEADING) or fix_last_variables (MLE_TRAILING) fixes next."""
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("round_evals: unknown order")
+        return DenseMultilinearExtension._round(tables, order, stream)
+
+    @staticmethod
+    def product_sum(tables, stream=None):
+        """sum_b prod_j f_j[b] over the hypercube as one ring element: the claimed sum of a sum-check (the `sum` of
+        random_mle_list, polynomials/multilinear_polynomial.rs:19-49)."""
+        return DenseMultilinearExtension._round(tables, MLE_ROUND_SUM, stream)
 
     def to_evaluations(self):
         """dense.rs `to_evaluations`: all 2^num_vars elements as one tensor, the zero tail written out."""

@@ -25,6 +25,7 @@ from . import _lib
 GOLDILOCKS_POW2, BABYBEAR_POW2, STARK_POW2, GOLDILOCKS_24, BABYBEAR_72, FROG_16 = 0, 1, 2, 3, 4, 5
 PROF_TAGS = ("fwd_cols", "rows", "inv_cols", "pointwise", "other")
 MLE_LEADING, MLE_TRAILING = 0, 1   # SR_MLE_LEADING / SR_MLE_TRAILING: which end of the index a fold starts from
+MLE_ROUND_SUM = 2                  # SR_MLE_ROUND_SUM: the plain sum of products of sr_mle_round_evals
 NORM_LINF, NORM_L2SQ = 1, 2        # SR_NORM_LINF / SR_NORM_L2SQ: the mask of sr_norm_batch*
 
 _RING_NAMES = {
@@ -778,6 +779,50 @@ class CyclotomicRing:
             nw //= self.words_per_elem
         self._check(self._lib.sr_mle_fix_variables_dev(self._ctx, po, pe, n_evals, int(num_vars), pp, n_fixed, int(order), pw, nw,
                                                        self._stream(stream)))
+        return out
+
+    def mle_round_plan(self, num_vars, n_tables, mode=MLE_LEADING):
+        """sr_mle_round_plan: (work_elems, launches) of a sum-check round message over n_tables tables -- host arithmetic only."""
+        work = ctypes.c_size_t()
+        launches = ctypes.c_int()
+        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
+        self._check(self._lib.sr_mle_round_plan(self.ring, k, int(num_vars), int(n_tables), int(mode), ctypes.byref(work), ctypes.byref(launches)))
+        return work.value, launches.value
+
+    def mle_round_evals_dev(self, out, tables, num_vars, mode=MLE_LEADING, work=None, stream=None):
+        """sr_mle_round_evals_dev: the prover's message of a sum-check round over the product of `tables` (1 .. 4 CUDA tensors, each
+        n_evals <= 2^num_vars elements, the rest zero; a table may appear twice).  MLE_LEADING / MLE_TRAILING: out[t] = sum over the
+        pairs of prod_j (lo_j + t (hi_j - lo_j)) for t = 0 .. len(tables), the pair being (f[2b], f[2b+1]) or (f[b], f[b + half]);
+        MLE_ROUND_SUM: out = sum_b prod_j f_j[b], one element.  work: a tensor of at least mle_round_plan()[0] elements (None only
+        where the plan needs none).  Allocates nothing."""
+        po, no = self._dev(out)
+        n = len(tables)
+        if no != self.words_per_elem * (1 if mode == MLE_ROUND_SUM else n + 1):
+            raise RingError("mle_round_evals: out must hold len(tables) + 1 elements (one for MLE_ROUND_SUM)")
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.numel())
+            ptrs[j] = self._dev(t)[0] if t.numel() else None
+        if work is None:
+            pw, nw = ctypes.c_void_p(0), 0
+        else:
+            pw, nw = self._dev(work)
+            nw //= self.words_per_elem
+        self._check(self._lib.sr_mle_round_evals_dev(self._ctx, po, ptrs, sizes, n, int(num_vars), int(mode), pw, nw, self._stream(stream)))
+        return out
+
+    def mle_round_evals(self, tables, num_vars, mode=MLE_LEADING):
+        """Host buffers: sr_mle_round_evals (see mle_round_evals_dev); returns the len(tables) + 1 elements (one for MLE_ROUND_SUM)."""
+        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+        n = len(tables)
+        out = np.empty(self.words_per_elem * (1 if mode == MLE_ROUND_SUM else n + 1), dtype=np.uint64)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.size)
+            ptrs[j] = t.ctypes.data if t.size else None
+        self._check(self._lib.sr_mle_round_evals(self._ctx, _np_ptr(out), ptrs, sizes, n, int(num_vars), int(mode)))
         return out
 
     def eq_table_dev(self, out, point, stream=None):
