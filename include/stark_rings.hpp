@@ -444,6 +444,41 @@ public:
     // sum_b prod_j f_j[b] over the hypercube: the claimed sum of a sum-check (the `sum` of random_mle_list,
     // polynomials/multilinear_polynomial.rs:19-49), one ring element
     static RqNTTVec product_sum(const std::vector<const DenseMultilinearExtension *> &tables) { return round(tables, SR_MLE_ROUND_SUM); }
+    // One prover round in one pass over the tables (sr_mle_round_fold_evals): every MLE of `tables` (1 .. 4 of one ring and one
+    // num_vars >= 2) with its next variable fixed at the ring element r, and the message of the round that follows over those folded
+    // tables: {message, folded tables} -- what fixed_variables / fix_last_variables of every table followed by round_evals returns.
+    static std::pair<RqNTTVec, std::vector<DenseMultilinearExtension>> fold_round_evals(const std::vector<const DenseMultilinearExtension *> &tables,
+                                                                                        const RqNTTVec &r, int order = SR_MLE_LEADING) {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("fold_round_evals: unknown order");
+        if (tables.empty() || tables.size() > SR_MLE_ROUND_MAX_TABLES) throw std::length_error("fold_round_evals: 1 .. 4 tables");
+        if (r.len() != 1) throw std::length_error("fold_round_evals: r is not one ring element");
+        const DenseMultilinearExtension &first = *tables[0];
+        if (first.nv_ < 2) throw std::length_error("fold_round_evals: num_vars >= 2");
+        const size_t w = first.cfg_.words_per_elem();
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        std::vector<std::vector<uint64_t>> folded;
+        std::vector<uint64_t *> optrs;
+        for (const DenseMultilinearExtension *t : tables) {
+            if (t->cfg_.raw() != first.cfg_.raw() || t->nv_ != first.nv_)
+                throw std::length_error("fold_round_evals: the tables differ in ring or num_vars");
+            ptrs.push_back(t->w_.empty() ? nullptr : t->w_.data());
+            sizes.push_back(t->len());
+            folded.emplace_back(t->w_.size());  // never shorter than the folded table
+        }
+        for (auto &f : folded) optrs.push_back(f.empty() ? nullptr : f.data());
+        std::vector<size_t> n_out(tables.size());
+        std::vector<uint64_t> out(w * (tables.size() + 1));
+        CyclotomicConfig::check(sr_mle_round_fold_evals(first.cfg_.raw(), out.data(), optrs.data(), n_out.data(), ptrs.data(), sizes.data(),
+                                                        (int)tables.size(), first.nv_, r.words().data(), order),
+                                "sr_mle_round_fold_evals");
+        std::vector<DenseMultilinearExtension> g;
+        for (size_t j = 0; j < tables.size(); j++) {
+            folded[j].resize(n_out[j] * w);
+            g.emplace_back(first.cfg_, first.nv_ - 1, std::move(folded[j]));
+        }
+        return {RqNTTVec(first.cfg_, std::move(out)), std::move(g)};
+    }
     // sr_mle_plan of a fold of n_fixed of this table's variables: {workspace elements, kernel launches} of the device form
     std::pair<size_t, int> plan(size_t n_fixed, int order, int log2_degree) const {
         size_t work = 0;

@@ -280,6 +280,41 @@ int sr_mle_round_evals_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *const *
                            size_t num_vars, int mode, uint64_t *d_work, size_t work_elems, void *stream);
 int sr_mle_round_evals(sr_ctx *ctx, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars,
                        int mode);
+/* A sum-check round in one pass (csrc/sumcheck_fold.hpp): fold every table at the challenge of the round that has just ended and
+ * compute the message of the round that follows while the folded neighbours are still in registers -- 1.5 n elements of traffic per
+ * table of n instead of the 2 n of sr_mle_fix_variables_dev followed by sr_mle_round_evals_dev on the folded tables.  order: SR_MLE_LEADING or
+ * SR_MLE_TRAILING; d = n_tables in 1 .. SR_MLE_ROUND_MAX_TABLES; 2 <= num_vars < 48.
+ *   d_out_tables[j]  g_j = f_j with one variable fixed at the ring element *d_r (one element in CRT/NTT form): exactly what
+ *                    sr_mle_fix_variables_dev(.., n_fixed = 1, order) computes, in truncated storage: n_evals_out[j] elements are written
+ *                    -- (n_evals[j] + 1) / 2 in leading order, min(n_evals[j], 2^(num_vars-1)) in trailing order -- and nothing beyond
+ *                    them is touched.  Every table is folded to ITS OWN length.
+ *   d_out[t]         t = 0 .. d: the message of the next round over g_0 .. g_{d-1} in num_vars - 1 variables, bit-identical to
+ *                    sr_mle_round_evals_dev on the folded tables with the same order.
+ * d_tables, d_out_tables and n_evals are HOST arrays consumed at call time; n_evals_out is a HOST array filled at call time by host
+ * arithmetic.  Canonical in, canonical out; all arithmetic is exact, so both outputs are bit-identical to the two calls made one after
+ * the other, whatever the grid or the split.  If any n_evals[j] == 0 the message is zero (no table is loaded for the product) and the
+ * other tables are still folded and written; if every table is empty one launch zeroes d_out.
+ * Aliasing: outputs may not overlap inputs, each other, d_r, d_out or d_work, with one exception: in SR_MLE_TRAILING
+ * d_out_tables[j] == d_tables[j] folds table j in place (a lane reads its four elements before it writes two of the same positions).
+ * Input tables may alias each other (f * f), but such a table cannot be folded in place: it would be folded twice.
+ * The call allocates nothing and touches no context scratch; every workspace word that is read was written by the same call, and the
+ * launches are one linear chain on one stream, so it can be captured without a warm-up.
+ * SR_E_INVALID: a null pointer, n_tables outside 1 .. 4, num_vars < 2 or >= 48, an unknown order, n_evals[j] > 2^num_vars, work_elems
+ * below the plan's, any forbidden overlap.
+ * sr_mle_round_fold_plan: pure host arithmetic, no device, no context; the records are those of sr_mle_round_plan at num_vars - 1.
+ * *work_elems == 0 exactly when *launches == 1; *work_elems <= SR_MLE_ROUND_MAX_GROUPS * (n_tables + 1).  The fused launch takes all
+ * d + 1 points for Goldilocks and BabyBear at every d <= 4 (at most two launches).  The other families keep the fused kernel within
+ * 256 registers by taking the first points there -- Stark 2, 3, 3, 2 for d = 1 .. 4, goldilocks24 2, 3, 2, 2, babybear72 2, 2, 1, 1, frog16
+ * 2, 1, 1, 1 -- and the remaining ones from the round kernels of sr_mle_round_evals_dev over the FOLDED tables (half the size), into the
+ * same records; such a plan always uses the workspace.
+ * The host-pointer form stages like sr_mle_round_evals: whole tables go to context-owned device temporaries, the folded tables and the
+ * message come back; chunked staging is not implemented. */
+int sr_mle_round_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int order, size_t *work_elems, int *launches);
+int sr_mle_round_fold_evals_dev(sr_ctx *ctx, uint64_t *d_out, uint64_t *const *d_out_tables, size_t *n_evals_out,
+                                const uint64_t *const *d_tables, const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *d_r,
+                                int order, uint64_t *d_work, size_t work_elems, void *stream);
+int sr_mle_round_fold_evals(sr_ctx *ctx, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
+                            const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, int order);
 /* Sparse multilinear extensions: the arithmetic of crates/poly's SparseMultilinearExtension (mle/sparse.rs) on device-resident
  * values.  Elements are ring elements in CRT / NTT form in the usual flat layout, canonical in and canonical out, for every ring id.
  *

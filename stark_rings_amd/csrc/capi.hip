@@ -33,6 +33,7 @@
 #include "sparse_mle.hpp"
 #include "symmetric.hpp"
 #include "sumcheck.hpp"
+#include "sumcheck_fold.hpp"
 
 namespace {
 
@@ -1633,6 +1634,61 @@ int check_mle_round(sr_ctx *c, const void *out, const uint64_t *const *tables, c
     return SR_OK;
 }
 
+// ---- fold at the challenge and the next round's message in one pass (csrc/sumcheck_fold.hpp): every launch under K_POINTWISE ---------
+int dev_mle_round_fold(sr_ctx *c, const sr::sumcheck_fold::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
+                       const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, uint64_t *work,
+                       hipStream_t st) {
+    namespace sf = sr::sumcheck_fold;
+    ProfScope ps(c, st, K_POINTWISE);
+    sr::sumcheck::Tables tb{};
+    sf::Folded fo{};
+    uintptr_t bits = (uintptr_t)out | (uintptr_t)r | (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int j = 0; j < n_tables; j++) {
+        tb.p[j] = tables[j];
+        tb.n[j] = n_evals[j];
+        fo.p[j] = out_tables[j];
+        bits |= (uintptr_t)tables[j] | (uintptr_t)out_tables[j];
+    }
+    const bool al = (bits & 15u) == 0;
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: e = sf::launch<sr::Goldilocks>(p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, al, work, st); break;
+        case SR_RING_BABYBEAR_POW2: e = sf::launch<sr::BabyBear>(p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, al, work, st); break;
+        case SR_RING_STARK_POW2: e = sf::launch<sr::Stark>(p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, al, work, st); break;
+        case SR_RING_GOLDILOCKS_24: e = sf::launch_slot<sr::SlotG24>(c->small, p, order, out, tb, fo, r, n_tables, num_vars, n_out, work, st); break;
+        case SR_RING_BABYBEAR_72: e = sf::launch_slot<sr::SlotB72>(c->small, p, order, out, tb, fo, r, n_tables, num_vars, n_out, work, st); break;
+        default: e = sf::launch_slot<sr::SlotFrog>(c->frog, p, order, out, tb, fo, r, n_tables, num_vars, n_out, work, st); break;
+    }
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("mle round fold launch: ") + hipGetErrorString(e));
+}
+// the shape checks sr_mle_round_fold_plan and the two forms of sr_mle_round_fold_evals share
+int round_fold_plan_for(int ring, int k, size_t num_vars, int n_tables, int order, sr::sumcheck_fold::Plan *p) {
+    if (n_tables < 1 || n_tables > SR_MLE_ROUND_MAX_TABLES) return fail(SR_E_INVALID, "mle_round_fold: n_tables must be 1 .. 4");
+    if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) return fail(SR_E_INVALID, "mle_round_fold: unknown order");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "mle_round_fold: num_vars must be below 48");
+    if (num_vars < 2) return fail(SR_E_INVALID, "mle_round_fold: num_vars >= 2 (the folded tables need a variable for the next round)");
+    if (!sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, order, p)) return fail(SR_E_INVALID, "mle_round_fold: no plan for these arguments");
+    return SR_OK;
+}
+// elements the fold of a table of n stored elements writes
+size_t round_fold_n_out(size_t n, size_t num_vars, int order) {
+    const size_t half = (size_t)1 << (num_vars - 1);
+    return order == SR_MLE_LEADING ? (n + 1) / 2 : (n < half ? n : half);
+}
+// the argument checks the two forms of sr_mle_round_fold_evals share
+int check_mle_round_fold(sr_ctx *c, const void *out, uint64_t *const *out_tables, const size_t *n_out, const uint64_t *const *tables,
+                         const size_t *n_evals, int n_tables, size_t num_vars, const void *r, int order, sr::sumcheck_fold::Plan *p) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!out || !out_tables || !n_out || !tables || !n_evals || !r) return fail(SR_E_INVALID, "mle_round_fold: null pointer");
+    if (int rc = round_fold_plan_for(c->ring, c->k, num_vars, n_tables, order, p)) return rc;
+    for (int j = 0; j < n_tables; j++) {
+        if (n_evals[j] > (size_t)1 << num_vars) return fail(SR_E_INVALID, "mle_round_fold: n_evals exceeds 2^num_vars");
+        if (n_evals[j] && (!tables[j] || !out_tables[j])) return fail(SR_E_INVALID, "mle_round_fold: null pointer (a table)");
+        if (int rc = check_count(c, n_evals[j])) return rc;
+    }
+    return SR_OK;
+}
+
 // ---- sparse multilinear extensions (csrc/sparse_mle.hpp): nothing allocated, no context scratch ----------------------------------
 sr::smle::One smle_one(const sr_ctx *c) {
     sr::smle::One one;
@@ -2417,6 +2473,95 @@ int sr_mle_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, 
         return rc;
     }
     HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], p.np_total * w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SR_OK;
+}
+int sr_mle_round_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int order, size_t *work_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "mle_round_fold_plan: null result pointer");
+    sr::sumcheck_fold::Plan p;
+    if (int rc = round_fold_plan_for(ring, log2_degree, num_vars, n_tables, order, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_mle_round_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
+                                const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, int order, uint64_t *work,
+                                size_t work_elems, void *stream) {
+    sr::sumcheck_fold::Plan p;
+    if (int rc = check_mle_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, order, &p)) return rc;
+    if (p.work_elems && !work) return fail(SR_E_INVALID, "mle_round_fold: null pointer (d_work)");
+    if (work_elems < p.work_elems)
+        return fail(SR_E_INVALID,
+                    "mle_round_fold: workspace too small (sr_mle_round_fold_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    size_t n_out[SR_MLE_ROUND_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
+    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps d_work");
+    if (ranges_overlap(out, p.np_total * w, r, w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps d_r");
+    if (ranges_overlap(work, p.work_elems * w, r, w)) return fail(SR_E_INVALID, "mle_round_fold: d_work overlaps d_r");
+    for (int j = 0; j < n_tables; j++) {
+        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps a table");
+        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_work overlaps a table");
+        if (ranges_overlap(r, w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_r overlaps a table");
+        if (ranges_overlap(out, p.np_total * w, out_tables[j], n_out[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps a folded table");
+        if (ranges_overlap(work, p.work_elems * w, out_tables[j], n_out[j] * w))
+            return fail(SR_E_INVALID, "mle_round_fold: d_work overlaps a folded table");
+        if (ranges_overlap(r, w, out_tables[j], n_out[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_r overlaps a folded table");
+        for (int i = 0; i < j; i++)
+            if (ranges_overlap(out_tables[i], n_out[i] * w, out_tables[j], n_out[j] * w))
+                return fail(SR_E_INVALID, "mle_round_fold: two folded tables overlap");
+        for (int i = 0; i < n_tables; i++) {
+            if (!ranges_overlap(out_tables[j], n_out[j] * w, tables[i], n_evals[i] * w)) continue;
+            // in place: the table's own output only, trailing order only, and no other input may be that table (it would be folded twice)
+            if (order != SR_MLE_TRAILING || out_tables[j] != tables[j])
+                return fail(SR_E_INVALID,
+                            "mle_round_fold: a folded table overlaps an input table (only a trailing-order fold may run in place, with "
+                            "d_out_tables[j] == d_tables[j])");
+            if (i != j) return fail(SR_E_INVALID, "mle_round_fold: an input table that appears twice cannot be folded in place");
+        }
+    }
+    const Call call(c, stream);
+    return dev_mle_round_fold(c, p, order, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, work, call.st);
+}
+int sr_mle_round_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
+                            const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, int order) {
+    sr::sumcheck_fold::Plan p;
+    if (int rc = check_mle_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, order, &p)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    // HOST_0: the tables one behind the other, each on a 16-byte boundary; HOST_1: the message, then r; HOST_2: the workspace; HOST_3: the
+    // folded tables, laid out like the tables
+    size_t off[SR_MLE_ROUND_MAX_TABLES], ooff[SR_MLE_ROUND_MAX_TABLES], total = 0, ototal = 0;
+    for (int j = 0; j < n_tables; j++) {
+        off[j] = total;
+        total += (n_evals[j] * w + 15) & ~(size_t)15;
+        ooff[j] = ototal;
+        ototal += (round_fold_n_out(n_evals[j], num_vars, order) * w + 15) & ~(size_t)15;
+    }
+    const size_t r_off = (p.np_total * w + 15) & ~(size_t)15;
+    if (int rc = grow(c, HOST_0, total)) return rc;
+    if (int rc = grow(c, HOST_1, r_off + w)) return rc;
+    if (int rc = grow(c, HOST_2, p.work_elems * w)) return rc;
+    if (int rc = grow(c, HOST_3, ototal)) return rc;
+    const uint64_t *dt[SR_MLE_ROUND_MAX_TABLES];
+    uint64_t *dout[SR_MLE_ROUND_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) {
+        dt[j] = (const uint64_t *)((char *)c->buf[HOST_0] + off[j]);
+        dout[j] = (uint64_t *)((char *)c->buf[HOST_3] + ooff[j]);
+        if (n_evals[j]) HIP_TRY(hipMemcpyAsync((void *)dt[j], tables[j], n_evals[j] * w, hipMemcpyHostToDevice, c->stream));
+    }
+    uint64_t *dr = (uint64_t *)((char *)c->buf[HOST_1] + r_off);
+    HIP_TRY(hipMemcpyAsync(dr, r, w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_mle_round_fold(c, p, order, (uint64_t *)c->buf[HOST_1], dout, n_evals_out, dt, n_evals, n_tables, num_vars, dr,
+                                    (uint64_t *)c->buf[HOST_2], c->stream)) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], p.np_total * w, hipMemcpyDeviceToHost, c->stream));
+    for (int j = 0; j < n_tables; j++)
+        if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SR_OK;
 }

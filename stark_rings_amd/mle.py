@@ -133,6 +133,36 @@ class DenseMultilinearExtension:
         random_mle_list, polynomials/multilinear_polynomial.rs:19-49)."""
         return DenseMultilinearExtension._round(tables, MLE_ROUND_SUM, stream)
 
+    @staticmethod
+    def fold_round_evals(tables, r, order=MLE_LEADING, stream=None):
+        """One prover round in one pass over the tables: every MLE of `tables` (1 .. 4 of one ring and one num_vars >= 2, each
+        appearing once) with the variable fix_variables (MLE_LEADING) or fix_last_variables (MLE_TRAILING) fixes next set to the ring
+        element `r`, and the message of the round that follows over those folded tables.  Returns (message, folded tables): what
+        fixed_variables / fix_last_variables of every table followed by round_evals returns, bit for bit, in one pass over the tables."""
+        import torch
+
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("fold_round_evals: unknown order")
+        if not 1 <= len(tables) <= 4:
+            raise RingError("fold_round_evals: 1 .. 4 tables")
+        first = tables[0]
+        ring, nv = first.ring, first.num_vars
+        if any(t.ring is not ring or t.num_vars != nv for t in tables):
+            raise RingError("fold_round_evals: the tables must share one ring and one num_vars")
+        if nv < 2:
+            raise RingError("fold_round_evals: num_vars >= 2 (the last round folds with fix_variables)")
+        w, ev = ring.words_per_elem, first.evaluations
+        out = torch.empty((len(tables) + 1) * w, dtype=ev.dtype, device=ev.device)
+        sizes = [(len(t) + 1) // 2 if order == MLE_LEADING else min(len(t), 1 << (nv - 1)) for t in tables]
+        folded = [torch.empty(n * w, dtype=ev.dtype, device=ev.device) for n in sizes]
+        need = ring.mle_round_fold_plan(nv, len(tables), order)[0]
+        work = torch.empty(need * w, dtype=ev.dtype, device=ev.device) if need else None
+        if stream is not None:
+            for t in folded + ([work] if work is not None else []):
+                t.record_stream(stream)
+        ring.mle_round_fold_evals_dev(out, folded, [t.evaluations for t in tables], nv, r, order, work, stream)
+        return out, [DenseMultilinearExtension(ring, nv - 1, f) for f in folded]
+
     def to_evaluations(self):
         """dense.rs `to_evaluations`: all 2^num_vars elements as one tensor, the zero tail written out."""
         import torch
