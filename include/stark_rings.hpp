@@ -816,6 +816,15 @@ public:
                                 "Matrix * Matrix");
         return MatrixNTT(cfg_, nrows_, m.ncols_, std::move(y));
     }
+    // Transpose for Matrix<R> (ops.rs:36-44).  The reference transposes vals but copies nrows and ncols UNSWAPPED; the result here
+    // reports the shape of its data, ncols x nrows.
+    MatrixNTT transpose() const {
+        std::vector<uint64_t> y(w_.size());
+        std::vector<uint64_t> dummy(1);
+        CyclotomicConfig::check(sr_transpose(cfg_.raw(), y.empty() ? dummy.data() : y.data(), w_.empty() ? dummy.data() : w_.data(), nrows_, ncols_),
+                                "Matrix::transpose");
+        return MatrixNTT(cfg_, ncols_, nrows_, std::move(y));
+    }
     MatrixNTT &operator*=(const RqNTTVec &r) {  // MulAssign<&R> for Matrix<R> (matrix.rs:207-211): every entry *= r
         if (r.len() != 1) throw std::length_error("Matrix *= &R: the multiplier is not one ring element");
         std::vector<uint64_t> dummy(1);
@@ -865,6 +874,58 @@ public:
         if (!r) throw std::length_error("DifferentLengths");
         return std::move(*r);
     }
+    // the rows as the constructor takes them: coeffs()[r] = the stored (element, column) pairs of row r
+    std::vector<std::vector<Entry>> coeffs() const {
+        const size_t w = cfg_.words_per_elem();
+        std::vector<std::vector<Entry>> out(nrows_);
+        for (size_t r = 0; r < nrows_; r++)
+            for (uint64_t t = row_ptr_[r]; t < row_ptr_[r + 1]; t++)
+                out[r].emplace_back(std::vector<uint64_t>(vals_.begin() + t * w, vals_.begin() + (t + 1) * w), (size_t)cols_[t]);
+        return out;
+    }
+    size_t nnz() const { return cols_.size(); }
+    // Transpose for SparseMatrix<R> (ops.rs:46-62): row c of the result lists (value, original row) in ascending original row; the
+    // rows of *this need not be sorted.  Throws where the reference panics (a column >= ncols).
+    SparseMatrixNTT transpose() const {
+        SparseMatrixNTT t(cfg_, ncols_, nrows_);
+        t.vals_.resize(vals_.size());
+        t.cols_.resize(cols_.size());
+        std::vector<uint64_t> dummy(1);
+        std::vector<uint32_t> dummy32(1);
+        CyclotomicConfig::check(sr_sparse_transpose(cfg_.raw(), t.vals_.empty() ? dummy.data() : t.vals_.data(),
+                                                    t.cols_.empty() ? dummy32.data() : t.cols_.data(), t.row_ptr_.data(),
+                                                    vals_.empty() ? dummy.data() : vals_.data(), cols_.empty() ? dummy32.data() : cols_.data(),
+                                                    row_ptr_.data(), nrows_, ncols_),
+                                "SparseMatrix::transpose");
+        return t;
+    }
+    // sparse_matrix.rs:219-275: None when ncols != m.nrows.  An entry is stored iff one of its products is non-zero (a stored entry may
+    // itself be zero).  The reference's merge-join needs rows that ascend strictly in both operands; anything else throws.
+    std::optional<SparseMatrixNTT> checked_mul_mat(const SparseMatrixNTT &m) const {
+        if (ncols_ != m.nrows_) return std::nullopt;
+        std::vector<uint64_t> dummy(1);
+        std::vector<uint32_t> dummy32(1);
+        const uint32_t *ac = cols_.empty() ? dummy32.data() : cols_.data(), *bc = m.cols_.empty() ? dummy32.data() : m.cols_.data();
+        size_t n_out = 0, n_pairs = 0, kept = 0;
+        CyclotomicConfig::check(sr_spgemm_pattern(ac, row_ptr_.data(), nrows_, ncols_, bc, m.row_ptr_.data(), m.ncols_, nullptr, nullptr, nullptr,
+                                                  nullptr, nullptr, &n_out, &n_pairs),
+                                "SparseMatrix * SparseMatrix");
+        SparseMatrixNTT y(cfg_, nrows_, m.ncols_);
+        y.vals_.resize(n_out * cfg_.words_per_elem());  // room for the structural entries; the dead ones are dropped by the call
+        y.cols_.resize(n_out);
+        CyclotomicConfig::check(sr_spgemm_ntt(cfg_.raw(), y.vals_.empty() ? dummy.data() : y.vals_.data(), y.cols_.empty() ? dummy32.data() : y.cols_.data(),
+                                              y.row_ptr_.data(), &kept, vals_.empty() ? dummy.data() : vals_.data(), ac, row_ptr_.data(), nrows_, ncols_,
+                                              m.vals_.empty() ? dummy.data() : m.vals_.data(), bc, m.row_ptr_.data(), m.ncols_),
+                                "SparseMatrix * SparseMatrix");
+        y.vals_.resize(kept * cfg_.words_per_elem());
+        y.cols_.resize(kept);
+        return y;
+    }
+    SparseMatrixNTT try_mul_mat(const SparseMatrixNTT &m) const {  // Mul<&SparseMatrix> (sparse_matrix.rs:293-301): DifferentLengths
+        auto r = checked_mul_mat(m);
+        if (!r) throw std::length_error("DifferentLengths");
+        return std::move(*r);
+    }
     SparseMatrixNTT &operator*=(const RqNTTVec &r) {  // MulAssign<&R> for SparseMatrix<R> (sparse_matrix.rs:303-307): every stored entry *= r
         if (r.len() != 1) throw std::length_error("SparseMatrix *= &R: the multiplier is not one ring element");
         std::vector<uint64_t> dummy(1);
@@ -874,6 +935,7 @@ public:
     }
 
 private:
+    SparseMatrixNTT(CyclotomicConfig cfg, size_t nrows, size_t ncols) : cfg_(std::move(cfg)), nrows_(nrows), ncols_(ncols), row_ptr_(nrows + 1, 0) {}
     CyclotomicConfig cfg_;
     size_t nrows_, ncols_;
     std::vector<uint64_t> vals_, row_ptr_;

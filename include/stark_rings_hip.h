@@ -447,6 +447,54 @@ int sr_symm_recompose_plan(int ring, int log2_degree, size_t n, size_t d, size_t
 int sr_symm_recompose_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_mat, size_t n, size_t d, const uint64_t *d_powers, uint64_t *d_work,
                           size_t work_elems, void *stream);
 int sr_symm_recompose(sr_ctx *ctx, uint64_t *out, const uint64_t *mat, size_t n, size_t d, const uint64_t *powers);
+/* Sparse matrices (csrc/sparse_matrix.hpp): SparseMatrix::transpose and Matrix::transpose (crates/linear_algebra/src/ops.rs:9-62) and
+ * SparseMatrix::checked_mul_mat (sparse_matrix.rs:219-281, the Mul<&SparseMatrix> of :293-301), over ring elements in CRT/NTT form, every
+ * ring id, canonical in and canonical out.  A sparse matrix is the CSR triple of sr_spmv_ntt_dev: uint32_t columns, uint64_t row pointers
+ * (row_ptr[0] == 0); positions into a value array are uint32_t, so an operand with 2^32 or more stored entries is SR_E_INVALID.  The index
+ * work is host arithmetic without device or context; the device moves and multiplies whole ring elements by position.
+ * sr_sparse_transpose_pattern: a stable counting sort by column.  Row c of the transpose lists the original rows (t_cols) of the entries in
+ * column c, ascending, whatever the order inside the input rows; t_vals[t] = vals[perm[t]].  SR_E_INVALID: a column >= ncols (the reference
+ * panics there), a non-monotone row_ptr or row_ptr[0] != 0, a null pointer, more than 2^32 - 1 rows.
+ * sr_spgemm_pattern: the STRUCTURAL product of A (n x m) and B (m x p): one entry per (i, j) whose index lists intersect, rows ascending in
+ * j, and per entry e the intersecting positions pair_a[t] into a_vals and pair_b[t] into b_vals for pair_ptr[e] <= t < pair_ptr[e + 1],
+ * ascending in k.  With the five output arrays null it only counts (*n_out, *n_pairs), so that a caller can size them; with buffers it
+ * fills them.  Both operands must have strictly ascending rows and indices in range (hconcat, from_dense, identity and rand produce such
+ * rows; the reference's merge-join means nothing otherwise): SR_E_INVALID.  Cost: nnz_a + nnz_b + n_pairs + n + m + p steps.
+ * sr_spgemm_ntt_dev: d_out_vals[e] = sum of d_a_vals[pair_a[t]] * d_b_vals[pair_b[t]] over the pairs of entry e, `*` the slot product;
+ * d_live[e] = 1 iff some product of the entry is a non-zero ring element (NTT-form elements have zero divisors, so the reference's stored
+ * pattern depends on the values), else 0.  The number of entries with d_live == 0 is added to a context counter that sr_spgemm_dead_count
+ * reads and clears (synchronises the stream).  With a dead count of 0 the structural pattern is the reference's result; otherwise the
+ * caller drops the dead entries.  A live entry may hold zero (a b + (-a) b).  A position >= nnz_a / nnz_b is skipped.  n_out == 0 writes
+ * nothing.  SR_E_INVALID: a null pointer, d_out_vals or d_live overlapping each other, an input or the workspace, a size overflow, a grid
+ * past one launch's limit.
+ * sr_spgemm_plan: host arithmetic on (n_out, n_pairs) only.  Pair lists are never cut into spans: work_elems is always 0 (d_work may be
+ * null) and launches is 2 -- the numeric kernel and the count of the dead entries -- or 0 for n_out == 0.
+ * sr_gather_batch_dev: d_out[t] = d_in[d_perm[t]] on whole ring elements, out of place; d_perm[t] >= n_in leaves element t unwritten and
+ * is counted with the out-of-range columns of spmv (sr_spmv_bad_index_count).  sr_transpose_dev: dense d_out[j][i] = d_in[i][j] for a
+ * row-major nrows x ncols d_in, out of place.  (Matrix::transpose copies nrows and ncols unswapped, ops.rs:36-44; the data it returns is the
+ * ncols x nrows matrix written here.)
+ * The _dev calls allocate nothing, touch no context scratch, write every flag word they later read and can be captured into a HIP graph
+ * without a warm-up.  The host-pointer forms stage whole operands in context-owned temporaries; sr_spgemm_ntt runs pattern, numeric phase
+ * and compaction and returns exactly the reference's SparseMatrix (out_vals and out_cols need room for the structural n_out entries,
+ * *nnz_out is the number kept). */
+int sr_sparse_transpose_pattern(const uint32_t *cols, const uint64_t *row_ptr, size_t nrows, size_t ncols, uint64_t *t_row_ptr /* ncols + 1 */,
+                                uint32_t *t_cols /* nnz */, uint32_t *perm /* nnz */);
+int sr_spgemm_pattern(const uint32_t *a_cols, const uint64_t *a_row_ptr, size_t n, size_t m, const uint32_t *b_cols, const uint64_t *b_row_ptr,
+                      size_t p, uint64_t *out_row_ptr /* n + 1 */, uint32_t *out_cols, uint64_t *pair_ptr /* n_out + 1 */, uint32_t *pair_a,
+                      uint32_t *pair_b, size_t *n_out, size_t *n_pairs);
+int sr_spgemm_plan(int ring, int log2_degree, size_t n_out, size_t n_pairs, size_t *work_elems, int *launches);
+int sr_gather_batch_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, const uint32_t *d_perm, size_t n_out, size_t n_in, void *stream);
+int sr_transpose_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_in, size_t nrows, size_t ncols, void *stream);
+int sr_spgemm_ntt_dev(sr_ctx *ctx, uint64_t *d_out_vals, uint32_t *d_live, const uint64_t *d_a_vals, size_t nnz_a, const uint64_t *d_b_vals,
+                      size_t nnz_b, const uint64_t *d_pair_ptr, const uint32_t *d_pair_a, const uint32_t *d_pair_b, size_t n_out, size_t n_pairs,
+                      uint64_t *d_work, size_t work_elems, void *stream);
+int sr_spgemm_dead_count(sr_ctx *ctx, unsigned long long *out, void *stream);
+int sr_sparse_transpose(sr_ctx *ctx, uint64_t *t_vals, uint32_t *t_cols, uint64_t *t_row_ptr, const uint64_t *vals, const uint32_t *cols,
+                        const uint64_t *row_ptr, size_t nrows, size_t ncols);
+int sr_transpose(sr_ctx *ctx, uint64_t *out, const uint64_t *in, size_t nrows, size_t ncols);
+int sr_spgemm_ntt(sr_ctx *ctx, uint64_t *out_vals, uint32_t *out_cols, uint64_t *out_row_ptr, size_t *nnz_out, const uint64_t *a_vals,
+                  const uint32_t *a_cols, const uint64_t *a_row_ptr, size_t n, size_t m, const uint64_t *b_vals, const uint32_t *b_cols,
+                  const uint64_t *b_row_ptr, size_t p);
 /* Cyclotomic::rot (crates/ring/src/traits.rs:54-66): every ring element of the batch (COEFFICIENT form) times X, modulo X^D + 1
  * (stark_prime/mod.rs:87-95, frog_ring/mod.rs:126-134 and the power-of-two rings) or X^D - X^(D/2) + 1 (goldilocks/mod.rs:138-149,
  * babybear/mod.rs:150-161).  The device form is out of place (d_out must not alias d_in); the host form works in place. */

@@ -9,6 +9,7 @@ Layout:
   mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values,
                         with the round message of a sum-check over a product of dense MLEs
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
+  sparse.py             SparseMatrix of crates/linear_algebra with device-resident values: transpose, sparse x sparse product
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
   sharding.py           batch sharding across the GPUs of one node (one process per GPU)
 """
@@ -26,3 +27,4 @@ from .rings import (  # noqa: F401
 )
 from .mle import DenseMultilinearExtension, SparseMultilinearExtension  # noqa: F401
 from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401
+from .sparse import SparseMatrixNTT  # noqa: F401

@@ -89,6 +89,18 @@ SYMBOLS = {
     "sr_symm_recompose_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_size_t, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
     "sr_symm_recompose_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sr_symm_recompose": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t, _c.c_size_t, u64p]),
+    "sr_sparse_transpose_pattern": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "sr_spgemm_pattern": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 5 +
+                          [_c.POINTER(_c.c_size_t)] * 2),
+    "sr_spgemm_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_size_t, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
+    "sr_gather_batch_dev": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_size_t, _c.c_void_p]),
+    "sr_transpose_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_size_t, _c.c_void_p]),
+    "sr_spgemm_ntt_dev": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 3 + [_c.c_size_t] * 2 +
+                          [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_spgemm_dead_count": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_ulonglong), _c.c_void_p]),
+    "sr_sparse_transpose": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_size_t] * 2),
+    "sr_transpose": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t, _c.c_size_t]),
+    "sr_spgemm_ntt": (_c.c_int, [_c.c_void_p] * 4 + [_c.POINTER(_c.c_size_t)] + [_c.c_void_p] * 3 + [_c.c_size_t] * 2 + [_c.c_void_p] * 3 + [_c.c_size_t]),
     "sr_decompose_balanced_batch_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_uint64, _c.c_size_t, _c.c_size_t, _c.c_void_p]),
     "sr_decompose_overflow_count": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_ulonglong), _c.c_void_p]),
     "sr_recompose_batch_dev": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_uint64, _c.c_size_t, _c.c_size_t, _c.c_void_p]),

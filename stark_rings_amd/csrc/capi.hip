@@ -32,6 +32,7 @@
 #include "norms.hpp"
 #include "sparse_mle.hpp"
 #include "symmetric.hpp"
+#include "sparse_matrix.hpp"
 #include "sumcheck.hpp"
 #include "sumcheck_fold.hpp"
 
@@ -1871,6 +1872,48 @@ int check_symm_recompose(sr_ctx *c, const void *out, const void *mat, size_t n, 
     return check_count(c, p->work_elems);
 }
 
+// ---- sparse matrices (csrc/sparse_matrix.hpp): nothing allocated, no context scratch --------------------------------------------------
+// out[t] = in[perm[t]] (perm != null) or the dense transpose of the nrows x ncols matrix `in`; n_out output elements
+int dev_move(sr_ctx *c, uint64_t *out, const uint64_t *in, const uint32_t *perm, size_t n_out, size_t n_in, size_t nrows, size_t ncols,
+             hipStream_t st) {
+    int v;
+    size_t units, blocks;
+    if (!sr::spm::move_grid(n_out, (size_t)c->degree * c->limbs, aligned16({out, in}), &v, &units, &blocks))
+        return fail(SR_E_INVALID, "gather / transpose: the grid exceeds one launch");
+    if (n_out == 0) return SR_OK;
+    ProfScope ps(c, st, K_OTHER);
+    const hipError_t e = sr::spm::launch_move(out, in, perm, n_in, nrows, ncols, v, units, blocks, c->d_counter + 1, st);
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("gather / transpose launch: ") + hipGetErrorString(e));
+}
+int dev_spgemm(sr_ctx *c, const sr::spm::SpgemmArgs &g, hipStream_t st) {
+    namespace sp = sr::spm;
+    ProfScope ps(c, st, K_OTHER);
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: e = sp::launch_spgemm<sr::Goldilocks>(g, c->k, st); break;
+        case SR_RING_BABYBEAR_POW2: e = sp::launch_spgemm<sr::BabyBear>(g, c->k, st); break;
+        case SR_RING_STARK_POW2:  // sums of products on 28-bit lazy limbs where the context's transforms run on them (stark_lazy.hpp)
+            e = on_stark_lazy(c->path) ? sp::launch_spgemm<sr::StarkL>(g, c->k, st) : sp::launch_spgemm<sr::Stark>(g, c->k, st);
+            break;
+        case SR_RING_GOLDILOCKS_24: e = sp::launch_slot_spgemm<sr::SlotG24>(c->small, g, st); break;
+        case SR_RING_BABYBEAR_72: e = sp::launch_slot_spgemm<sr::SlotB72>(c->small, g, st); break;
+        default: e = sp::launch_slot_spgemm<sr::SlotFrog>(c->frog, g, st); break;
+    }
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("spgemm launch: ") + hipGetErrorString(e));
+}
+// the checks the two forms of the sparse product share: the grid of n_out entries, the element counts
+int check_spgemm(sr_ctx *c, size_t nnz_a, size_t nnz_b, size_t n_out, size_t n_pairs) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    size_t work;
+    int launches;
+    if (!sr::spm::spgemm_plan(c->ring, c->k, n_out, n_pairs, &work, &launches)) return fail(SR_E_INVALID, "spgemm: the grid exceeds one launch");
+    if (nnz_a > 0xFFFFFFFFull || nnz_b > 0xFFFFFFFFull) return fail(SR_E_INVALID, "spgemm: 2^32 or more stored entries (positions are 32-bit)");
+    if (n_pairs > ((size_t)1 << 60)) return fail(SR_E_INVALID, "spgemm: pair count too large");
+    if (int rc = check_count(c, nnz_a)) return rc;
+    if (int rc = check_count(c, nnz_b)) return rc;
+    return check_count(c, n_out);
+}
+
 int check_fold(sr_ctx *c, const uint64_t *out, const uint64_t *in, size_t n) {
     if (int rc = check(c, {out, n ? (const void *)in : (const void *)1}, n)) return rc;
     const uintptr_t w = (uintptr_t)c->degree * c->limbs * 8, po = (uintptr_t)out, pi = (uintptr_t)in;
@@ -2213,11 +2256,11 @@ int sr_ctx_create_ex(int ring, int log2_degree, int device, const sr_plan *plan,
     };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(SR_E_HIP, "hipStreamCreate failed"));
     if (hipStreamCreateWithFlags(&c->out_stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(SR_E_HIP, "hipStreamCreate failed"));
-    // four words: [0] scratch counter of count_noncanonical, [1] out-of-range column indices seen by spmv, [2] coefficients
-    // that needed more digits than padding_size in a decomposition, [3] wire coefficients >= p / misaligned wire offsets
-    // ([1]..[3] sticky until read)
-    if (hipMalloc(&c->d_counter, 4 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_ALLOC, "hipMalloc counter failed"));
-    if (hipMemset(c->d_counter, 0, 4 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_HIP, "hipMemset counter failed"));
+    // five words: [0] scratch counter of count_noncanonical, [1] out-of-range column indices seen by spmv and out-of-range positions
+    // seen by the gather, [2] coefficients that needed more digits than padding_size in a decomposition, [3] wire coefficients >= p /
+    // misaligned wire offsets, [4] structural entries of a sparse product none of whose products was non-zero ([1]..[4] sticky until read)
+    if (hipMalloc(&c->d_counter, 5 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_ALLOC, "hipMalloc counter failed"));
+    if (hipMemset(c->d_counter, 0, 5 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_HIP, "hipMemset counter failed"));
     if (is_pow2_ring(ring)) {
         const int k = log2_degree;
         c->k = k;
@@ -2993,6 +3036,168 @@ int sr_symm_recompose(sr_ctx *c, uint64_t *out, const uint64_t *mat, size_t n, s
                       return dev_symm_recompose(c, p, (uint64_t *)dv[2], (const uint64_t *)dv[0], (const uint64_t *)dv[1], n, d, (uint64_t *)dv[3],
                                                 c->stream);
                   });
+}
+// ---- sparse matrices: transpose and sparse x sparse product (csrc/sparse_matrix.hpp) ---------------------------------------------------
+int sr_sparse_transpose_pattern(const uint32_t *cols, const uint64_t *row_ptr, size_t nrows, size_t ncols, uint64_t *t_row_ptr, uint32_t *t_cols,
+                                uint32_t *perm) {
+    if (const char *e = sr::spm::transpose_pattern(cols, row_ptr, nrows, ncols, t_row_ptr, t_cols, perm))
+        return fail(SR_E_INVALID, std::string("sparse_transpose_pattern: ") + e);
+    return SR_OK;
+}
+int sr_spgemm_pattern(const uint32_t *a_cols, const uint64_t *a_row_ptr, size_t n, size_t m, const uint32_t *b_cols, const uint64_t *b_row_ptr,
+                      size_t p, uint64_t *out_row_ptr, uint32_t *out_cols, uint64_t *pair_ptr, uint32_t *pair_a, uint32_t *pair_b, size_t *n_out,
+                      size_t *n_pairs) {
+    const bool fill = out_row_ptr || out_cols || pair_ptr || pair_a || pair_b;
+    try {
+        if (const char *e = sr::spm::spgemm_pattern(a_cols, a_row_ptr, n, m, b_cols, b_row_ptr, p, fill, out_row_ptr, out_cols, pair_ptr, pair_a,
+                                                    pair_b, n_out, n_pairs))
+            return fail(SR_E_INVALID, std::string("spgemm_pattern: ") + e);
+    } catch (const std::exception &) {
+        return fail(SR_E_ALLOC, "spgemm_pattern: out of host memory");
+    }
+    return SR_OK;
+}
+int sr_spgemm_plan(int ring, int log2_degree, size_t n_out, size_t n_pairs, size_t *work_elems, int *launches) {
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "spgemm_plan: null result pointer");
+    if (!sr::spm::spgemm_plan(ring, is_pow2_ring(ring) ? log2_degree : 0, n_out, n_pairs, work_elems, launches))
+        return fail(SR_E_INVALID, "spgemm: the grid exceeds one launch");
+    return SR_OK;
+}
+int sr_gather_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, const uint32_t *perm, size_t n_out, size_t n_in, void *stream) {
+    if (int rc = check(c, {}, n_out)) return rc;
+    if (int rc = check_count(c, n_in)) return rc;
+    if (n_out == 0) return SR_OK;
+    if (!out || !perm || (n_in && !in)) return fail(SR_E_INVALID, "gather: null buffer");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    if (ranges_overlap(out, n_out * w, in, n_in * w)) return fail(SR_E_INVALID, "gather: d_out overlaps d_in");
+    if (ranges_overlap(out, n_out * w, perm, n_out * 4)) return fail(SR_E_INVALID, "gather: d_out overlaps d_perm");
+    const Call call(c, stream);
+    return dev_move(c, out, in, perm, n_out, n_in, 0, 0, call.st);
+}
+int sr_transpose_dev(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t nrows, size_t ncols, void *stream) {
+    if (int rc = check(c, {}, nrows, ncols)) return rc;
+    if (nrows == 0 || ncols == 0) return SR_OK;
+    if (!out || !in) return fail(SR_E_INVALID, "transpose: null buffer");
+    const size_t bytes = nrows * ncols * c->degree * c->limbs * 8;
+    if (ranges_overlap(out, bytes, in, bytes)) return fail(SR_E_INVALID, "transpose: d_out overlaps d_in");
+    const Call call(c, stream);
+    return dev_move(c, out, in, nullptr, nrows * ncols, nrows * ncols, nrows, ncols, call.st);
+}
+int sr_spgemm_ntt_dev(sr_ctx *c, uint64_t *out, uint32_t *live, const uint64_t *a, size_t nnz_a, const uint64_t *b, size_t nnz_b,
+                      const uint64_t *pair_ptr, const uint32_t *pair_a, const uint32_t *pair_b, size_t n_out, size_t n_pairs, uint64_t *work,
+                      size_t work_elems, void *stream) {
+    if (int rc = check_spgemm(c, nnz_a, nnz_b, n_out, n_pairs)) return rc;
+    (void)work_elems;  // sr_spgemm_plan asks for none
+    if (n_out == 0) return SR_OK;
+    if (!out || !live || !pair_ptr || (n_pairs && (!pair_a || !pair_b)) || (nnz_a && !a) || (nnz_b && !b)) return fail(SR_E_INVALID, "spgemm: null buffer");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const struct {
+        const void *p;
+        size_t bytes;
+        const char *name;
+    } in[] = {{a, nnz_a * w, "d_a_vals"},       {b, nnz_b * w, "d_b_vals"},       {pair_ptr, (n_out + 1) * 8, "d_pair_ptr"},
+              {pair_a, n_pairs * 4, "d_pair_a"}, {pair_b, n_pairs * 4, "d_pair_b"}, {work, work_elems * w, "d_work"}};
+    for (const auto &r : in) {
+        if (ranges_overlap(out, n_out * w, r.p, r.bytes)) return fail(SR_E_INVALID, std::string("spgemm: d_out_vals overlaps ") + r.name);
+        if (ranges_overlap(live, n_out * 4, r.p, r.bytes)) return fail(SR_E_INVALID, std::string("spgemm: d_live overlaps ") + r.name);
+    }
+    if (ranges_overlap(out, n_out * w, live, n_out * 4)) return fail(SR_E_INVALID, "spgemm: d_out_vals overlaps d_live");
+    const Call call(c, stream);
+    return dev_spgemm(c, {out, live, a, b, nnz_a, nnz_b, pair_ptr, pair_a, pair_b, n_out, n_pairs, c->d_counter + 4}, call.st);
+}
+int sr_spgemm_dead_count(sr_ctx *c, unsigned long long *out, void *stream) {
+    if (int rc = check(c, {out})) return rc;
+    const Call call(c, stream);
+    return read_counter(c, 4, out, call.st);
+}
+int sr_sparse_transpose(sr_ctx *c, uint64_t *t_vals, uint32_t *t_cols, uint64_t *t_row_ptr, const uint64_t *vals, const uint32_t *cols,
+                        const uint64_t *row_ptr, size_t nrows, size_t ncols) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!row_ptr) return fail(SR_E_INVALID, "sparse_transpose: null buffer");
+    std::vector<uint32_t> perm;
+    try {
+        perm.resize(row_ptr[nrows] <= 0xFFFFFFFFull ? (size_t)row_ptr[nrows] : 0);
+    } catch (const std::exception &) {
+        return fail(SR_E_ALLOC, "sparse_transpose: out of host memory");
+    }
+    if (int rc = sr_sparse_transpose_pattern(cols, row_ptr, nrows, ncols, t_row_ptr, t_cols, perm.data())) return rc;
+    const size_t nnz = perm.size();
+    if (int rc = check_count(c, nnz)) return rc;
+    if (nnz == 0) return SR_OK;
+    if (!vals || !t_vals) return fail(SR_E_INVALID, "sparse_transpose: null buffer");
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    return staged(c, {{vals, nullptr, nnz * w}, {perm.data(), nullptr, nnz * 4}, {nullptr, t_vals, nnz * w}}, [&](void *const *d) {
+        return dev_move(c, (uint64_t *)d[2], (const uint64_t *)d[0], (const uint32_t *)d[1], nnz, nnz, 0, 0, c->stream);
+    });
+}
+int sr_transpose(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t nrows, size_t ncols) {
+    if (int rc = check(c, {}, nrows, ncols)) return rc;
+    if (nrows == 0 || ncols == 0) return SR_OK;
+    if (!out || !in) return fail(SR_E_INVALID, "transpose: null buffer");
+    const Call call(c);
+    const size_t bytes = nrows * ncols * c->degree * c->limbs * 8;
+    return staged(c, {{in, nullptr, bytes}, {nullptr, out, bytes}}, [&](void *const *d) {
+        return dev_move(c, (uint64_t *)d[1], (const uint64_t *)d[0], nullptr, nrows * ncols, nrows * ncols, nrows, ncols, c->stream);
+    });
+}
+int sr_spgemm_ntt(sr_ctx *c, uint64_t *out_vals, uint32_t *out_cols, uint64_t *out_row_ptr, size_t *nnz_out, const uint64_t *a_vals,
+                  const uint32_t *a_cols, const uint64_t *a_row_ptr, size_t n, size_t m, const uint64_t *b_vals, const uint32_t *b_cols,
+                  const uint64_t *b_row_ptr, size_t p) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!out_row_ptr || !nnz_out) return fail(SR_E_INVALID, "spgemm: null buffer");
+    size_t n_out = 0, n_pairs = 0;
+    if (int rc = sr_spgemm_pattern(a_cols, a_row_ptr, n, m, b_cols, b_row_ptr, p, nullptr, nullptr, nullptr, nullptr, nullptr, &n_out, &n_pairs)) return rc;
+    *nnz_out = 0;
+    if (n_out == 0) {
+        for (size_t i = 0; i <= n; i++) out_row_ptr[i] = 0;
+        return SR_OK;
+    }
+    const size_t nnz_a = (size_t)a_row_ptr[n], nnz_b = (size_t)b_row_ptr[m];
+    if (!out_vals || !out_cols || !a_vals || !b_vals) return fail(SR_E_INVALID, "spgemm: null buffer");
+    if (int rc = check_spgemm(c, nnz_a, nnz_b, n_out, n_pairs)) return rc;
+    // one index block [pair_ptr | pair_a | pair_b] so that the five HOST_* slots suffice
+    std::vector<uint64_t> idx, row_ptr;
+    std::vector<uint32_t> cols, live;
+    try {
+        idx.resize(n_out + 1 + n_pairs);  // two 32-bit positions per pair: one 64-bit word
+        row_ptr.resize(n + 1);
+        cols.resize(n_out);
+        live.resize(n_out);
+    } catch (const std::exception &) {
+        return fail(SR_E_ALLOC, "spgemm: out of host memory");
+    }
+    uint32_t *pa = reinterpret_cast<uint32_t *>(idx.data() + n_out + 1), *pb = pa + n_pairs;
+    if (int rc = sr_spgemm_pattern(a_cols, a_row_ptr, n, m, b_cols, b_row_ptr, p, row_ptr.data(), cols.data(), idx.data(), pa, pb, &n_out, &n_pairs))
+        return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    {
+        const Call call(c);
+        const Staged ops[] = {{a_vals, nullptr, nnz_a * w}, {b_vals, nullptr, nnz_b * w}, {idx.data(), nullptr, idx.size() * 8}, {nullptr, out_vals, n_out * w},
+                              {nullptr, live.data(), n_out * 4}};
+        if (int rc = staged(c, ops, [&](void *const *d) {
+                const uint64_t *di = (const uint64_t *)d[2];
+                const uint32_t *dpa = reinterpret_cast<const uint32_t *>(di + n_out + 1);
+                return dev_spgemm(c, {(uint64_t *)d[3], (uint32_t *)d[4], (const uint64_t *)d[0], (const uint64_t *)d[1], nnz_a, nnz_b, di, dpa, dpa + n_pairs,
+                                      n_out, n_pairs, nullptr}, c->stream);
+            }))
+            return rc;
+    }
+    // the reference's matrix: the entries none of whose products was non-zero are dropped, in place (kept <= e throughout)
+    const size_t words = (size_t)c->degree * c->limbs;
+    size_t kept = 0, e = 0;
+    out_row_ptr[0] = 0;
+    for (size_t i = 0; i < n; i++) {
+        for (; e < row_ptr[i + 1]; e++) {
+            if (!live[e]) continue;
+            if (kept != e) std::memmove(out_vals + kept * words, out_vals + e * words, words * 8);
+            out_cols[kept++] = cols[e];
+        }
+        out_row_ptr[i + 1] = kept;
+    }
+    *nnz_out = kept;
+    return SR_OK;
 }
 int sr_sum_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n) { return host_fold(c, out, in, n, false); }
 int sr_product_batch(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n) { return host_fold(c, out, in, n, true); }

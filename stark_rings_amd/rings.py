@@ -119,6 +119,77 @@ def symm_recompose_plan(ring, log2_degree, n, d):
     return work.value, launches.value
 
 
+def _idx(a, dtype):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, ctypes.c_void_p(a.ctypes.data if a.size else 0)
+
+
+def _csr_args(cols, row_ptr, nrows, what):
+    if nrows < 0:
+        raise RingError("%s: negative count" % what)
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+    if row_ptr.size != nrows + 1:
+        raise RingError("%s: row_ptr must have nrows + 1 entries" % what)
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    if cols.size != int(row_ptr[-1]):
+        raise RingError("%s: cols must have row_ptr[nrows] entries" % what)
+    return cols, row_ptr
+
+
+def sparse_transpose_pattern(cols, row_ptr, nrows, ncols):
+    """sr_sparse_transpose_pattern: (t_row_ptr, t_cols, perm) of the transpose of a CSR pattern -- a stable counting sort by column,
+    t_vals[t] = vals[perm[t]].  Host arithmetic, no device, no context."""
+    if ncols < 0:
+        raise RingError("sparse_transpose_pattern: negative count")
+    cols, row_ptr = _csr_args(cols, row_ptr, nrows, "sparse_transpose_pattern")
+    t_row_ptr = np.empty(ncols + 1, dtype=np.uint64)
+    t_cols, perm = np.empty(cols.size, dtype=np.uint32), np.empty(cols.size, dtype=np.uint32)
+    rc = _lib.load().sr_sparse_transpose_pattern(_idx(cols, np.uint32)[1], row_ptr.ctypes.data, nrows, ncols, t_row_ptr.ctypes.data,
+                                                 _idx(t_cols, np.uint32)[1], _idx(perm, np.uint32)[1])
+    if rc != 0:
+        raise RingError("sr_sparse_transpose_pattern failed (%d): %s" % (rc, _lib.last_error()))
+    return t_row_ptr, t_cols, perm
+
+
+def spgemm_pattern(a_cols, a_row_ptr, n, m, b_cols, b_row_ptr, p, count_only=False):
+    """sr_spgemm_pattern: the structural product of two CSR patterns with strictly ascending rows -- (out_row_ptr, out_cols, pair_ptr,
+    pair_a, pair_b), or (n_out, n_pairs) with count_only.  Host arithmetic, no device, no context."""
+    if m < 0 or p < 0:
+        raise RingError("spgemm_pattern: negative count")
+    a_cols, a_row_ptr = _csr_args(a_cols, a_row_ptr, n, "spgemm_pattern")
+    b_cols, b_row_ptr = _csr_args(b_cols, b_row_ptr, m, "spgemm_pattern")
+    lib = _lib.load()
+    n_out, n_pairs = ctypes.c_size_t(), ctypes.c_size_t()
+    head = (_idx(a_cols, np.uint32)[1], a_row_ptr.ctypes.data, n, m, _idx(b_cols, np.uint32)[1], b_row_ptr.ctypes.data, p)
+    rc = lib.sr_spgemm_pattern(*head, None, None, None, None, None, ctypes.byref(n_out), ctypes.byref(n_pairs))
+    if rc != 0:
+        raise RingError("sr_spgemm_pattern failed (%d): %s" % (rc, _lib.last_error()))
+    if count_only:
+        return n_out.value, n_pairs.value
+    out_row_ptr, pair_ptr = np.empty(n + 1, dtype=np.uint64), np.empty(n_out.value + 1, dtype=np.uint64)
+    out_cols = np.empty(n_out.value, dtype=np.uint32)
+    pair_a, pair_b = np.empty(n_pairs.value, dtype=np.uint32), np.empty(n_pairs.value, dtype=np.uint32)
+    rc = lib.sr_spgemm_pattern(*head, out_row_ptr.ctypes.data, _idx(out_cols, np.uint32)[1], pair_ptr.ctypes.data, _idx(pair_a, np.uint32)[1],
+                               _idx(pair_b, np.uint32)[1], ctypes.byref(n_out), ctypes.byref(n_pairs))
+    if rc != 0:
+        raise RingError("sr_spgemm_pattern failed (%d): %s" % (rc, _lib.last_error()))
+    return out_row_ptr, out_cols, pair_ptr, pair_a, pair_b
+
+
+def spgemm_plan(ring, log2_degree, n_out, n_pairs):
+    """sr_spgemm_plan: (work_elems, launches) of the numeric phase of a sparse product -- host arithmetic, no device, no context."""
+    if isinstance(ring, str):
+        ring = _RING_NAMES[ring]
+    if n_out < 0 or n_pairs < 0:
+        raise RingError("spgemm: negative count")
+    work, launches = ctypes.c_size_t(), ctypes.c_int()
+    rc = _lib.load().sr_spgemm_plan(int(ring), _log2_degree_arg(ring, log2_degree), int(n_out), int(n_pairs), ctypes.byref(work),
+                                    ctypes.byref(launches))
+    if rc != 0:
+        raise RingError("sr_spgemm_plan failed (%d): %s" % (rc, _lib.last_error()))
+    return work.value, launches.value
+
+
 def _basis_words(basis, decompose):
     """(lo, hi) 64-bit words of a decomposition basis (the reference takes b: u128, balanced_decomposition/mod.rs:62).  Anything
     outside [0, 2^128) is refused instead of being truncated by ctypes.  decompose_balanced_in_place casts `b as i128` (mod.rs:73),
@@ -455,6 +526,69 @@ class CyclotomicRing:
         self._check(self._lib.sr_symm_recompose(self._ctx, _np_ptr(out), _np_ptr(mat if mat.size else out), n, d,
                                                 _np_ptr(powers if powers.size else out)))
         return out[:n * (n + 1) // 2 * w]
+
+    # -- sparse matrices: transpose and sparse x sparse product (linear_algebra/src/ops.rs:9-62, sparse_matrix.rs:219-281) --------------
+    sparse_transpose_pattern = staticmethod(sparse_transpose_pattern)
+    spgemm_pattern = staticmethod(spgemm_pattern)
+
+    def _flatten_rows(self, rows):
+        """the reference's SparseMatrix.coeffs (rows of (element words, column)) -> (vals, cols, row_ptr)"""
+        w = self.words_per_elem
+        row_ptr = np.zeros(len(rows) + 1, dtype=np.uint64)
+        for r, row in enumerate(rows):
+            row_ptr[r + 1] = row_ptr[r] + len(row)
+        nnz = int(row_ptr[-1])
+        vals, cols = np.zeros(max(nnz * w, 1), dtype=np.uint64), np.zeros(max(nnz, 1), dtype=np.uint32)
+        j = 0
+        for row in rows:
+            for elem, col in row:
+                if not 0 <= col < 1 << 32:
+                    raise RingError("column index out of range")
+                vals[j * w:(j + 1) * w] = elem
+                cols[j] = col
+                j += 1
+        return vals, cols, row_ptr, nnz
+
+    def _rows_of(self, vals, cols, row_ptr):
+        w = self.words_per_elem
+        return [[(vals[t * w:(t + 1) * w].copy(), int(cols[t])) for t in range(int(row_ptr[i]), int(row_ptr[i + 1]))]
+                for i in range(len(row_ptr) - 1)]
+
+    def transpose(self, data, nrows, ncols):
+        """Host buffers: the data of Matrix::transpose (ops.rs:36-44) -- out[j][i] = data[i][j] for a row-major nrows x ncols matrix,
+        as one flat array of ncols x nrows ring elements."""
+        if nrows < 0 or ncols < 0 or data.size != nrows * ncols * self.words_per_elem:
+            raise RingError("transpose: DifferentLengths")
+        out = np.empty(max(data.size, 1), dtype=np.uint64)
+        self._check(self._lib.sr_transpose(self._ctx, _np_ptr(out), _np_ptr(data if data.size else out), nrows, ncols))
+        return out[:data.size]
+
+    def sparse_transpose(self, rows, ncols):
+        """Host buffers: SparseMatrix::transpose (ops.rs:46-62) of the len(rows) x ncols matrix whose rows are those of spmv_ntt
+        (SparseMatrix.coeffs); returns the ncols rows of the result.  The rows need not be sorted."""
+        w, nrows = self.words_per_elem, len(rows)
+        vals, cols, row_ptr, nnz = self._flatten_rows(rows)
+        t_vals, t_cols = np.zeros(max(nnz * w, 1), dtype=np.uint64), np.zeros(max(nnz, 1), dtype=np.uint32)
+        t_row_ptr = np.zeros(ncols + 1, dtype=np.uint64)
+        self._check(self._lib.sr_sparse_transpose(self._ctx, t_vals.ctypes.data, t_cols.ctypes.data, t_row_ptr.ctypes.data, vals.ctypes.data,
+                                                  cols.ctypes.data, row_ptr.ctypes.data, nrows, ncols))
+        return self._rows_of(t_vals, t_cols, t_row_ptr)
+
+    def spgemm_ntt(self, rows_a, rows_b, m, p):
+        """Host buffers: SparseMatrix<RqNTT>::checked_mul_mat (sparse_matrix.rs:219-275) of A (len(rows_a) x m) and B (m x p); the row
+        lists are those of spmv_ntt.  Returns the rows of the product; RingError where the reference returns None (len(rows_b) != m)
+        and for rows that do not ascend strictly."""
+        if len(rows_b) != m:
+            raise RingError("spgemm: DifferentLengths")
+        n, w = len(rows_a), self.words_per_elem
+        av, ac, ap, _ = self._flatten_rows(rows_a)
+        bv, bc, bp, _ = self._flatten_rows(rows_b)
+        n_out, _ = spgemm_pattern(ac[:int(ap[-1])], ap, n, m, bc[:int(bp[-1])], bp, p, count_only=True)
+        out_vals, out_cols = np.zeros(max(n_out * w, 1), dtype=np.uint64), np.zeros(max(n_out, 1), dtype=np.uint32)
+        out_row_ptr, nnz = np.zeros(n + 1, dtype=np.uint64), ctypes.c_size_t()
+        self._check(self._lib.sr_spgemm_ntt(self._ctx, out_vals.ctypes.data, out_cols.ctypes.data, out_row_ptr.ctypes.data, ctypes.byref(nnz),
+                                            av.ctypes.data, ac.ctypes.data, ap.ctypes.data, n, m, bv.ctypes.data, bc.ctypes.data, bp.ctypes.data, p))
+        return self._rows_of(out_vals, out_cols, out_row_ptr)
 
     def rot(self, data):
         """Cyclotomic::rot (traits.rs:54-66) of every element of the batch, in place: coefficients times X modulo the ring."""
@@ -1079,6 +1213,69 @@ class CyclotomicRing:
             raise RingError("symm_recompose: DifferentLengths")
         self._check(self._lib.sr_symm_recompose_dev(self._ctx, po, pm, n, d, pp, pw, nw // w, self._stream(stream)))
         return out
+
+    def spgemm_plan(self, n_out, n_pairs):
+        """sr_spgemm_plan for this ring: (work_elems, launches)."""
+        return spgemm_plan(self.ring, self.degree.bit_length() - 1, n_out, n_pairs)
+
+    def _dev_idx(self, t, dtype, what):
+        """(pointer, length) of an index tensor on this context's device; None or empty: (null, 0)"""
+        if t is None or t.numel() == 0:
+            return ctypes.c_void_p(0), 0
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.device.index == self.device):
+            raise RingError("%s must be a contiguous %s tensor on cuda:%d" % (what, dtype, self.device))
+        return ctypes.c_void_p(t.data_ptr()), t.numel()
+
+    def gather_dev(self, out, src, perm, stream=None):
+        """sr_gather_batch_dev: out[t] = src[perm[t]] on whole ring elements (perm: int32 positions), out of place.  A position outside
+        src is skipped and counted (spmv_bad_index_count).  Allocates nothing; capturable."""
+        import torch
+
+        w = self.words_per_elem
+        po, no = self._dev_or_null(out)
+        pi, ni = self._dev_or_null(src)
+        pp, n = self._dev_idx(perm, torch.int32, "perm")
+        if no != n * w or ni % w:
+            raise RingError("gather: DifferentLengths")
+        self._check(self._lib.sr_gather_batch_dev(self._ctx, po, pi, pp, n, ni // w, self._stream(stream)))
+        return out
+
+    def transpose_dev(self, out, a, nrows, ncols, stream=None):
+        """sr_transpose_dev: out[j][i] = a[i][j] for a dense row-major nrows x ncols matrix, out of place.  Allocates nothing."""
+        w = self.words_per_elem
+        po, no = self._dev_or_null(out)
+        pa, na = self._dev_or_null(a)
+        if nrows < 0 or ncols < 0 or na != nrows * ncols * w or no != na:
+            raise RingError("transpose: DifferentLengths")
+        self._check(self._lib.sr_transpose_dev(self._ctx, po, pa, nrows, ncols, self._stream(stream)))
+        return out
+
+    def spgemm_ntt_dev(self, out_vals, live, a_vals, b_vals, pair_ptr, pair_a, pair_b, work=None, stream=None):
+        """sr_spgemm_ntt_dev: out_vals[e] = sum of a_vals[pair_a[t]] * b_vals[pair_b[t]] over pair_ptr[e] <= t < pair_ptr[e + 1];
+        live[e] (int32) = 1 iff some product of the entry is non-zero.  pair_ptr: int64 [n_out + 1], pair_a / pair_b: int32 (what
+        spgemm_pattern wrote).  Entries that stay dead are counted (spgemm_dead_count).  Allocates nothing; capturable."""
+        import torch
+
+        w = self.words_per_elem
+        po, no = self._dev_or_null(out_vals)
+        pa, na = self._dev_or_null(a_vals)
+        pb, nb = self._dev_or_null(b_vals)
+        pw, nw = self._dev_or_null(work)
+        pl, nl = self._dev_idx(live, torch.int32, "live")
+        ppp, npp = self._dev_idx(pair_ptr, torch.int64, "pair_ptr")
+        ppa, npa = self._dev_idx(pair_a, torch.int32, "pair_a")
+        ppb, npb = self._dev_idx(pair_b, torch.int32, "pair_b")
+        if npp < 1 or no != (npp - 1) * w or nl != npp - 1 or npa != npb or na % w or nb % w:
+            raise RingError("spgemm: DifferentLengths")
+        self._check(self._lib.sr_spgemm_ntt_dev(self._ctx, po, pl, pa, na // w, pb, nb // w, ppp, ppa, ppb, npp - 1, npa, pw, nw // w,
+                                                self._stream(stream)))
+        return out_vals
+
+    def spgemm_dead_count(self, stream=None):
+        """sr_spgemm_dead_count: the structural entries none of whose products was non-zero since the last read; clears the count."""
+        n = ctypes.c_ulonglong(0)
+        self._check(self._lib.sr_spgemm_dead_count(self._ctx, ctypes.byref(n), self._stream(stream)))
+        return int(n.value)
 
     def rot_dev(self, out, a, stream=None):
         po, n = self._dev(out)
