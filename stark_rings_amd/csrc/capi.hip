@@ -2153,6 +2153,9 @@ int packed_elementwise(sr_ctx *c, uint32_t *l, const uint32_t *r, size_t batch, 
 // on the host, one scalar operation per call.  Lets the CPU test-suite check fields.hpp without a
 // GPU.  Not a compute path: no batch entry point routes through it.
 // op: 0 add, 1 sub, 2 mul_boundary (a*b*R_b^-1 on in-memory images), 3 mul_tw, 4 tw_from_u64(a[0])
+// tools/ubench/field_ops_device.hip runs the same operations in kernels and takes the field ids of sr_selftest_field_op
+// (0 Goldilocks, 1 BabyBear, 2 Stark, 3 Frog, 4 StarkL) and the op numbers of selftest_op / selftest_lazy below (its own
+// additions start at 16): keep the two equal.
 template <class F>
 int selftest_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out) {
     using S = typename F::storage;

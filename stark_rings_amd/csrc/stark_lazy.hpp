@@ -22,10 +22,13 @@
 //       mul_tw(x 2^256, w 2^280) = x w 2^256.  The slot product of two data elements comes out as a b 2^232: the generic
 //       set-up code folds the missing 2^24 into the inverse transform's scale constants (kappa_bits = 280 in capi.hip).
 //
-// Everything is plain C++ (host and device compile the same source); constants the compiler would otherwise turn into shift
-// sequences are made opaque so that each reduction term is one v_mad_u64_u32.
-// Checked against Python big integers (tests/test_host_fields.py via sr_selftest_field_op) and, through the kernels, by
-// every Stark parity test.
+// Everything but mul_tw is plain C++ that host and device compile from the same source.  mul_tw exists twice: the device build
+// is generated asm, one statement per column (tools/gen_stark_mul_cols.py -> stark_mul_cols.inc), the host build is the C++
+// loop next to it.
+// Checked against Python big integers: the host build by tests/test_host_fields.py (via sr_selftest_field_op), the device
+// build AND the host build by tests/test_device_fields_gpu.py (tools/ubench/field_ops_device.hip, crafted operands in mixed
+// and partially masked waves) -- that test is the check between the two mul_tw -- and, through the kernels, by every Stark
+// parity test.
 #pragma once
 #include "fields.hpp"
 

@@ -33,6 +33,43 @@ def test_device_arithmetic_equals_host_build_of_the_same_source():
     assert r.returncode == 0 and "field_check: 0 mismatches" in out, out[-2000:]
 
 
+def _hipcc():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        hipcc = shutil.which("hipcc")
+    return hipcc
+
+
+def _run_checker(name, deps, timeout):
+    """Build tools/ubench/<name> if it is older than its sources, run it once, return (exit status, output)."""
+    src, exe = os.path.join(ROOT, "tools", "ubench", name + ".hip"), os.path.join(ROOT, "tools", "ubench", name)
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in [src] + deps):
+        if not _hipcc():
+            pytest.fail("hipcc not found: cannot build tools/ubench/" + name)
+        subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-result", "-o", exe, src], check=True, cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout, cwd=ROOT)
+    return r.returncode, r.stdout.decode()
+
+
+@pytest.mark.gpu
+def test_stark_mont_mul_device_equals_host_build():
+    """Stark::mont_mul: the device build (product scanning, inline-asm multiply-accumulates with their carries in SGPR pairs)
+    against the host build (CIOS) on 2^16 uniform and edge operand pairs (tools/ubench/stark_montmul_check.hip)."""
+    rc, out = _run_checker("stark_montmul_check", [DEPS[1]], 120)
+    assert rc == 0 and "stark mont_mul device vs host: 0 mismatches of 65536" in out, out[-2000:]
+
+
+@pytest.mark.gpu
+def test_stark_lazy_products_device_equals_host_build():
+    """StarkL::mul_tw and mul_data: the generated asm columns of the device build against the host loop, limb for limb, on lazy
+    operands with signed limbs up to +-2^31 -- the only place where such operands meet the generated columns on the device
+    (tools/ubench/stark_lazy_check.hip)."""
+    csrc = os.path.join(ROOT, "stark_rings_amd", "csrc")
+    rc, out = _run_checker("stark_lazy_check", [DEPS[1], os.path.join(csrc, "stark_lazy.hpp"), os.path.join(csrc, "stark_mul_cols.inc")], 120)
+    assert rc == 0 and "StarkL mul_tw / mul_data device vs host: 0 mismatches of 131072" in out, out[-2000:]
+
+
 SELF_SRC = os.path.join(ROOT, "tools", "ubench", "repcheck_selftest.hip")
 SELF_EXE = os.path.join(ROOT, "tools", "ubench", "repcheck_selftest")
 

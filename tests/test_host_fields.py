@@ -19,6 +19,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["goldilocks", "babybear", "stark", "frog"]
 KAPPA_BITS = {"goldilocks": 0, "babybear": 32, "stark": 256, "frog": 64}
 
+# Edge operands, shared with tests/test_device_fields_gpu.py (the device build of the same arithmetic).
+
+
+def field_edges(p):
+    return [0, 1, 2, p - 1, p - 2, (p - 1) // 2, 2**32 % p, (2**32 - 1) % p, (2**63) % p]
+
+
+FIELD_EDGES = {name: field_edges(P.PRIMES[name][0]) for name in NAMES}
+# products whose 128-bit image stresses every carry/borrow branch of reduce128
+GOLDILOCKS_MUL_SPECIALS = [P.GOLDILOCKS_P - 1, P.GOLDILOCKS_P - 2, 2**32, 2**32 - 1, 2**32 + 1, 2**63, 2**64 - 2**33, 0xFFFFFFFF00000000,
+                           0xFFFFFFFE, 1]
+_SP = P.STARK_P
+STARK_LAZY_EDGES = [0, 1, 2, _SP - 1, _SP - 2, (_SP - 1) // 2, 2**28 - 1, 2**28, 2**224, 2**251, 2**251 - 1, 17 * 2**192, (1 << 250) + 12345,
+                    sum(((1 << 28) - 1) << (28 * i) for i in range(9)) % _SP]
+# the slow path of canonical(): a borrow out of limb 0 after the fold (value still >= 0), and values that fold to < 0
+_H = 2**250 + 17 * 2**192
+STARK_LAZY_SLOW_PAIRS = ((_H, _H), (2**251, 0), (2**251 + 2**28, 0), (0, 1), (1, 2**251), (2**251 + 2**56, 2**251 + 2**84), (_SP - 1, _SP - 1))
+# canonical() on signed lazy states around every boundary it distinguishes (multiples of 2^251, of p, limb borders)
+STARK_LAZY_BOUNDARIES = sorted({v % _SP for base in (0, 2**251, _SP, 2**28, 2**196, 17 * 2**192, 2**224, (_SP - 1) // 2, (_SP + 1) // 3,
+                                                     (2 * _SP) // 5, (_SP + 2**251) // 7, 2**251 // 3, 2**251 // 5)
+                                for v in (base - 2, base - 1, base, base + 1, base + 2, base + 2**28, base - 2**28)})
+
 
 def test_library_exports_every_declared_symbol():
     lib = _lib.load()
@@ -44,8 +66,7 @@ def _op(field, op, a, b, limbs):
 def test_field_ops_match_python_model(fid, name):
     p, _, limbs = P.PRIMES[name]
     rng = random.Random(11 + fid)
-    edge = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, 2**32 % p, (2**32 - 1) % p, (2**63) % p]
-    vals = edge + [rng.randrange(p) for _ in range(300)]
+    vals = FIELD_EDGES[name] + [rng.randrange(p) for _ in range(300)]
     Rb_inv = pow(pow(2, 64 * limbs, p), -1, p)
     kap_inv = pow(pow(2, KAPPA_BITS[name], p), -1, p)
     for i in range(0, len(vals) - 1):
@@ -59,9 +80,8 @@ def test_field_ops_match_python_model(fid, name):
 
 
 def test_goldilocks_mul_worst_cases():
-    # products whose 128-bit image stresses every carry/borrow branch of reduce128
     p = P.GOLDILOCKS_P
-    specials = [p - 1, p - 2, 2**32, 2**32 - 1, 2**32 + 1, 2**63, 2**64 - 2**33, 0xFFFFFFFF00000000, 0xFFFFFFFE, 1]
+    specials = GOLDILOCKS_MUL_SPECIALS
     for a in specials:
         for b in specials:
             a_, b_ = a % p, b % p
@@ -87,9 +107,7 @@ def test_stark_lazy_limb_arithmetic_matches_python_model():
     p = P.STARK_P
     rng = random.Random(41)
     r_inv = pow(pow(2, 280, p), -1, p)
-    edge = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, 2**28 - 1, 2**28, 2**224, 2**251, 2**251 - 1, 17 * 2**192, (1 << 250) + 12345,
-            sum(((1 << 28) - 1) << (28 * i) for i in range(9)) % p]
-    vals = edge + [rng.randrange(p) for _ in range(400)]
+    vals = STARK_LAZY_EDGES + [rng.randrange(p) for _ in range(400)]
     for i in range(len(vals)):
         a, b = vals[i], vals[(i * 5 + 2) % len(vals)]
         assert _op(4, 0, a, b, 4) == (a + b) % p
@@ -101,15 +119,12 @@ def test_stark_lazy_limb_arithmetic_matches_python_model():
     for x in (0, 1, 7, 2**40, 2**64 - 1):
         assert _op(4, 4, x, 0, 4) == x * pow(2, 280, p) % p
     # the slow path of canonical(): a borrow out of limb 0 after the fold (value still >= 0), and values that fold to < 0
-    h = 2**250 + 17 * 2**192
-    for a, b in ((h, h), (2**251, 0), (2**251 + 2**28, 0), (0, 1), (1, 2**251), (2**251 + 2**56, 2**251 + 2**84), (p - 1, p - 1)):
+    for a, b in STARK_LAZY_SLOW_PAIRS:
         assert _op(4, 0, a, b, 4) == (a + b) % p
         assert _op(4, 1, a, b, 4) == (a - b) % p
         assert _op(4, 1, b, a, 4) == (b - a) % p
     # canonical() on signed lazy states around every boundary it distinguishes (multiples of 2^251, of p, limb borders)
-    bnd = sorted({v % p for base in (0, 2**251, p, 2**28, 2**196, 17 * 2**192, 2**224, (p - 1) // 2, (p + 1) // 3, (2 * p) // 5,
-                                     (p + 2**251) // 7, 2**251 // 3, 2**251 // 5)
-                  for v in (base - 2, base - 1, base, base + 1, base + 2, base + 2**28, base - 2**28)})
+    bnd = STARK_LAZY_BOUNDARIES
     for a in bnd:
         for b in bnd:
             assert _op(4, 7, a, b, 4) == (3 * a - 5 * b) % p
