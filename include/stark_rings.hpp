@@ -29,6 +29,8 @@
 //   DenseMultilinearExtension<RqNTT>     crates/poly mle/dense.rs    class DenseMultilinearExtension: fix_variables, fixed_variables,
 //     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations;
 //                                                                      round_evals / product_sum: a sum-check round's message (sr_mle_round_evals)
+//   a sum of products of dense MLEs      (HyperPlonk's VirtualPolynomial) class VirtualPolynomial: add_mle_list, mul_by_mle, degree, round_evals, sum
+//                                                                      (sr_vpoly_round_evals: one pass, every distinct table read once)
 //   SparseMultilinearExtension<RqNTT>    crates/poly mle/sparse.rs   class SparseMultilinearExtension: from_slice, from_matrix, fix_variables,
 //     precompute_eq                      sparse.rs:381-394             fixed_variables, evaluate, to_evaluations; eq_table(point); device
 //                                                                      pointers: CyclotomicConfig::eq_table_dev / smle_plan / smle_fix_variables_dev
@@ -526,6 +528,99 @@ inline RqNTTVec eq_table(const RqNTTVec &point) {
     CyclotomicConfig::check(sr_eq_table(cfg.raw(), out.data(), point.len() ? point.words().data() : &dummy, point.len()), "sr_eq_table");
     return RqNTTVec(cfg, std::move(out));
 }
+
+// A sum of products of dense MLEs with ring coefficients, g = sum_k c_k prod_s f_{k,s}, after HyperPlonk's VirtualPolynomial (the code
+// crates/poly's polynomials/multilinear_polynomial.rs was adapted from): the object a sum-check is run on -- eq (a b - c),
+// sum_i alpha_i eq prod_j (...).  The MLEs are referred to, not copied, and must outlive the polynomial; an MLE that is in several
+// products is one table slot and is read once per round (sr_vpoly_round_evals).  At most SR_VPOLY_MAX_TABLES distinct MLEs,
+// SR_VPOLY_MAX_TERMS products, SR_VPOLY_MAX_FACTORS factors per product; throws std::length_error beyond, leaving the polynomial as it was.
+class VirtualPolynomial {
+public:
+    VirtualPolynomial(CyclotomicConfig cfg, size_t num_vars) : cfg_(std::move(cfg)), nv_(num_vars) {}
+    size_t num_vars() const { return nv_; }
+    // the largest number of factors of a product: a round message has degree() + 1 elements
+    size_t degree() const {
+        int d = 0;
+        for (const sr_vpoly_term &t : terms_) d = t.n_factors > d ? t.n_factors : d;
+        return (size_t)d;
+    }
+    const std::vector<const DenseMultilinearExtension *> &tables() const { return tables_; }  // the table slots, in order of first use
+    const std::vector<sr_vpoly_term> &terms() const { return terms_; }
+    // g += coeff * prod(mles): 1 .. 4 MLEs (one may appear twice), coeff one ring element or nullptr for one()
+    void add_mle_list(const std::vector<const DenseMultilinearExtension *> &mles, const RqNTTVec *coeff = nullptr) {
+        if (mles.empty() || mles.size() > SR_VPOLY_MAX_FACTORS) throw std::length_error("VirtualPolynomial: a product has 1 .. 4 factors");
+        if (terms_.size() >= SR_VPOLY_MAX_TERMS) throw std::length_error("VirtualPolynomial: more than 8 products");
+        if (coeff && coeff->len() != 1) throw std::length_error("VirtualPolynomial: the coefficient is not one ring element");
+        std::vector<const DenseMultilinearExtension *> slots = tables_;
+        sr_vpoly_term t{};
+        for (const DenseMultilinearExtension *m : mles) t.table[t.n_factors++] = slot_of(slots, m);
+        tables_ = std::move(slots);
+        terms_.push_back(t);
+        has_coeff_.push_back(coeff != nullptr);
+        coeffs_.push_back(coeff ? coeff->words() : std::vector<uint64_t>());
+    }
+    // g *= mle: the MLE becomes one more factor of every product
+    void mul_by_mle(const DenseMultilinearExtension *mle) {
+        if (terms_.empty()) throw std::length_error("VirtualPolynomial: mul_by_mle on an empty polynomial");
+        for (const sr_vpoly_term &t : terms_)
+            if (t.n_factors >= SR_VPOLY_MAX_FACTORS) throw std::length_error("VirtualPolynomial: a product has 1 .. 4 factors");
+        std::vector<const DenseMultilinearExtension *> slots = tables_;
+        const int slot = slot_of(slots, mle);
+        tables_ = std::move(slots);
+        for (sr_vpoly_term &t : terms_) t.table[t.n_factors++] = slot;
+    }
+    // The prover's message of one sum-check round over g: the degree() + 1 elements p(t) = sum_b g(t, b), t = 0 .. degree(), the variable
+    // being the one fix_variables (SR_MLE_LEADING) or fix_last_variables (SR_MLE_TRAILING) fixes next.
+    RqNTTVec round_evals(int order = SR_MLE_LEADING) const {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("round_evals: unknown order");
+        return call(order);
+    }
+    // sum_b g(b) over the hypercube: the claimed sum of the sum-check, one ring element
+    RqNTTVec sum() const { return call(SR_MLE_ROUND_SUM); }
+
+private:
+    int slot_of(std::vector<const DenseMultilinearExtension *> &slots, const DenseMultilinearExtension *m) const {
+        if (m->config().raw() != cfg_.raw() || m->num_vars() != nv_) throw std::length_error("VirtualPolynomial: the MLEs differ in ring or num_vars");
+        for (size_t j = 0; j < slots.size(); j++)
+            if (slots[j] == m) return (int)j;
+        if (slots.size() >= SR_VPOLY_MAX_TABLES) throw std::length_error("VirtualPolynomial: more than 8 distinct tables");
+        slots.push_back(m);
+        return (int)slots.size() - 1;
+    }
+    RqNTTVec call(int mode) const {
+        if (terms_.empty()) throw std::length_error("VirtualPolynomial: no product has been added");
+        const size_t w = cfg_.words_per_elem();
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        for (const DenseMultilinearExtension *t : tables_) {
+            ptrs.push_back(t->words().empty() ? nullptr : t->words().data());
+            sizes.push_back(t->len());
+        }
+        std::vector<uint64_t> coeffs;  // empty: every coefficient is one() and none is passed
+        bool any = false;
+        for (bool h : has_coeff_) any = any || h;
+        if (any) {
+            const uint64_t dummy = 0;
+            std::vector<uint64_t> one(w);  // the eq table of no variables is the single element one()
+            CyclotomicConfig::check(sr_eq_table(cfg_.raw(), one.data(), &dummy, 0), "sr_eq_table");
+            for (size_t k = 0; k < terms_.size(); k++) {
+                const std::vector<uint64_t> &c = has_coeff_[k] ? coeffs_[k] : one;
+                coeffs.insert(coeffs.end(), c.begin(), c.end());
+            }
+        }
+        std::vector<uint64_t> out(w * (mode == SR_MLE_ROUND_SUM ? 1 : degree() + 1));
+        CyclotomicConfig::check(sr_vpoly_round_evals(cfg_.raw(), out.data(), ptrs.data(), sizes.data(), (int)tables_.size(), terms_.data(),
+                                                     (int)terms_.size(), any ? coeffs.data() : nullptr, nv_, mode),
+                                "sr_vpoly_round_evals");
+        return RqNTTVec(cfg_, std::move(out));
+    }
+    CyclotomicConfig cfg_;
+    size_t nv_;
+    std::vector<const DenseMultilinearExtension *> tables_;
+    std::vector<sr_vpoly_term> terms_;
+    std::vector<bool> has_coeff_;
+    std::vector<std::vector<uint64_t>> coeffs_;
+};
 
 // SparseMultilinearExtension<RqNTT> of crates/poly (src/mle/sparse.rs): the stored evaluations as ascending indices and their values
 // in CRT/NTT form, the iteration order of the reference's BTreeMap.  Stored zeros are kept.  Host buffers over sr_smle_fix_variables;

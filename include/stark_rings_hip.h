@@ -315,6 +315,49 @@ int sr_mle_round_fold_evals_dev(sr_ctx *ctx, uint64_t *d_out, uint64_t *const *d
                                 int order, uint64_t *d_work, size_t work_elems, void *stream);
 int sr_mle_round_fold_evals(sr_ctx *ctx, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
                             const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, int order);
+/* The round message of a SUM OF PRODUCTS of dense MLEs with ring coefficients in one pass (csrc/sumcheck_vpoly.hpp): HyperPlonk's
+ * VirtualPolynomial, the shape of the claims built on DenseMultilinearExtension -- eq (a b - c), sum_i alpha_i eq prod_j (...).
+ *   g(x) = sum_k c_k prod_{s < terms[k].n_factors} f_{terms[k].table[s]}(x),   d = max_k n_factors (the plan's `degree`)
+ *   SR_MLE_LEADING    d_out[t] = sum_{b < half} sum_k c_k prod_s ( f[2b] + t (f[2b+1] - f[2b]) ),  t = 0 .. d: d + 1 elements
+ *   SR_MLE_TRAILING   the same with the pair (f[b], f[b + half])
+ *   SR_MLE_ROUND_SUM  d_out[0] = sum_b g(b): one element; num_vars = 0 is allowed here only
+ * Everything is in CRT / NTT form, `*` is the slot product of the ring, t is R::from(t); every ring id, canonical in and out.  A
+ * table may occur more than once in a term and in any number of terms, and two table slots may hold the same pointer; every distinct
+ * table slot is read once per launch.  d_coeffs: n_terms contiguous ring elements on the device, or NULL for one() everywhere (no
+ * coefficient product is computed).  terms, d_tables and n_evals are HOST arrays, consumed at call time: a captured graph holds no
+ * host pointer.
+ *
+ * Truncated storage, per term: an element beyond the stored part of a table is zero and is never loaded; a pair contributes to a
+ * term only while its first element lies inside every table of that term, so the pass ends at the longest term.  A term with an empty
+ * table contributes nothing; if every term has one, a single launch zeroes d_out and loads nothing.
+ *
+ * All arithmetic is exact on canonical values: the output depends on neither the grid, the split nor the association of the sums,
+ * and one term with d_coeffs == NULL gives sr_mle_round_evals_dev's output bit for bit.  The call allocates nothing and touches no
+ * context scratch; partial results live in d_work, every word of which is written before it is read; the launches form one chain on
+ * one stream, so the call is capturable on a fresh context.  The points go in several launches where d + 1 lazy sums do not fit the
+ * registers beside the tables (the plan reports them); each launch reads the tables once.
+ *
+ * sr_vpoly_round_plan is pure host arithmetic on the shape (no device, no context): *work_elems == 0 exactly when *launches == 1,
+ * *work_elems <= SR_MLE_ROUND_MAX_GROUPS * (degree + 1); the records are those of sr_mle_round_plan.  `degree` must be the largest
+ * n_factors of the call.  SR_E_INVALID (nothing launched, the reason in sr_last_error): a null pointer; n_tables outside 1 ..
+ * SR_VPOLY_MAX_TABLES; n_terms outside 1 .. SR_VPOLY_MAX_TERMS; n_factors outside 1 .. SR_VPOLY_MAX_FACTORS; a table index outside
+ * 0 .. n_tables - 1; a table no term uses; an unknown mode; num_vars >= 48, or 0 in a round mode; n_evals[j] > 2^num_vars; a
+ * workspace below the plan's; d_out, d_work or d_coeffs overlapping a table or each other.
+ * The host-pointer form stages whole tables through context-owned temporaries, as sr_mle_round_evals does. */
+#define SR_VPOLY_MAX_TABLES 8
+#define SR_VPOLY_MAX_TERMS 8
+#define SR_VPOLY_MAX_FACTORS 4
+typedef struct {
+    int n_factors;
+    int table[SR_VPOLY_MAX_FACTORS];
+} sr_vpoly_term;
+int sr_vpoly_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int mode, size_t *work_elems,
+                        int *launches);
+int sr_vpoly_round_evals_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *const *d_tables, const size_t *n_evals, int n_tables,
+                             const sr_vpoly_term *terms, int n_terms, const uint64_t *d_coeffs, size_t num_vars, int mode, uint64_t *d_work,
+                             size_t work_elems, void *stream);
+int sr_vpoly_round_evals(sr_ctx *ctx, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                         const sr_vpoly_term *terms, int n_terms, const uint64_t *coeffs, size_t num_vars, int mode);
 /* Sparse multilinear extensions: the arithmetic of crates/poly's SparseMultilinearExtension (mle/sparse.rs) on device-resident
  * values.  Elements are ring elements in CRT / NTT form in the usual flat layout, canonical in and canonical out, for every ring id.
  *

@@ -7,7 +7,7 @@ Layout:
                         Flatten at batch granularity) on top of the C ABI
   wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix / SymmetricMatrix around the device codec
   mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values,
-                        with the round message of a sum-check over a product of dense MLEs
+                        with the round message of a sum-check over a product, or a sum of products (VirtualPolynomial), of dense MLEs
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
   sparse.py             SparseMatrix of crates/linear_algebra with device-resident values: transpose, sparse x sparse product
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
@@ -25,6 +25,6 @@ from .rings import (  # noqa: F401
     CyclotomicRing,
     RingError,
 )
-from .mle import DenseMultilinearExtension, SparseMultilinearExtension  # noqa: F401
+from .mle import DenseMultilinearExtension, SparseMultilinearExtension, VirtualPolynomial  # noqa: F401
 from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401
 from .sparse import SparseMatrixNTT  # noqa: F401

@@ -53,6 +53,12 @@ SYMBOLS = {
                                                _c.c_size_t, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sr_mle_round_fold_evals": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, u64p,
                                            _c.c_int]),
+    "sr_vpoly_round_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t),
+                                       _c.POINTER(_c.c_int)]),
+    "sr_vpoly_round_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                            _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_vpoly_round_evals": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                        _c.c_int]),
     "sr_eq_table_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sr_eq_table": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t]),
     "sr_smle_fix_pattern": (_c.c_int, [u64p, _c.c_size_t, _c.c_size_t, _c.c_size_t, u64p, u64p, _c.POINTER(_c.c_size_t)]),
@@ -141,6 +147,13 @@ SYMBOLS = {
     "sr_version": (_c.c_char_p, []),
 }
 
+
+VPOLY_MAX_TABLES, VPOLY_MAX_TERMS, VPOLY_MAX_FACTORS = 8, 8, 4
+
+
+class VPolyTerm(ctypes.Structure):
+    """sr_vpoly_term of include/stark_rings_hip.h: one product of a sum of products, as indices into the call's table slots."""
+    _fields_ = [("n_factors", _c.c_int), ("table", _c.c_int * VPOLY_MAX_FACTORS)]
 
 
 class Plan(ctypes.Structure):

@@ -35,6 +35,7 @@
 #include "sparse_matrix.hpp"
 #include "sumcheck.hpp"
 #include "sumcheck_fold.hpp"
+#include "sumcheck_vpoly.hpp"
 
 namespace {
 
@@ -1635,6 +1636,84 @@ int check_mle_round(sr_ctx *c, const void *out, const uint64_t *const *tables, c
     return SR_OK;
 }
 
+// ---- sum-check round messages of a sum of products (csrc/sumcheck_vpoly.hpp): every launch under K_POINTWISE, nothing allocated -------
+int dev_vpoly_round(sr_ctx *c, const sr::vpoly::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
+                    int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, uint64_t *work, hipStream_t st) {
+    namespace vp = sr::vpoly;
+    ProfScope ps(c, st, K_POINTWISE);
+    vp::Tables tb{};
+    vp::Term tm[SR_VPOLY_MAX_TERMS];
+    uintptr_t bits = (uintptr_t)out | (uintptr_t)coef | (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int j = 0; j < n_tables; j++) {
+        tb.p[j] = tables[j];
+        tb.n[j] = n_evals[j];
+        bits |= (uintptr_t)tables[j];
+    }
+    for (int k = 0; k < n_terms; k++) {
+        tm[k].n_factors = terms[k].n_factors;
+        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
+    }
+    const bool al = (bits & 15u) == 0;
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2:
+            e = vp::launch<sr::Goldilocks>(p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, c->k, al, work, st);
+            break;
+        case SR_RING_BABYBEAR_POW2:
+            e = vp::launch<sr::BabyBear>(p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, c->k, al, work, st);
+            break;
+        case SR_RING_STARK_POW2: e = vp::launch<sr::Stark>(p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, c->k, al, work, st); break;
+        case SR_RING_GOLDILOCKS_24:
+            e = vp::launch_slot<sr::SlotG24>(c->small, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, work, st);
+            break;
+        case SR_RING_BABYBEAR_72:
+            e = vp::launch_slot<sr::SlotB72>(c->small, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, work, st);
+            break;
+        default: e = vp::launch_slot<sr::SlotFrog>(c->frog, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, work, st); break;
+    }
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("vpoly round launch: ") + hipGetErrorString(e));
+}
+// the shape checks sr_vpoly_round_plan and the two forms of sr_vpoly_round_evals share
+int vpoly_plan_for(int ring, int k, size_t num_vars, int n_tables, int n_terms, int degree, int mode, sr::vpoly::Plan *p) {
+    if (n_tables < 1 || n_tables > SR_VPOLY_MAX_TABLES) return fail(SR_E_INVALID, "vpoly_round: n_tables must be 1 .. 8");
+    if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return fail(SR_E_INVALID, "vpoly_round: n_terms must be 1 .. 8");
+    if (degree < 1 || degree > SR_VPOLY_MAX_FACTORS) return fail(SR_E_INVALID, "vpoly_round: degree (the largest n_factors) must be 1 .. 4");
+    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && mode != SR_MLE_ROUND_SUM) return fail(SR_E_INVALID, "vpoly_round: unknown mode");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "vpoly_round: num_vars must be below 48");
+    if (num_vars == 0 && mode != SR_MLE_ROUND_SUM)
+        return fail(SR_E_INVALID, "vpoly_round: a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
+    if (!sr::vpoly::plan(ring, k, num_vars, n_tables, degree, mode, p)) return fail(SR_E_INVALID, "vpoly_round: no plan for these arguments");
+    return SR_OK;
+}
+// the argument checks the two forms of sr_vpoly_round_evals share
+int check_vpoly_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
+                      int n_terms, size_t num_vars, int mode, sr::vpoly::Plan *p) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!out || !tables || !n_evals || !terms) return fail(SR_E_INVALID, "vpoly_round: null pointer");
+    if (n_tables < 1 || n_tables > SR_VPOLY_MAX_TABLES) return fail(SR_E_INVALID, "vpoly_round: n_tables must be 1 .. 8");
+    if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return fail(SR_E_INVALID, "vpoly_round: n_terms must be 1 .. 8");
+    int degree = 0;
+    unsigned used = 0;
+    for (int k = 0; k < n_terms; k++) {
+        if (terms[k].n_factors < 1 || terms[k].n_factors > SR_VPOLY_MAX_FACTORS)
+            return fail(SR_E_INVALID, "vpoly_round: n_factors must be 1 .. 4 (term " + std::to_string(k) + ")");
+        degree = terms[k].n_factors > degree ? terms[k].n_factors : degree;
+        for (int s = 0; s < terms[k].n_factors; s++) {
+            if (terms[k].table[s] < 0 || terms[k].table[s] >= n_tables)
+                return fail(SR_E_INVALID, "vpoly_round: table index outside 0 .. n_tables - 1 (term " + std::to_string(k) + ")");
+            used |= 1u << terms[k].table[s];
+        }
+    }
+    if (used != (1u << n_tables) - 1) return fail(SR_E_INVALID, "vpoly_round: a table that no term uses");
+    if (int rc = vpoly_plan_for(c->ring, c->k, num_vars, n_tables, n_terms, degree, mode, p)) return rc;
+    for (int j = 0; j < n_tables; j++) {
+        if (n_evals[j] > (size_t)1 << num_vars) return fail(SR_E_INVALID, "vpoly_round: n_evals exceeds 2^num_vars");
+        if (n_evals[j] && !tables[j]) return fail(SR_E_INVALID, "vpoly_round: null pointer (a table)");
+        if (int rc = check_count(c, n_evals[j])) return rc;
+    }
+    return SR_OK;
+}
+
 // ---- fold at the challenge and the next round's message in one pass (csrc/sumcheck_fold.hpp): every launch under K_POINTWISE ---------
 int dev_mle_round_fold(sr_ctx *c, const sr::sumcheck_fold::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
                        const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, uint64_t *work,
@@ -2515,6 +2594,70 @@ int sr_mle_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, 
         if (n_evals[j]) HIP_TRY(hipMemcpyAsync((void *)dt[j], tables[j], n_evals[j] * w, hipMemcpyHostToDevice, c->stream));
     }
     if (int rc = dev_mle_round(c, p, mode, (uint64_t *)c->buf[HOST_1], dt, n_evals, n_tables, num_vars, (uint64_t *)c->buf[HOST_2], c->stream)) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], p.np_total * w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SR_OK;
+}
+int sr_vpoly_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int mode, size_t *work_elems,
+                        int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "vpoly_round_plan: null result pointer");
+    sr::vpoly::Plan p;
+    if (int rc = vpoly_plan_for(ring, log2_degree, num_vars, n_tables, n_terms, degree, mode, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_vpoly_round_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                             const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int mode, uint64_t *work,
+                             size_t work_elems, void *stream) {
+    sr::vpoly::Plan p;
+    if (int rc = check_vpoly_round(c, out, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, &p)) return rc;
+    if (p.work_elems && !work) return fail(SR_E_INVALID, "vpoly_round: null pointer (d_work)");
+    if (work_elems < p.work_elems)
+        return fail(SR_E_INVALID, "vpoly_round: workspace too small (sr_vpoly_round_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const size_t cw = coef ? n_terms * w : 0;
+    for (int j = 0; j < n_tables; j++) {
+        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "vpoly_round: d_out overlaps a table");
+        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "vpoly_round: d_work overlaps a table");
+        if (ranges_overlap(coef, cw, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "vpoly_round: d_coeffs overlaps a table");
+    }
+    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "vpoly_round: d_out overlaps d_work");
+    if (ranges_overlap(out, p.np_total * w, coef, cw)) return fail(SR_E_INVALID, "vpoly_round: d_out overlaps d_coeffs");
+    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return fail(SR_E_INVALID, "vpoly_round: d_work overlaps d_coeffs");
+    const Call call(c, stream);
+    return dev_vpoly_round(c, p, mode, out, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, work, call.st);
+}
+int sr_vpoly_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
+                         int n_terms, const uint64_t *coef, size_t num_vars, int mode) {
+    sr::vpoly::Plan p;
+    if (int rc = check_vpoly_round(c, out, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, &p)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    // HOST_0: the tables one behind the other, each on a 16-byte boundary; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients
+    size_t off[SR_VPOLY_MAX_TABLES], total = 0;
+    for (int j = 0; j < n_tables; j++) {
+        off[j] = total;
+        total += (n_evals[j] * w + 15) & ~(size_t)15;
+    }
+    if (int rc = grow(c, HOST_0, total)) return rc;
+    if (int rc = grow(c, HOST_1, p.np_total * w)) return rc;
+    if (int rc = grow(c, HOST_2, p.work_elems * w)) return rc;
+    if (coef)
+        if (int rc = grow(c, HOST_3, n_terms * w)) return rc;
+    const uint64_t *dt[SR_VPOLY_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) {
+        dt[j] = (const uint64_t *)((char *)c->buf[HOST_0] + off[j]);
+        if (n_evals[j]) HIP_TRY(hipMemcpyAsync((void *)dt[j], tables[j], n_evals[j] * w, hipMemcpyHostToDevice, c->stream));
+    }
+    if (coef) HIP_TRY(hipMemcpyAsync(c->buf[HOST_3], coef, n_terms * w, hipMemcpyHostToDevice, c->stream));
+    if (int rc = dev_vpoly_round(c, p, mode, (uint64_t *)c->buf[HOST_1], dt, n_evals, n_tables, terms, n_terms,
+                                 coef ? (const uint64_t *)c->buf[HOST_3] : nullptr, num_vars, (uint64_t *)c->buf[HOST_2], c->stream)) {
         (void)hipStreamSynchronize(c->stream);
         return rc;
     }

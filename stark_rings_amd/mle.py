@@ -1,5 +1,5 @@
-"""DenseMultilinearExtension (src/mle/dense.rs) and, at the end of the file, SparseMultilinearExtension (src/mle/sparse.rs) of
-crates/poly.  The dense class: DenseMultilinearExtension (src/mle/dense.rs) over a device-resident table of ring elements in CRT/NTT form.
+"""DenseMultilinearExtension (src/mle/dense.rs), VirtualPolynomial (a sum of products of dense MLEs, after HyperPlonk's) and, at the
+end of the file, SparseMultilinearExtension (src/mle/sparse.rs) of crates/poly.  The dense class: DenseMultilinearExtension (src/mle/dense.rs) over a device-resident table of ring elements in CRT/NTT form.
 
 The evaluations live in one torch CUDA tensor of 8-byte integers in the flat layout of every other call (element-major, D
 coefficients per element, N u64 limbs each, Montgomery residues).  Like the reference's constructor (dense.rs:35-54) the object may
@@ -173,6 +173,126 @@ class DenseMultilinearExtension:
         out = torch.zeros(full, dtype=self.evaluations.dtype, device=self.evaluations.device)
         out[:self.evaluations.numel()] = self.evaluations
         return out
+
+
+class VirtualPolynomial:
+    """A sum of products of dense MLEs with ring coefficients, g = sum_k c_k prod_s f_{k,s}, after HyperPlonk's VirtualPolynomial
+    (the code crates/poly's polynomials/multilinear_polynomial.rs was adapted from): the object a sum-check is run on -- eq (a b - c),
+    sum_i alpha_i eq prod_j (...).  The tables stay where they are; a table that is in several products is held, and read, once
+    (sr_vpoly_round_evals_dev).  At most 8 distinct tables, 8 products, 4 factors per product."""
+
+    MAX_TABLES, MAX_TERMS, MAX_FACTORS = 8, 8, 4
+
+    def __init__(self, ring, num_vars):
+        self.ring = ring
+        self._num_vars = int(num_vars)
+        self.tables = []   # the distinct MLEs, in the order they were first added: the table slots of the call
+        self.terms = []    # per product: the list of its table slots
+        self.coeffs = []   # per product: one ring element (a tensor) or None for one()
+        self._slot = {}    # device pointer of a table -> its slot
+
+    @property
+    def num_vars(self):
+        return self._num_vars
+
+    @property
+    def degree(self):
+        """the largest number of factors of a product: a round message has degree + 1 elements"""
+        return max([len(t) for t in self.terms] or [0])
+
+    def _slot_of(self, mle, new):
+        if mle.ring is not self.ring or mle.num_vars != self._num_vars:
+            raise RingError("VirtualPolynomial: every MLE must have the polynomial's ring and num_vars")
+        key = mle.evaluations.data_ptr() if len(mle) else ("empty", id(mle))
+        if key in self._slot:
+            return self._slot[key]
+        if key in new:
+            return new[key][0]
+        if len(self.tables) + len(new) >= self.MAX_TABLES:
+            raise RingError("VirtualPolynomial: more than %d distinct tables" % self.MAX_TABLES)
+        new[key] = (len(self.tables) + len(new), mle)
+        return new[key][0]
+
+    def _commit(self, new):
+        for key, (slot, mle) in sorted(new.items(), key=lambda kv: kv[1][0]):
+            self._slot[key] = slot
+            self.tables.append(mle)
+
+    def add_mle_list(self, mles, coeff=None):
+        """g += coeff * prod(mles): 1 .. 4 MLEs (one may appear twice), coeff one ring element (a tensor) or None for one().
+        Tables are deduplicated by device pointer into table slots."""
+        mles = list(mles)
+        if not 1 <= len(mles) <= self.MAX_FACTORS:
+            raise RingError("VirtualPolynomial: a product has 1 .. %d factors" % self.MAX_FACTORS)
+        if len(self.terms) >= self.MAX_TERMS:
+            raise RingError("VirtualPolynomial: more than %d products" % self.MAX_TERMS)
+        if coeff is not None and coeff.numel() != self.ring.words_per_elem:
+            raise RingError("VirtualPolynomial: the coefficient is not one ring element")
+        new = {}
+        term = [self._slot_of(m, new) for m in mles]
+        self._commit(new)
+        self.terms.append(term)
+        self.coeffs.append(coeff)
+        return self
+
+    def mul_by_mle(self, mle):
+        """g *= mle: the MLE becomes one more factor of every product."""
+        if not self.terms:
+            raise RingError("VirtualPolynomial: mul_by_mle on an empty polynomial")
+        if any(len(t) >= self.MAX_FACTORS for t in self.terms):
+            raise RingError("VirtualPolynomial: a product has 1 .. %d factors" % self.MAX_FACTORS)
+        new = {}
+        slot = self._slot_of(mle, new)
+        self._commit(new)
+        for t in self.terms:
+            t.append(slot)
+        return self
+
+    def _coeff_tensor(self, like, stream):
+        """the coefficients as one tensor, or None where every product has none"""
+        import torch
+
+        if all(c is None for c in self.coeffs):
+            return None
+        w = self.ring.words_per_elem
+        out = torch.empty(len(self.coeffs) * w, dtype=like.dtype, device=like.device)
+        for k, c in enumerate(self.coeffs):
+            if c is None:
+                self.ring.eq_table_dev(out[k * w:(k + 1) * w], None, stream)  # the eq table of no variables is the single element one()
+            else:
+                out[k * w:(k + 1) * w] = c
+        return out
+
+    def _call(self, mode, stream):
+        import torch
+
+        if not self.terms:
+            raise RingError("VirtualPolynomial: no product has been added")
+        ring, nv = self.ring, self._num_vars
+        like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
+        w = ring.words_per_elem
+        n_out = 1 if mode == MLE_ROUND_SUM else self.degree + 1
+        out = torch.empty(n_out * w, dtype=like.dtype, device=like.device)
+        need = ring.vpoly_round_plan(nv, len(self.tables), len(self.terms), self.degree, mode)[0]
+        work = torch.empty(need * w, dtype=like.dtype, device=like.device) if need else None
+        coeffs = self._coeff_tensor(like, stream)
+        if stream is not None:
+            for t in (work, coeffs):
+                if t is not None:
+                    t.record_stream(stream)
+        ring.vpoly_round_evals_dev(out, [t.evaluations for t in self.tables], self.terms, coeffs, nv, mode, work, stream)
+        return out
+
+    def round_evals(self, order=MLE_LEADING, stream=None):
+        """The prover's message of one sum-check round over g: the degree + 1 elements p(t) = sum_b g(t, b), t = 0 .. degree, the
+        variable being the one fix_variables (MLE_LEADING) or fix_last_variables (MLE_TRAILING) fixes next."""
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("round_evals: unknown order")
+        return self._call(order, stream)
+
+    def sum(self, stream=None):
+        """sum_b g(b) over the hypercube as one ring element: the claimed sum of the sum-check."""
+        return self._call(MLE_ROUND_SUM, stream)
 
 
 def _next_pow2(n):

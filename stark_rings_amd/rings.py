@@ -959,6 +959,79 @@ class CyclotomicRing:
         self._check(self._lib.sr_mle_round_evals(self._ctx, _np_ptr(out), ptrs, sizes, n, int(num_vars), int(mode)))
         return out
 
+    @staticmethod
+    def _vpoly_terms(terms):
+        """a list of index lists -> (the sr_vpoly_term array, n_terms, the largest factor count); the library checks the limits"""
+        from ._lib import VPOLY_MAX_FACTORS, VPolyTerm
+        arr = (VPolyTerm * max(len(terms), 1))()
+        for k, t in enumerate(terms):
+            t = list(t)
+            arr[k].n_factors = len(t)
+            for s, j in enumerate(t[:VPOLY_MAX_FACTORS]):
+                arr[k].table[s] = int(j)
+        return arr, len(terms), max([len(list(t)) for t in terms] or [0])
+
+    def vpoly_round_plan(self, num_vars, n_tables, n_terms, degree, mode=MLE_LEADING):
+        """sr_vpoly_round_plan: (work_elems, launches) of a round message over a sum of n_terms products of at most `degree` of
+        n_tables tables -- host arithmetic only."""
+        work = ctypes.c_size_t()
+        launches = ctypes.c_int()
+        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
+        self._check(self._lib.sr_vpoly_round_plan(self.ring, k, int(num_vars), int(n_tables), int(n_terms), int(degree), int(mode),
+                                                  ctypes.byref(work), ctypes.byref(launches)))
+        return work.value, launches.value
+
+    def vpoly_round_evals_dev(self, out, tables, terms, coeffs, num_vars, mode=MLE_LEADING, work=None, stream=None):
+        """sr_vpoly_round_evals_dev: the prover's message of a sum-check round over g = sum_k c_k prod_s f_{terms[k][s]} in one pass
+        that reads every table once.  tables: 1 .. 8 CUDA tensors (n_evals <= 2^num_vars elements each, the rest zero); terms: 1 .. 8
+        lists of 1 .. 4 indices into `tables`; coeffs: a CUDA tensor of len(terms) ring elements, or None for one() everywhere.
+        MLE_LEADING / MLE_TRAILING: out[t] for t = 0 .. d, d the longest term; MLE_ROUND_SUM: out = sum_b g(b), one element.  work: a
+        tensor of at least vpoly_round_plan()[0] elements (None only where the plan needs none).  Allocates nothing."""
+        po, no = self._dev(out)
+        n = len(tables)
+        arr, n_terms, d = self._vpoly_terms(terms)
+        if no != self.words_per_elem * (1 if mode == MLE_ROUND_SUM else d + 1):
+            raise RingError("vpoly_round_evals: out must hold d + 1 elements, d the longest term (one for MLE_ROUND_SUM)")
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.numel())
+            ptrs[j] = self._dev(t)[0] if t.numel() else None
+        if coeffs is None:
+            pc = ctypes.c_void_p(0)
+        else:
+            pc, nc = self._dev(coeffs)
+            if nc != n_terms * self.words_per_elem:
+                raise RingError("vpoly_round_evals: one coefficient per term")
+        if work is None:
+            pw, nw = ctypes.c_void_p(0), 0
+        else:
+            pw, nw = self._dev(work)
+            nw //= self.words_per_elem
+        self._check(self._lib.sr_vpoly_round_evals_dev(self._ctx, po, ptrs, sizes, n, arr, n_terms, pc, int(num_vars), int(mode), pw, nw,
+                                                       self._stream(stream)))
+        return out
+
+    def vpoly_round_evals(self, tables, terms, coeffs, num_vars, mode=MLE_LEADING):
+        """Host buffers: sr_vpoly_round_evals (see vpoly_round_evals_dev); returns the d + 1 elements (one for MLE_ROUND_SUM)."""
+        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+        n = len(tables)
+        arr, n_terms, d = self._vpoly_terms(terms)
+        out = np.empty(self.words_per_elem * (1 if mode == MLE_ROUND_SUM else max(d, 1) + 1), dtype=np.uint64)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.size)
+            ptrs[j] = t.ctypes.data if t.size else None
+        pc = None
+        if coeffs is not None:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+            if coeffs.size != n_terms * self.words_per_elem:
+                raise RingError("vpoly_round_evals: one coefficient per term")
+            pc = coeffs.ctypes.data
+        self._check(self._lib.sr_vpoly_round_evals(self._ctx, _np_ptr(out), ptrs, sizes, n, arr, n_terms, pc, int(num_vars), int(mode)))
+        return out
+
     def mle_round_fold_plan(self, num_vars, n_tables, order=MLE_LEADING):
         """sr_mle_round_fold_plan: (work_elems, launches) of the fused fold-and-round call over n_tables tables of num_vars >= 2
         variables -- host arithmetic only."""

@@ -1,0 +1,19 @@
+// The sum-of-products round kernels alone (stark_rings_amd/csrc/sumcheck_vpoly.hpp), so that `hipcc -S` takes minutes rather than the
+// whole library: tests/test_vpoly_isa.py reads the listing.  The launchers themselves are instantiated, so the listing holds exactly
+// the kernels the dispatcher can reach -- every (field, table slots, round / plain sum) -- and nothing it cannot.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o vpoly.s tools/ubench/vpoly_isa.hip
+#include "../../stark_rings_amd/csrc/stark_lazy.hpp"
+#include "../../stark_rings_amd/csrc/sumcheck_vpoly.hpp"
+using namespace sr;
+#define POW2(F)                                                                                                                            \
+    template hipError_t vpoly::launch<F>(const vpoly::Plan &, int, uint64_t *, const vpoly::Tables &, int, const vpoly::Term *, int, const uint64_t *, \
+                                         size_t, const size_t *, int, bool, uint64_t *, hipStream_t);
+POW2(Goldilocks)
+POW2(BabyBear)
+POW2(Stark)
+#define SLOT(SL)                                                                                                                          \
+    template hipError_t vpoly::launch_slot<SL>(const SL::K &, const vpoly::Plan &, int, uint64_t *, const vpoly::Tables &, int, const vpoly::Term *, \
+                                               int, const uint64_t *, size_t, const size_t *, uint64_t *, hipStream_t);
+SLOT(SlotG24)
+SLOT(SlotB72)
+SLOT(SlotFrog)
