@@ -695,8 +695,9 @@ __global__ __launch_bounds__(16 << LC, 4) void cols256_pair_kernel(u64 *data_a, 
 // tile (one 8-byte L2 read per coefficient and pass otherwise: 26 GB per config-2 batch that no HBM counter shows), and the
 // 256-entry W table sits in 2 KiB of LDS.  Compiled for four workgroups per CU (a 128-VGPR budget) the scheduler trades registers
 // for spills (48-84 bytes; the round-4 harness lost 11 %); compiled for THREE (__launch_bounds__(256, 3): up to 168) the allocator
-// ends at 120 / 126 VGPRs with nothing spilled -- which the hardware still packs four to a CU (tests/test_isa_budget.py holds it
-// there).  Alone on the chip the kernel is slower than cols256_kernel (3.65 against 3.27 ms per config-2 batch on one stream: one
+// ends at 100 / 102 VGPRs with nothing spilled (120 / 126 before the addresses moved to the scalar side and the exchange to
+// immediate offsets) -- which the hardware still packs four to a CU (tests/test_isa_budget.py, tests/test_cols_keep_isa.py hold
+// it there).  Alone on the chip the kernel is slower than cols256_kernel (3.65 against 3.27 ms per config-2 batch on one stream: one
 // more barrier per tile, no fresh workgroup overlapping the old one's tail); beside the other lane's kernels it is faster -- 14.9-15.05
 // against 15.55 ms per batch in the harness, 14.96-15.08 against 15.64-15.70 ms through the library (tools/bench_keep_cols.py,
 // DESIGN.md 6) -- so only the lane plans use it; the one-stream plan keeps cols256_kernel.
@@ -707,73 +708,114 @@ __global__ __launch_bounds__(16 << LC, 4) void cols256_pair_kernel(u64 *data_a, 
 // data2 / src2 != nullptr: the forward pass of a SECOND operand (b of a ring product) in the same launch, walked over behind the first
 // by the same workgroups with the same factors: one launch boundary per lane chunk fewer (-1.1 % on the config-2 step).
 // ------------------------------------------------------------------------------------------------
+// D = 2^16 at compile time (the launch helpers refuse every other degree; k is ignored): N2 = 256, a leg is 2 KiB, 16 column chunks.
+// Global addresses: every access of a run of 16 is a wave-uniform pointer, formed on the scalar side from the ring element's base
+// plus a constant, and ONE 32-bit lane offset shared by the whole run -- the scalar-base form of global_load / global_store with an
+// unchanged offset register, no VALU add per access.  The offA run strides 16 legs (32 KiB): one scalar base per access.  The offB
+// run strides one leg: a base biased by two legs reaches four consecutive legs through the instruction's signed 13-bit immediate.
+// Order inside a launch: the first element's coefficient loads are issued AHEAD of the table and twist-factor loads (vmcnt retires
+// in issue order, so the first network waits for the coefficients alone), the wl[] store sits in front of the first barrier, and
+// the "tile free" barrier of an iteration stands just in front of its exchange writes: a wave that has stored its results goes
+// straight on to the next element's loads and first network while its siblings finish.
+constexpr long kKeepLeg = 2048;  // bytes between consecutive legs at D = 2^16
+// The empty statement pins the wave-uniform pointer in a scalar register pair: without it the constant is reassociated behind the lane
+// offset and the sum goes back to the vector pipe.  It goes through an integer, so the pointer is given its address space back by hand.
+typedef __attribute__((address_space(1))) char *keep_gptr;
+typedef __attribute__((address_space(1))) u64 *keep_gword;
+__device__ __forceinline__ keep_gptr keep_scalar(const char *base) {
+    u64 b = reinterpret_cast<u64>(base);
+    asm("" : "+s"(b));
+    return (keep_gptr)b;
+}
+__device__ __forceinline__ keep_gword keep_ptr_a(const char *base, unsigned off, int jj) {  // leg rg + 16 jj (jj a constant)
+    return (keep_gword)(keep_scalar(base + jj * 16 * kKeepLeg) + off);
+}
+__device__ __forceinline__ keep_gword keep_ptr_b(const char *base, unsigned off, int sg) {  // leg 16 rg + sg (sg a constant)
+    return (keep_gword)((keep_scalar(base + ((sg >> 2) * 4 + 2) * kKeepLeg) + off) + ((sg & 3) - 2) * kKeepLeg);
+}
 template <int DIR>
-__global__ __launch_bounds__(256, 3) void cols256_keep_kernel(u64 *data, const u64 *src, u64 *data2, const u64 *src2, int k,
+__global__ __launch_bounds__(256, 3) void cols256_keep_kernel(u64 *data, const u64 *src, u64 *data2, const u64 *src2, int /* k = 16 */,
                                                               const u64 *__restrict__ wc, const u64 *__restrict__ twist, unsigned npoly,
                                                               unsigned groups) {
     using CT = ColsTile<4>;
+    constexpr int k = 16, ls = 8;  // log2 D, log2 N2
     __shared__ u64 lds[CT::kElems];
     __shared__ u64 wl[256];
     const int t = threadIdx.x;
-    wl[t] = wc[t];
-    const int ls = k - 8;  // log2 N2
-    const unsigned chunks = 1u << (ls - 4);
     const unsigned xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
-    const unsigned ci = slot & (chunks - 1u), grp = slot >> (ls - 4);
+    const unsigned ci = slot & 15u, grp = slot >> 4;  // 16 column chunks per ring element
     const int col = t & 15, rg = t >> 4;
     const unsigned i = ci * 16u + (unsigned)col;
     const char *tb = reinterpret_cast<const char *>(twist);
-    const unsigned leg = 8u << ls;
     const unsigned offA0 = (((unsigned)rg << ls) + i) * 8u;          // leg rg (+ 16 jj)
     const unsigned offB0 = (((unsigned)rg << (ls + 4)) + i) * 8u;    // leg 16 rg (+ sigma) = final block b
-    u64 x[16], tw[16];
-#pragma unroll
-    for (int sg = 0; sg < 16; sg++) tw[sg] = *reinterpret_cast<const u64 *>(tb + (offB0 + (unsigned)sg * leg));
-    __syncthreads();
+    // CT::idx(leg, col) = 17 leg + col for col < 16: each exchange pattern is one lane address + an immediate per access
+    u64 *const lh = lds + 17 * rg + col;   // [272 h] = leg 16 h + rg
+    u64 *const lj = lds + 272 * rg + col;  // [17 j] = leg 16 rg + j
+    static_assert(CT::kElems == 17 * 256, "padded tile: 17 words per leg");
+    u64 x[16], tw[16], wv = 0;
     // data2 != nullptr: a second operand (the forward passes of a and b of a ring product) in the same launch, behind the first
     const unsigned total = data2 ? 2u * npoly : npoly;
+    bool first = true;
     for (unsigned it = xcd + 8u * grp; it < total; it += 8u * groups) {  // uniform per workgroup: every lane reaches every barrier
         const bool second = it >= npoly;
         const unsigned poly = second ? it - npoly : it;
         char *pb = reinterpret_cast<char *>((second ? data2 : data) + ((size_t)poly << k));
         const char *ps = reinterpret_cast<const char *>((second ? src2 : src) + ((size_t)poly << k));
-        // opaque per iteration: otherwise the 32 per-access offsets are hoisted out of the loop as invariants and live across it
+        // opaque per iteration: otherwise address arithmetic on the two lane offsets is hoisted out of the loop and lives across it
         unsigned offA = offA0, offB = offB0;
         asm volatile("" : "+v"(offA), "+v"(offB));
         if (DIR == 0) {
 #pragma unroll
-            for (int jj = 0; jj < 16; jj++) x[jj] = ld_stream(reinterpret_cast<const u64 *>(ps + (offA + (unsigned)jj * 16u * leg)));
+            for (int jj = 0; jj < 16; jj++) x[jj] = __builtin_nontemporal_load(keep_ptr_a(ps, offA, jj));  // operands: as ld_stream
+            if (first) {  // behind the coefficient loads: pass A starts before the tables are in
+                wv = wc[t];
+    #pragma unroll
+            for (int sg = 0; sg < 16; sg++) tw[sg] = *keep_ptr_b(tb, offB, sg);
+            }
             cols_stage_fwd<0>(x);
             cols_stage_fwd<1>(x);
             cols_stage_fwd<2>(x);
             cols_stage_fwd<3>(x);
+            if (first) {
+                wl[t] = wv;
+                __syncthreads();
+            }
 #pragma unroll
             for (int h = 0; h < 16; h++) {
                 x[h] = G::mul(x[h], wl[h * 16 + rg]);
                 if ((h & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // keeps the 16 table reads from all being hoisted in front
             }
+            if (!first) __syncthreads();  // every lane has read the previous ring element's exchange before these writes land
 #pragma unroll
-            for (int h = 0; h < 16; h++) lds[CT::idx(16 * h + rg, col)] = x[h];
+            for (int h = 0; h < 16; h++) lh[272 * h] = x[h];
             __syncthreads();
 #pragma unroll
-            for (int j = 0; j < 16; j++) x[j] = lds[CT::idx(16 * rg + j, col)];
+            for (int j = 0; j < 16; j++) x[j] = lj[17 * j];
             dft16_fwd_hot(x);
 #pragma unroll
-            for (int sg = 0; sg < 16; sg++) st_scratch(reinterpret_cast<u64 *>(pb + (offB + (unsigned)sg * leg)), G::mul(x[sg], tw[sg]));
+            for (int sg = 0; sg < 16; sg++) *keep_ptr_b(pb, offB, sg) = G::mul(x[sg], tw[sg]);  // as st_scratch
         } else {
 #pragma unroll
-            for (int sg = 0; sg < 16; sg++) x[sg] = ld_scratch(reinterpret_cast<const u64 *>(ps + (offB + (unsigned)sg * leg)));
+            for (int sg = 0; sg < 16; sg++) x[sg] = *keep_ptr_b(ps, offB, sg);  // as ld_scratch
+            if (first) {
+                wv = wc[t];
+    #pragma unroll
+            for (int sg = 0; sg < 16; sg++) tw[sg] = *keep_ptr_b(tb, offB, sg);
+            }
 #pragma unroll
             for (int sg = 0; sg < 16; sg++) {
                 x[sg] = G::mul(x[sg], tw[sg]);
                 if ((sg & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             }
             dft16_inv_hot(x);
+            if (first) wl[t] = wv;   // read behind the "tile full" barrier below
+            else __syncthreads();    // every lane has read the previous ring element's exchange before these writes land
 #pragma unroll
-            for (int j = 0; j < 16; j++) lds[CT::idx(16 * rg + j, col)] = x[j];
+            for (int j = 0; j < 16; j++) lj[17 * j] = x[j];
             __syncthreads();
 #pragma unroll
-            for (int h = 0; h < 16; h++) x[h] = lds[CT::idx(16 * h + rg, col)];
+            for (int h = 0; h < 16; h++) x[h] = lh[272 * h];
 #pragma unroll
             for (int h = 0; h < 16; h++) {
                 x[h] = G::mul(x[h], wl[h * 16 + rg]);
@@ -784,9 +826,12 @@ __global__ __launch_bounds__(256, 3) void cols256_keep_kernel(u64 *data, const u
             cols_stage_inv<1>(x);
             cols_stage_inv<0>(x);
 #pragma unroll
-            for (int jj = 0; jj < 16; jj++) st_result(reinterpret_cast<u64 *>(pb + (offA + (unsigned)jj * 16u * leg)), x[jj]);
+            for (int jj = 0; jj < 16; jj++) {  // as st_result
+                repcheck::leaves_library(x[jj]);
+                __builtin_nontemporal_store(x[jj], keep_ptr_a(pb, offA, jj));
+            }
         }
-        __syncthreads();  // every lane has read the exchange before the next ring element's writes land
+        first = false;
     }
 }
 
@@ -1033,21 +1078,31 @@ __device__ __forceinline__ void tile256_inv(u64 *x, const Wave256 &W, const int 
 #pragma unroll
     for (int j = 0; j < 16; j++) st_scratch(dst + base2 + j * 16, x[j]);
 }
-// xw: kWaveWords 32-bit words per wave of the workgroup
+// xw: kWaveWords 32-bit words per wave of the workgroup; wl: 512 words for the two table layers, copied here (see rows256_kernel)
 template <int MODE>
-__device__ __forceinline__ void rows256_tile(const unsigned tile, u64 *a, const u64 *b, u64 *out, const Tables &T, unsigned *xw) {
+__device__ __forceinline__ void rows256_tile(const unsigned tile, u64 *a, const u64 *b, u64 *out, Tables T, unsigned *xw, u64 *wl) {
     const int t = threadIdx.x;
     const size_t base = (size_t)tile * kTile;
     const Wave256 W(xw, t);
     u64 A[16];
+    // the first tile loads go out ahead of the table copy and its barrier: one memory round trip per launch wave instead of two
     if (MODE == 1) {
         // the inverse starts from 16 consecutive slots per lane: the wave loads its 1 024 slots lane-contiguous (512-byte
         // segments), one exchange
 #pragma unroll
         for (int j = 0; j < 16; j++) A[j] = a[base + W.gpos + j * 64];
+    } else {
+        tile256_load(a + base, t, A);
+    }
+    wl[t] = T.w2f[t];
+    wl[256 + t] = T.w2i[t];
+    __syncthreads();
+    T.w2f = wl;
+    T.w2i = wl + 256;
+    if (MODE == 1) {
         wave256_exchange<68, 1>(W.coalesced, W.own, A);
     } else {
-        tile256_fwd<MODE == 0>(a + base, W, t, T, A);
+        tile256_fwd_regs<MODE == 0>(W, t, T, A);
         if (MODE == 0) {
             wave256_exchange<1, 68>(W.own, W.coalesced, A);
 #pragma unroll
@@ -1070,18 +1125,13 @@ __device__ __forceinline__ void rows256_tile(const unsigned tile, u64 *a, const 
 // The two 256-entry table layers (w2f, w2i: 45 of the fused product's 93 global loads per lane and tile, 24 GB of L2 reads per
 // config-2 batch) are copied into 4 KiB of LDS first (-0.9 % on the two-lane step, 97 instead of 112 VGPRs).  With the per-wave
 // exchange regions that is 21 KiB per workgroup; compiled for FIVE workgroups per CU (512 registers per SIMD lane in granules of 8:
-// <= 96 each; 160 KiB of LDS: <= 32 KiB each; tests/test_rows256_residency.py).  The barrier behind the table copy is the only
-// one: wl[] is shared by the four waves.
+// <= 96 each; 160 KiB of LDS: <= 32 KiB each; tests/test_rows256_residency.py).  The barrier behind the table copy (in rows256_tile,
+// behind the first tile loads) is the only one: wl[] is shared by the four waves.
 template <int MODE>
 __global__ __launch_bounds__(256, 5) void rows256_kernel(u64 *a, const u64 *b, u64 *out, Tables T) {
     __shared__ unsigned xw[4 * kWaveWords];
     __shared__ u64 wl[512];
-    wl[threadIdx.x] = T.w2f[threadIdx.x];
-    wl[256 + threadIdx.x] = T.w2i[threadIdx.x];
-    __syncthreads();
-    T.w2f = wl;
-    T.w2i = wl + 256;
-    rows256_tile<MODE>(blockIdx.x, a, b, out, T, xw);
+    rows256_tile<MODE>(blockIdx.x, a, b, out, T, xw, wl);
 }
 
 
