@@ -20,6 +20,7 @@ import ctypes  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import model_fast_goldilocks as M  # noqa: E402
 from stark_rings_amd import CyclotomicRing, _lib  # noqa: E402
+from crafted_poly_operands import max_limb_images  # noqa: E402
 from test_gpu_parity import _structured_operands, edge_and_random  # noqa: E402
 
 F = O.GOLDILOCKS
@@ -147,22 +148,6 @@ def run_lanes(k, batch):
     print("%-28s clean" % ("D=2^%d x %d on two lanes" % (k, batch)), flush=True)
 
 
-def max_limb_images(d, flavour):
-    """Stark memory images (4 u64 words per coefficient, any canonical value is some element's Montgomery image) whose nine 28-bit
-    limbs are as large as canonical values get: 2^251 - 1 (all limbs 0xfffffff, the top one 2^27 - 1), its negative, and values
-    with every limb's top bits set."""
-    PS = (1 << 251) + 17 * (1 << 192) + 1
-    hi = (1 << 251) - 1
-    vals = {"max": [hi] * d,
-            "alternating": [hi if i & 1 else PS - hi for i in range(d)],
-            "topbits": [(hi - (i * 0x0123456789ABCDEF % (1 << 24)) * sum(1 << (28 * j) for j in range(9))) % PS for i in range(d)]}[flavour]
-    out = np.empty(4 * d, dtype=np.uint64)
-    for i, v in enumerate(vals):
-        for j in range(4):
-            out[4 * i + j] = (v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
-    return out
-
-
 def run_stark(k, env=None):
     """The Stark rings compute in nine signed 28-bit limbs with postponed carries (csrc/stark_lazy.hpp): the invariants are limb bounds
     (no add / sub may leave int32, no product may overflow its 64-bit column accumulator) which the kernels keep by reducing weakly
@@ -271,6 +256,129 @@ def negative_control():
     print("negative control: %d + %d canonical-input violations counted for raw words >= p" % (c1[0], c2[0]), flush=True)
 
 
+# ---- the polynomial and matrix kernels (tests/crafted_poly_driver.py on tests/crafted_poly_operands.py) -------------------------------
+LINALG_RINGS = [("goldilocks", 6), ("goldilocks24", 0), ("frog16", 0), ("babybear", 5), ("babybear72", 0), ("stark", 4)]
+POLY_FAMILIES = ("fold", "round", "fused", "vpoly", "sparse")
+
+
+def _runner(name, k):
+    import torch
+
+    import crafted_poly_driver as D
+
+    def check(group):
+        high = expect_clean("%s %s" % (name, group))
+        print("%-52s clean" % ("%s D=2^%d: %s" % (name, k, group)), flush=True)
+        return high
+
+    run = D.Run(torch, name, k, check)
+    counters()     # building the context uses the same arithmetic: start from zero
+    return run
+
+
+def poly_negative_control(name, k, nv):
+    """the hooks are live in these kernels too: the raw words p and p + 5 (no field element's image) in one table of a call must be
+    counted where the first routine that touches a table word is Goldilocks::add / sub -- the hi - lo of the fold and of the three round
+    kernels, and the accumulator of mul_elem_add.  The eq table (prev * g, then prev - that), the sparse fold, the Gram, recompose and
+    sparse x sparse kernels touch their operands with a Montgomery product first, which takes any 64-bit representative: printed, not asserted.
+    Outputs are not compared: this is arithmetic on non-canonical data, nothing more."""
+    import torch
+
+    import crafted_poly_driver as D
+    import crafted_poly_operands as C
+
+    run = _runner(name, k)
+    o, ring, w = run.o, run.ring, run.o.w
+    raw = O.fill_uniform(F, 0x9E + k, 0, (o.w << nv)).copy()
+    raw[::2] = np.uint64(P)
+    raw[1::4] = np.uint64(P + 5)
+    t_raw = D.dev(torch, raw)
+    good = [D.dev(torch, O.fill_uniform(F, 0x9F + j, 0, (o.w << nv))) for j in range(3)]
+    r = D.dev(torch, O.fill_uniform(F, 0xA1, 0, o.w))
+    seen = {}
+    D.fold_dev(torch, ring, t_raw, nv, r, C.LEADING)
+    torch.cuda.synchronize()
+    seen["dense fold (sub)"] = counters()[0]
+    acc = t_raw[:4 * w].clone()
+    ring.mul_elem_add_dev(acc, good[0][:4 * w], r)
+    torch.cuda.synchronize()
+    seen["mul_elem_add (add)"] = counters()[0]
+    D.round_dev(torch, ring, [good[0], t_raw], nv, C.TRAILING)
+    seen["round message (sub)"] = counters()[0]
+    D.fold_round_dev(torch, ring, [t_raw, good[1]], nv, r, C.LEADING)
+    torch.cuda.synchronize()
+    seen["fused fold and round (sub)"] = counters()[0]
+    D.vp_dev(torch, ring, [good[0], good[1], good[2], t_raw], C.VP.R1CS, None, nv, C.LEADING)
+    seen["sum of products (sub)"] = counters()[0]
+    bad = [key for key, n in seen.items() if n == 0]
+    assert not bad, "%s: the checking build did not count raw words >= p in: %r (%r)" % (name, bad, seen)
+    print("negative control %s: %s" % (name, ", ".join("%s %d" % kv for kv in seen.items())), flush=True)
+    idx = list(range(0, 64, 2))
+    D.smle_fold_dev(torch, ring, t_raw[:len(idx) * w], idx, 10, good[0][:3 * w])
+    unasserted = {"sparse fold": counters()[0]}
+    out = torch.empty(w << 3, dtype=torch.int64, device="cuda")
+    ring.eq_table_dev(out, t_raw[:3 * w])
+    torch.cuda.synchronize()
+    unasserted["eq table"] = counters()[0]
+    D.gram_dev(torch, ring, t_raw[:6 * w], 2, 3)
+    unasserted["Gram"] = counters()[0]
+    D.recompose_dev(torch, ring, t_raw[:3 * w], 1, 2, good[0][:2 * w])
+    unasserted["recompose"] = counters()[0]
+    print("negative control %s, not asserted (the first routine that touches an operand is the Montgomery product mul / mul_boundary, "
+          "which takes any representative): %s" % (name, ", ".join("%s %d" % kv for kv in unasserted.items())), flush=True)
+
+
+def run_poly(cases=None):
+    import crafted_poly_operands as C
+
+    paths = {}
+    for name, k, nv in (cases or C.POLY_CASES):
+        run = _runner(name, k)
+        run.poly(nv)
+        fam = {"goldilocks": "one-limb", "babybear": "one-limb"}.get(name, name)
+        for call, seen in run.paths.items():
+            paths.setdefault((fam, call), set()).update(seen)
+    if cases is None:   # the one-launch and the split path are both taken, per family of rings and of calls
+        for fam in ("one-limb", "stark", "goldilocks24", "babybear72", "frog16"):
+            for call in POLY_FAMILIES:
+                assert {True, False} <= paths[(fam, call)], "%s %s: launch paths taken %r" % (fam, call, paths[(fam, call)])
+        print("launch paths: the single launch and the split path were taken by every family of calls in every family of rings", flush=True)
+    poly_negative_control("goldilocks", 6, 10)
+    poly_negative_control("goldilocks24", 0, 11)
+    for name in ("babybear", "babybear72", "frog16", "stark"):
+        print("negative control %s: none -- the checking build hooks Goldilocks::add / sub / addsub and the Stark limb sums; this "
+              "field's add and sub carry no counter" % name, flush=True)
+
+
+def run_linalg():
+    for name, k in LINALG_RINGS:
+        _runner(name, k).linalg()
+    bound = (1 << 31) - 16
+    for k, nv, n, m in ((4, 6, 5, 41), (12, 3, 3, 41)):
+        run = _runner("stark", k)
+        high = run.stark_max(nv, n, m)
+        c = counters(reset=False)
+        assert c[5] == 0 and c[6] == 0
+        for family, h in high.items():
+            assert h <= bound
+            print("Stark D=2^%d max-limb %-36s largest |limb| in any add / sub %d = 2^31 - %.2f x 2^28" % (k, family + ":", h, ((1 << 31) - h) / (1 << 28)),
+                  flush=True)
+        print("Stark limb high-water mark over the polynomial and matrix kernels at D=2^%d: %d of %d (2^31 - 16)" % (k, max(high.values()), bound),
+              flush=True)
+    import crafted_poly_driver as D
+    import torch
+
+    run = _runner("goldilocks", 6)
+    raw = O.fill_uniform(F, 0x77, 0, 64 * 6).copy()
+    raw[::2] = np.uint64(P)
+    raw[1::4] = np.uint64(P + 5)
+    D.gram_dev(torch, run.ring, D.dev(torch, raw), 2, 3)
+    c = counters()
+    print("negative control linalg: %d canonical-input violations counted for raw words >= p in a Gram matrix (not asserted: the first "
+          "routine that touches an entry is the Montgomery product, which takes any representative; transpose and gather compute nothing)"
+          % c[0], flush=True)
+
+
 def main():
     assert os.environ.get("SR_LIB_PATH", "").endswith("_check.so"), "run with SR_LIB_PATH=<the checking build>"
     which = sys.argv[1:] or ["goldilocks", "stark"]
@@ -288,6 +396,10 @@ def main():
         highs += [run_stark(k, {"SR_ST_WHOLE_MAX": v}) for k, v in ((10, "9"), (12, "12"))]
         run_stark_sums()
         print("Stark limb high-water mark over all plans: %d of %d (2^31 - 16)" % (max(highs), (1 << 31) - 16), flush=True)
+    if "poly" in which:
+        run_poly()
+    if "linalg" in which:
+        run_linalg()
     print("rep_invariants: OK", flush=True)
 
 

@@ -56,3 +56,25 @@ def test_every_stark_plan_keeps_its_limb_bounds():
     over memory images with every limb at its maximum, through every Stark kernel family and the lazily summed matrix products."""
     out = _worker("stark")
     assert out.count(" clean") >= 15 and "Stark limb high-water mark" in out, out[-4000:]
+
+
+@pytest.mark.gpu
+def test_the_polynomial_kernels_keep_their_representative_invariants():
+    """The dense folds, the three round kernels, the sums of products and the sparse multilinear extensions (csrc/mle.hpp, sumcheck*.hpp,
+    sparse_mle.hpp) are built from Goldilocks::add / sub and the lazy sums, whose preconditions no parity test on uniform data can see.
+    tests/crafted_poly_operands.py puts their INTERMEDIATE words on the borders; the worker runs those and the family tests' edge
+    tables through the checking build for the seven shapes at which both launch paths are reached: five groups per ring, all counters
+    zero after each, every output compared with the integer models, and raw words >= p counted where add / sub touch them first."""
+    out = _worker("poly")
+    assert out.count(" clean") == 7 * 5 and out.count("negative control") >= 4, out[-4000:]
+    assert "launch paths: the single launch and the split path were taken" in out, out[-4000:]
+
+
+@pytest.mark.gpu
+def test_the_matrix_kernels_keep_their_invariants_on_max_limb_operands():
+    """Gram, G^T M G, sparse x sparse, gather and transpose on crafted operands (three groups for each of six rings), then every
+    polynomial and matrix call on Stark rings of degree 2^4 and 2^12 with every operand a max-limb image (eight groups each): the
+    limb-bound counters stay zero and the largest |limb| is reported per family."""
+    out = _worker("linalg")
+    assert out.count(" clean") == 6 * 3 + 2 * 8 and "negative control" in out, out[-4000:]
+    assert out.count("largest |limb| in any add / sub") == 2 * 8 and out.count("Stark limb high-water mark") == 2, out[-4000:]
