@@ -1589,184 +1589,178 @@ int check_mle(sr_ctx *c, const void *out, const void *evals, size_t n_evals, siz
     return check_count(c, p.work_elems);
 }
 
-// ---- sum-check round messages (csrc/sumcheck.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch -----------
-int dev_mle_round(sr_ctx *c, const sr::sumcheck::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
-                  int n_tables, size_t num_vars, uint64_t *work, hipStream_t st) {
-    namespace sc = sr::sumcheck;
+// ---- sum-check round messages (csrc/sumcheck.hpp, sumcheck_fold.hpp, sumcheck_vpoly.hpp): every launch under K_POINTWISE, nothing
+// allocated, no context scratch.  The three families share the ring dispatch, the table collector and the argument checks.
+struct RoundFamily {
+    const char *name;  // the prefix of every message
+    int max_tables;
+    bool terms, fold;  // a sum of products (n_terms, degree); a fold as well (an order, no SR_MLE_ROUND_SUM, two variables)
+};
+const RoundFamily kMleRound{"mle_round", SR_MLE_ROUND_MAX_TABLES, false, false}, kVpolyRound{"vpoly_round", SR_VPOLY_MAX_TABLES, true, false},
+    kMleRoundFold{"mle_round_fold", SR_MLE_ROUND_MAX_TABLES, false, true};
+extern "C++" {
+template <class T> struct FamilyType {
+    using type = T;
+};
+// fn(the family type of the context's ring, its constants) enqueues the launches of a call; `what` opens the message of a failed launch
+template <class Fn>
+int round_dispatch(sr_ctx *c, hipStream_t st, const char *what, Fn fn) {
     ProfScope ps(c, st, K_POINTWISE);
-    sc::Tables tb{};
-    uintptr_t bits = (uintptr_t)out | (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int j = 0; j < n_tables; j++) {
-        tb.p[j] = tables[j];
-        tb.n[j] = n_evals[j];
-        bits |= (uintptr_t)tables[j];
-    }
-    const bool al = (bits & 15u) == 0;
+    const sr::sumcheck::NoConsts none;
     hipError_t e;
     switch (c->ring) {
-        case SR_RING_GOLDILOCKS_POW2: e = sc::launch<sr::Goldilocks>(p, mode, out, tb, n_tables, num_vars, n_evals, c->k, al, work, st); break;
-        case SR_RING_BABYBEAR_POW2: e = sc::launch<sr::BabyBear>(p, mode, out, tb, n_tables, num_vars, n_evals, c->k, al, work, st); break;
-        case SR_RING_STARK_POW2: e = sc::launch<sr::Stark>(p, mode, out, tb, n_tables, num_vars, n_evals, c->k, al, work, st); break;
-        case SR_RING_GOLDILOCKS_24: e = sc::launch_slot<sr::SlotG24>(c->small, p, mode, out, tb, n_tables, num_vars, n_evals, work, st); break;
-        case SR_RING_BABYBEAR_72: e = sc::launch_slot<sr::SlotB72>(c->small, p, mode, out, tb, n_tables, num_vars, n_evals, work, st); break;
-        default: e = sc::launch_slot<sr::SlotFrog>(c->frog, p, mode, out, tb, n_tables, num_vars, n_evals, work, st); break;
+        case SR_RING_GOLDILOCKS_POW2: e = fn(FamilyType<sr::Goldilocks>{}, none); break;
+        case SR_RING_BABYBEAR_POW2: e = fn(FamilyType<sr::BabyBear>{}, none); break;
+        case SR_RING_STARK_POW2: e = fn(FamilyType<sr::Stark>{}, none); break;
+        case SR_RING_GOLDILOCKS_24: e = fn(FamilyType<sr::SlotG24>{}, c->small); break;
+        case SR_RING_BABYBEAR_72: e = fn(FamilyType<sr::SlotB72>{}, c->small); break;
+        default: e = fn(FamilyType<sr::SlotFrog>{}, c->frog); break;
     }
-    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("mle round launch: ") + hipGetErrorString(e));
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
 }
-// the shape checks sr_mle_round_plan and the two forms of sr_mle_round_evals share
-int round_plan_for(int ring, int k, size_t num_vars, int n_tables, int mode, sr::sumcheck::Plan *p) {
-    if (n_tables < 1 || n_tables > SR_MLE_ROUND_MAX_TABLES) return fail(SR_E_INVALID, "mle_round: n_tables must be 1 .. 4");
-    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && mode != SR_MLE_ROUND_SUM) return fail(SR_E_INVALID, "mle_round: unknown mode");
-    if (num_vars >= 48) return fail(SR_E_INVALID, "mle_round: num_vars must be below 48");
-    if (num_vars == 0 && mode != SR_MLE_ROUND_SUM) return fail(SR_E_INVALID, "mle_round: a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
-    if (!sr::sumcheck::plan(ring, k, num_vars, n_tables, mode, p)) return fail(SR_E_INVALID, "mle_round: no plan for these arguments");
+// the tables of a call by value; returns the bits of every table pointer (for the 16-byte alignment test)
+template <class TB>
+uintptr_t collect_tables(TB *tb, const uint64_t *const *tables, const size_t *n_evals, int n_tables) {
+    uintptr_t bits = 0;
+    for (int j = 0; j < n_tables; j++) {
+        tb->p[j] = tables[j];
+        tb->n[j] = n_evals[j];
+        bits |= (uintptr_t)tables[j];
+    }
+    return bits;
+}
+}  // extern "C++"
+int dev_mle_round(sr_ctx *c, const sr::sumcheck::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
+                  int n_tables, size_t num_vars, uint64_t *work, hipStream_t st) {
+    sr::sumcheck::Tables tb{};
+    const uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (p.groups > 1 ? (uintptr_t)work : 0);
+    return round_dispatch(c, st, "mle round", [&](auto t, const auto &kc) {
+        return sr::sumcheck::launch<typename decltype(t)::type>(kc, p, mode, out, tb, n_tables, num_vars, c->k, (bits & 15u) == 0, work, st);
+    });
+}
+int dev_vpoly_round(sr_ctx *c, const sr::vpoly::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
+                    int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, uint64_t *work, hipStream_t st) {
+    sr::vpoly::Tables tb{};
+    sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
+    const uintptr_t bits =
+        collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)coef | (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int k = 0; k < n_terms; k++) {
+        tm[k].n_factors = terms[k].n_factors;
+        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
+    }
+    return round_dispatch(c, st, "vpoly round", [&](auto t, const auto &kc) {
+        return sr::vpoly::launch<typename decltype(t)::type>(kc, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, c->k, (bits & 15u) == 0,
+                                                             work, st);
+    });
+}
+// fold at the challenge and the next round's message in one pass
+int dev_mle_round_fold(sr_ctx *c, const sr::sumcheck_fold::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
+                       const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, uint64_t *work,
+                       hipStream_t st) {
+    sr::sumcheck::Tables tb{};
+    sr::sumcheck_fold::Folded fo{};
+    uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)r | (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int j = 0; j < n_tables; j++) {
+        fo.p[j] = out_tables[j];
+        bits |= (uintptr_t)out_tables[j];
+    }
+    return round_dispatch(c, st, "mle round fold", [&](auto t, const auto &kc) {
+        return sr::sumcheck_fold::launch<typename decltype(t)::type>(kc, p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, (bits & 15u) == 0,
+                                                                     work, st);
+    });
+}
+// a refusal of family f: the message is assembled here, on the failing path only
+int refuse(const RoundFamily &f, const std::string &what) { return fail(SR_E_INVALID, std::string(f.name) + ": " + what); }
+// the shape checks the *_plan call and the two forms of the *_evals call of a family share (n_terms, degree: families with terms)
+int round_plan_for(const RoundFamily &f, int ring, int k, size_t num_vars, int n_tables, int n_terms, int degree, int mode, sr::sumcheck::Plan *p) {
+    if (n_tables < 1 || n_tables > f.max_tables) return refuse(f, "n_tables must be 1 .. " + std::to_string(f.max_tables));
+    if (f.terms) {
+        if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return refuse(f, "n_terms must be 1 .. 8");
+        if (degree < 1 || degree > SR_VPOLY_MAX_FACTORS) return refuse(f, "degree (the largest n_factors) must be 1 .. 4");
+    }
+    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && (f.fold || mode != SR_MLE_ROUND_SUM))
+        return refuse(f, f.fold ? "unknown order" : "unknown mode");
+    if (num_vars >= 48) return refuse(f, "num_vars must be below 48");
+    if (f.fold && num_vars < 2) return refuse(f, "num_vars >= 2 (the folded tables need a variable for the next round)");
+    if (num_vars == 0 && mode != SR_MLE_ROUND_SUM) return refuse(f, "a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
+    const bool ok = f.fold    ? sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, mode, p)
+                    : f.terms ? sr::vpoly::plan(ring, k, num_vars, n_tables, degree, mode, p)
+                              : sr::sumcheck::plan(ring, k, num_vars, n_tables, mode, p);
+    return ok ? (int)SR_OK : refuse(f, "no plan for these arguments");
+}
+// the body of the three *_plan entry points
+int round_plan_entry(const RoundFamily &f, int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int mode,
+                     size_t *work_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!work_elems || !launches) return fail(SR_E_INVALID, std::string(f.name) + "_plan: null result pointer");
+    sr::sumcheck::Plan p;
+    if (int rc = round_plan_for(f, ring, log2_degree, num_vars, n_tables, n_terms, degree, mode, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+// the per-table checks of the three families; out_tables: the fold's outputs, null otherwise
+int check_round_tables(sr_ctx *c, const RoundFamily &f, const uint64_t *const *tables, uint64_t *const *out_tables, const size_t *n_evals,
+                       int n_tables, size_t num_vars) {
+    for (int j = 0; j < n_tables; j++) {
+        if (n_evals[j] > (size_t)1 << num_vars) return refuse(f, "n_evals exceeds 2^num_vars");
+        if (n_evals[j] && (!tables[j] || (out_tables && !out_tables[j]))) return refuse(f, "null pointer (a table)");
+        if (int rc = check_count(c, n_evals[j])) return rc;
+    }
     return SR_OK;
 }
 // the argument checks the two forms of sr_mle_round_evals share
 int check_mle_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, int mode,
                     sr::sumcheck::Plan *p) {
     if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !tables || !n_evals) return fail(SR_E_INVALID, "mle_round: null pointer");
-    if (int rc = round_plan_for(c->ring, c->k, num_vars, n_tables, mode, p)) return rc;
-    for (int j = 0; j < n_tables; j++) {
-        if (n_evals[j] > (size_t)1 << num_vars) return fail(SR_E_INVALID, "mle_round: n_evals exceeds 2^num_vars");
-        if (n_evals[j] && !tables[j]) return fail(SR_E_INVALID, "mle_round: null pointer (a table)");
-        if (int rc = check_count(c, n_evals[j])) return rc;
-    }
-    return SR_OK;
-}
-
-// ---- sum-check round messages of a sum of products (csrc/sumcheck_vpoly.hpp): every launch under K_POINTWISE, nothing allocated -------
-int dev_vpoly_round(sr_ctx *c, const sr::vpoly::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
-                    int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, uint64_t *work, hipStream_t st) {
-    namespace vp = sr::vpoly;
-    ProfScope ps(c, st, K_POINTWISE);
-    vp::Tables tb{};
-    vp::Term tm[SR_VPOLY_MAX_TERMS];
-    uintptr_t bits = (uintptr_t)out | (uintptr_t)coef | (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int j = 0; j < n_tables; j++) {
-        tb.p[j] = tables[j];
-        tb.n[j] = n_evals[j];
-        bits |= (uintptr_t)tables[j];
-    }
-    for (int k = 0; k < n_terms; k++) {
-        tm[k].n_factors = terms[k].n_factors;
-        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
-    }
-    const bool al = (bits & 15u) == 0;
-    hipError_t e;
-    switch (c->ring) {
-        case SR_RING_GOLDILOCKS_POW2:
-            e = vp::launch<sr::Goldilocks>(p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, c->k, al, work, st);
-            break;
-        case SR_RING_BABYBEAR_POW2:
-            e = vp::launch<sr::BabyBear>(p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, c->k, al, work, st);
-            break;
-        case SR_RING_STARK_POW2: e = vp::launch<sr::Stark>(p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, c->k, al, work, st); break;
-        case SR_RING_GOLDILOCKS_24:
-            e = vp::launch_slot<sr::SlotG24>(c->small, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, work, st);
-            break;
-        case SR_RING_BABYBEAR_72:
-            e = vp::launch_slot<sr::SlotB72>(c->small, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, work, st);
-            break;
-        default: e = vp::launch_slot<sr::SlotFrog>(c->frog, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, n_evals, work, st); break;
-    }
-    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("vpoly round launch: ") + hipGetErrorString(e));
-}
-// the shape checks sr_vpoly_round_plan and the two forms of sr_vpoly_round_evals share
-int vpoly_plan_for(int ring, int k, size_t num_vars, int n_tables, int n_terms, int degree, int mode, sr::vpoly::Plan *p) {
-    if (n_tables < 1 || n_tables > SR_VPOLY_MAX_TABLES) return fail(SR_E_INVALID, "vpoly_round: n_tables must be 1 .. 8");
-    if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return fail(SR_E_INVALID, "vpoly_round: n_terms must be 1 .. 8");
-    if (degree < 1 || degree > SR_VPOLY_MAX_FACTORS) return fail(SR_E_INVALID, "vpoly_round: degree (the largest n_factors) must be 1 .. 4");
-    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && mode != SR_MLE_ROUND_SUM) return fail(SR_E_INVALID, "vpoly_round: unknown mode");
-    if (num_vars >= 48) return fail(SR_E_INVALID, "vpoly_round: num_vars must be below 48");
-    if (num_vars == 0 && mode != SR_MLE_ROUND_SUM)
-        return fail(SR_E_INVALID, "vpoly_round: a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
-    if (!sr::vpoly::plan(ring, k, num_vars, n_tables, degree, mode, p)) return fail(SR_E_INVALID, "vpoly_round: no plan for these arguments");
-    return SR_OK;
+    if (!out || !tables || !n_evals) return refuse(kMleRound, "null pointer");
+    if (int rc = round_plan_for(kMleRound, c->ring, c->k, num_vars, n_tables, 0, 0, mode, p)) return rc;
+    return check_round_tables(c, kMleRound, tables, nullptr, n_evals, n_tables, num_vars);
 }
 // the argument checks the two forms of sr_vpoly_round_evals share
 int check_vpoly_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
                       int n_terms, size_t num_vars, int mode, sr::vpoly::Plan *p) {
+    const RoundFamily &f = kVpolyRound;
     if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !tables || !n_evals || !terms) return fail(SR_E_INVALID, "vpoly_round: null pointer");
-    if (n_tables < 1 || n_tables > SR_VPOLY_MAX_TABLES) return fail(SR_E_INVALID, "vpoly_round: n_tables must be 1 .. 8");
-    if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return fail(SR_E_INVALID, "vpoly_round: n_terms must be 1 .. 8");
+    if (!out || !tables || !n_evals || !terms) return refuse(f, "null pointer");
+    if (n_tables < 1 || n_tables > f.max_tables) return refuse(f, "n_tables must be 1 .. " + std::to_string(f.max_tables));
+    if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return refuse(f, "n_terms must be 1 .. 8");
     int degree = 0;
     unsigned used = 0;
     for (int k = 0; k < n_terms; k++) {
         if (terms[k].n_factors < 1 || terms[k].n_factors > SR_VPOLY_MAX_FACTORS)
-            return fail(SR_E_INVALID, "vpoly_round: n_factors must be 1 .. 4 (term " + std::to_string(k) + ")");
+            return refuse(f, "n_factors must be 1 .. 4 (term " + std::to_string(k) + ")");
         degree = terms[k].n_factors > degree ? terms[k].n_factors : degree;
         for (int s = 0; s < terms[k].n_factors; s++) {
             if (terms[k].table[s] < 0 || terms[k].table[s] >= n_tables)
-                return fail(SR_E_INVALID, "vpoly_round: table index outside 0 .. n_tables - 1 (term " + std::to_string(k) + ")");
+                return refuse(f, "table index outside 0 .. n_tables - 1 (term " + std::to_string(k) + ")");
             used |= 1u << terms[k].table[s];
         }
     }
-    if (used != (1u << n_tables) - 1) return fail(SR_E_INVALID, "vpoly_round: a table that no term uses");
-    if (int rc = vpoly_plan_for(c->ring, c->k, num_vars, n_tables, n_terms, degree, mode, p)) return rc;
-    for (int j = 0; j < n_tables; j++) {
-        if (n_evals[j] > (size_t)1 << num_vars) return fail(SR_E_INVALID, "vpoly_round: n_evals exceeds 2^num_vars");
-        if (n_evals[j] && !tables[j]) return fail(SR_E_INVALID, "vpoly_round: null pointer (a table)");
-        if (int rc = check_count(c, n_evals[j])) return rc;
-    }
-    return SR_OK;
+    if (used != (1u << n_tables) - 1) return refuse(f, "a table that no term uses");
+    if (int rc = round_plan_for(f, c->ring, c->k, num_vars, n_tables, n_terms, degree, mode, p)) return rc;
+    return check_round_tables(c, f, tables, nullptr, n_evals, n_tables, num_vars);
 }
-
-// ---- fold at the challenge and the next round's message in one pass (csrc/sumcheck_fold.hpp): every launch under K_POINTWISE ---------
-int dev_mle_round_fold(sr_ctx *c, const sr::sumcheck_fold::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
-                       const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, uint64_t *work,
-                       hipStream_t st) {
-    namespace sf = sr::sumcheck_fold;
-    ProfScope ps(c, st, K_POINTWISE);
-    sr::sumcheck::Tables tb{};
-    sf::Folded fo{};
-    uintptr_t bits = (uintptr_t)out | (uintptr_t)r | (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int j = 0; j < n_tables; j++) {
-        tb.p[j] = tables[j];
-        tb.n[j] = n_evals[j];
-        fo.p[j] = out_tables[j];
-        bits |= (uintptr_t)tables[j] | (uintptr_t)out_tables[j];
-    }
-    const bool al = (bits & 15u) == 0;
-    hipError_t e;
-    switch (c->ring) {
-        case SR_RING_GOLDILOCKS_POW2: e = sf::launch<sr::Goldilocks>(p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, al, work, st); break;
-        case SR_RING_BABYBEAR_POW2: e = sf::launch<sr::BabyBear>(p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, al, work, st); break;
-        case SR_RING_STARK_POW2: e = sf::launch<sr::Stark>(p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, al, work, st); break;
-        case SR_RING_GOLDILOCKS_24: e = sf::launch_slot<sr::SlotG24>(c->small, p, order, out, tb, fo, r, n_tables, num_vars, n_out, work, st); break;
-        case SR_RING_BABYBEAR_72: e = sf::launch_slot<sr::SlotB72>(c->small, p, order, out, tb, fo, r, n_tables, num_vars, n_out, work, st); break;
-        default: e = sf::launch_slot<sr::SlotFrog>(c->frog, p, order, out, tb, fo, r, n_tables, num_vars, n_out, work, st); break;
-    }
-    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("mle round fold launch: ") + hipGetErrorString(e));
+// the argument checks the two forms of sr_mle_round_fold_evals share
+int check_mle_round_fold(sr_ctx *c, const void *out, uint64_t *const *out_tables, const size_t *n_out, const uint64_t *const *tables,
+                         const size_t *n_evals, int n_tables, size_t num_vars, const void *r, int order, sr::sumcheck_fold::Plan *p) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!out || !out_tables || !n_out || !tables || !n_evals || !r) return refuse(kMleRoundFold, "null pointer");
+    if (int rc = round_plan_for(kMleRoundFold, c->ring, c->k, num_vars, n_tables, 0, 0, order, p)) return rc;
+    return check_round_tables(c, kMleRoundFold, tables, out_tables, n_evals, n_tables, num_vars);
 }
-// the shape checks sr_mle_round_fold_plan and the two forms of sr_mle_round_fold_evals share
-int round_fold_plan_for(int ring, int k, size_t num_vars, int n_tables, int order, sr::sumcheck_fold::Plan *p) {
-    if (n_tables < 1 || n_tables > SR_MLE_ROUND_MAX_TABLES) return fail(SR_E_INVALID, "mle_round_fold: n_tables must be 1 .. 4");
-    if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) return fail(SR_E_INVALID, "mle_round_fold: unknown order");
-    if (num_vars >= 48) return fail(SR_E_INVALID, "mle_round_fold: num_vars must be below 48");
-    if (num_vars < 2) return fail(SR_E_INVALID, "mle_round_fold: num_vars >= 2 (the folded tables need a variable for the next round)");
-    if (!sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, order, p)) return fail(SR_E_INVALID, "mle_round_fold: no plan for these arguments");
+// the workspace of a *_evals_dev call
+int check_round_work(const RoundFamily &f, const sr::sumcheck::Plan &p, const uint64_t *work, size_t work_elems) {
+    if (p.work_elems && !work) return refuse(f, "null pointer (d_work)");
+    if (work_elems < p.work_elems)
+        return refuse(f, "workspace too small (sr_" + std::string(f.name) + "_plan asks for " + std::to_string(p.work_elems) + " elements)");
     return SR_OK;
 }
 // elements the fold of a table of n stored elements writes
 size_t round_fold_n_out(size_t n, size_t num_vars, int order) {
     const size_t half = (size_t)1 << (num_vars - 1);
     return order == SR_MLE_LEADING ? (n + 1) / 2 : (n < half ? n : half);
-}
-// the argument checks the two forms of sr_mle_round_fold_evals share
-int check_mle_round_fold(sr_ctx *c, const void *out, uint64_t *const *out_tables, const size_t *n_out, const uint64_t *const *tables,
-                         const size_t *n_evals, int n_tables, size_t num_vars, const void *r, int order, sr::sumcheck_fold::Plan *p) {
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !out_tables || !n_out || !tables || !n_evals || !r) return fail(SR_E_INVALID, "mle_round_fold: null pointer");
-    if (int rc = round_fold_plan_for(c->ring, c->k, num_vars, n_tables, order, p)) return rc;
-    for (int j = 0; j < n_tables; j++) {
-        if (n_evals[j] > (size_t)1 << num_vars) return fail(SR_E_INVALID, "mle_round_fold: n_evals exceeds 2^num_vars");
-        if (n_evals[j] && (!tables[j] || !out_tables[j])) return fail(SR_E_INVALID, "mle_round_fold: null pointer (a table)");
-        if (int rc = check_count(c, n_evals[j])) return rc;
-    }
-    return SR_OK;
 }
 
 // ---- sparse multilinear extensions (csrc/sparse_mle.hpp): nothing allocated, no context scratch ----------------------------------
@@ -2032,6 +2026,26 @@ int staged(sr_ctx *c, const Staged (&ops)[N], Body body) {
     for (size_t i = 0; i < N; i++)
         if (ops[i].down && ops[i].bytes) HIP_TRY(hipMemcpyAsync(ops[i].down, c->buf[HOST_0 + i], ops[i].bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return SR_OK;
+}
+// The tables of a host-pointer call in one HOST_* slot: one behind the other, each on a 16-byte boundary
+struct TableSlot {
+    size_t off[SR_VPOLY_MAX_TABLES], total = 0;
+    TableSlot(const size_t *n, int n_tables, size_t w) {
+        for (int j = 0; j < n_tables; j++) {
+            off[j] = total;
+            total += (n[j] * w + 15) & ~(size_t)15;
+        }
+    }
+    // d[j]: table j of the slot at `base`
+    void at(void *base, int n_tables, uint64_t **d) const {
+        for (int j = 0; j < n_tables; j++) d[j] = (uint64_t *)((char *)base + off[j]);
+    }
+};
+// the host tables to their places d[j], on the context's stream
+int upload_tables(sr_ctx *c, uint64_t *const *d, const uint64_t *const *tables, const size_t *n, int n_tables, size_t w) {
+    for (int j = 0; j < n_tables; j++)
+        if (n[j]) HIP_TRY(hipMemcpyAsync(d[j], tables[j], n[j] * w, hipMemcpyHostToDevice, c->stream));
     return SR_OK;
 }
 // Sum / Product on host buffers: the n elements go to a device temporary as a whole (like the linear-algebra calls)
@@ -2549,22 +2563,13 @@ int sr_mle_fix_variables(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t
                   });
 }
 int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
-    if (!work_elems || !launches) return fail(SR_E_INVALID, "mle_round_plan: null result pointer");
-    sr::sumcheck::Plan p;
-    if (int rc = round_plan_for(ring, log2_degree, num_vars, n_tables, mode, &p)) return rc;
-    *work_elems = p.work_elems;
-    *launches = p.launches;
-    return SR_OK;
+    return round_plan_entry(kMleRound, ring, log2_degree, num_vars, n_tables, 0, 0, mode, work_elems, launches);
 }
 int sr_mle_round_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars,
                            int mode, uint64_t *work, size_t work_elems, void *stream) {
     sr::sumcheck::Plan p;
     if (int rc = check_mle_round(c, out, tables, n_evals, n_tables, num_vars, mode, &p)) return rc;
-    if (p.work_elems && !work) return fail(SR_E_INVALID, "mle_round: null pointer (d_work)");
-    if (work_elems < p.work_elems)
-        return fail(SR_E_INVALID, "mle_round: workspace too small (sr_mle_round_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    if (int rc = check_round_work(kMleRound, p, work, work_elems)) return rc;
     const size_t w = (size_t)c->degree * c->limbs * 8;
     for (int j = 0; j < n_tables; j++) {
         if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round: d_out overlaps a table");
@@ -2579,47 +2584,25 @@ int sr_mle_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, 
     if (int rc = check_mle_round(c, out, tables, n_evals, n_tables, num_vars, mode, &p)) return rc;
     const Call call(c);
     const size_t w = (size_t)c->degree * c->limbs * 8;
-    // HOST_0: the tables one behind the other, each on a 16-byte boundary; HOST_1: the result; HOST_2: the workspace
-    size_t off[SR_MLE_ROUND_MAX_TABLES], total = 0;
-    for (int j = 0; j < n_tables; j++) {
-        off[j] = total;
-        total += (n_evals[j] * w + 15) & ~(size_t)15;
-    }
-    if (int rc = grow(c, HOST_0, total)) return rc;
-    if (int rc = grow(c, HOST_1, p.np_total * w)) return rc;
-    if (int rc = grow(c, HOST_2, p.work_elems * w)) return rc;
-    const uint64_t *dt[SR_MLE_ROUND_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) {
-        dt[j] = (const uint64_t *)((char *)c->buf[HOST_0] + off[j]);
-        if (n_evals[j]) HIP_TRY(hipMemcpyAsync((void *)dt[j], tables[j], n_evals[j] * w, hipMemcpyHostToDevice, c->stream));
-    }
-    if (int rc = dev_mle_round(c, p, mode, (uint64_t *)c->buf[HOST_1], dt, n_evals, n_tables, num_vars, (uint64_t *)c->buf[HOST_2], c->stream)) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], p.np_total * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    const TableSlot in(n_evals, n_tables, w);
+    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}}, [&](void *const *d) -> int {
+        uint64_t *dt[SR_MLE_ROUND_MAX_TABLES];
+        in.at(d[0], n_tables, dt);
+        if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
+        return dev_mle_round(c, p, mode, (uint64_t *)d[1], dt, n_evals, n_tables, num_vars, (uint64_t *)d[2], c->stream);
+    });
 }
 int sr_vpoly_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int mode, size_t *work_elems,
                         int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
-    if (!work_elems || !launches) return fail(SR_E_INVALID, "vpoly_round_plan: null result pointer");
-    sr::vpoly::Plan p;
-    if (int rc = vpoly_plan_for(ring, log2_degree, num_vars, n_tables, n_terms, degree, mode, &p)) return rc;
-    *work_elems = p.work_elems;
-    *launches = p.launches;
-    return SR_OK;
+    return round_plan_entry(kVpolyRound, ring, log2_degree, num_vars, n_tables, n_terms, degree, mode, work_elems, launches);
 }
 int sr_vpoly_round_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                              const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int mode, uint64_t *work,
                              size_t work_elems, void *stream) {
     sr::vpoly::Plan p;
     if (int rc = check_vpoly_round(c, out, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, &p)) return rc;
-    if (p.work_elems && !work) return fail(SR_E_INVALID, "vpoly_round: null pointer (d_work)");
-    if (work_elems < p.work_elems)
-        return fail(SR_E_INVALID, "vpoly_round: workspace too small (sr_vpoly_round_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    if (int rc = check_round_work(kVpolyRound, p, work, work_elems)) return rc;
     const size_t w = (size_t)c->degree * c->limbs * 8;
     const size_t cw = coef ? n_terms * w : 0;
     for (int j = 0; j < n_tables; j++) {
@@ -2639,51 +2622,26 @@ int sr_vpoly_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables
     if (int rc = check_vpoly_round(c, out, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, &p)) return rc;
     const Call call(c);
     const size_t w = (size_t)c->degree * c->limbs * 8;
-    // HOST_0: the tables one behind the other, each on a 16-byte boundary; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients
-    size_t off[SR_VPOLY_MAX_TABLES], total = 0;
-    for (int j = 0; j < n_tables; j++) {
-        off[j] = total;
-        total += (n_evals[j] * w + 15) & ~(size_t)15;
-    }
-    if (int rc = grow(c, HOST_0, total)) return rc;
-    if (int rc = grow(c, HOST_1, p.np_total * w)) return rc;
-    if (int rc = grow(c, HOST_2, p.work_elems * w)) return rc;
-    if (coef)
-        if (int rc = grow(c, HOST_3, n_terms * w)) return rc;
-    const uint64_t *dt[SR_VPOLY_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) {
-        dt[j] = (const uint64_t *)((char *)c->buf[HOST_0] + off[j]);
-        if (n_evals[j]) HIP_TRY(hipMemcpyAsync((void *)dt[j], tables[j], n_evals[j] * w, hipMemcpyHostToDevice, c->stream));
-    }
-    if (coef) HIP_TRY(hipMemcpyAsync(c->buf[HOST_3], coef, n_terms * w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_vpoly_round(c, p, mode, (uint64_t *)c->buf[HOST_1], dt, n_evals, n_tables, terms, n_terms,
-                                 coef ? (const uint64_t *)c->buf[HOST_3] : nullptr, num_vars, (uint64_t *)c->buf[HOST_2], c->stream)) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], p.np_total * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    const TableSlot in(n_evals, n_tables, w);
+    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {coef, nullptr, coef ? n_terms * w : 0}},
+                  [&](void *const *d) -> int {
+                      uint64_t *dt[SR_VPOLY_MAX_TABLES];
+                      in.at(d[0], n_tables, dt);
+                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
+                      return dev_vpoly_round(c, p, mode, (uint64_t *)d[1], dt, n_evals, n_tables, terms, n_terms, coef ? (const uint64_t *)d[3] : nullptr,
+                                             num_vars, (uint64_t *)d[2], c->stream);
+                  });
 }
 int sr_mle_round_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int order, size_t *work_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
-    if (!work_elems || !launches) return fail(SR_E_INVALID, "mle_round_fold_plan: null result pointer");
-    sr::sumcheck_fold::Plan p;
-    if (int rc = round_fold_plan_for(ring, log2_degree, num_vars, n_tables, order, &p)) return rc;
-    *work_elems = p.work_elems;
-    *launches = p.launches;
-    return SR_OK;
+    return round_plan_entry(kMleRoundFold, ring, log2_degree, num_vars, n_tables, 0, 0, order, work_elems, launches);
 }
 int sr_mle_round_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
                                 const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, int order, uint64_t *work,
                                 size_t work_elems, void *stream) {
     sr::sumcheck_fold::Plan p;
     if (int rc = check_mle_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, order, &p)) return rc;
-    if (p.work_elems && !work) return fail(SR_E_INVALID, "mle_round_fold: null pointer (d_work)");
-    if (work_elems < p.work_elems)
-        return fail(SR_E_INVALID,
-                    "mle_round_fold: workspace too small (sr_mle_round_fold_plan asks for " + std::to_string(p.work_elems) + " elements)");
+    if (int rc = check_round_work(kMleRoundFold, p, work, work_elems)) return rc;
     const size_t w = (size_t)c->degree * c->limbs * 8;
     size_t n_out[SR_MLE_ROUND_MAX_TABLES];
     for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
@@ -2720,39 +2678,24 @@ int sr_mle_round_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_table
     if (int rc = check_mle_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, order, &p)) return rc;
     const Call call(c);
     const size_t w = (size_t)c->degree * c->limbs * 8;
-    // HOST_0: the tables one behind the other, each on a 16-byte boundary; HOST_1: the message, then r; HOST_2: the workspace; HOST_3: the
-    // folded tables, laid out like the tables
-    size_t off[SR_MLE_ROUND_MAX_TABLES], ooff[SR_MLE_ROUND_MAX_TABLES], total = 0, ototal = 0;
-    for (int j = 0; j < n_tables; j++) {
-        off[j] = total;
-        total += (n_evals[j] * w + 15) & ~(size_t)15;
-        ooff[j] = ototal;
-        ototal += (round_fold_n_out(n_evals[j], num_vars, order) * w + 15) & ~(size_t)15;
-    }
-    const size_t r_off = (p.np_total * w + 15) & ~(size_t)15;
-    if (int rc = grow(c, HOST_0, total)) return rc;
-    if (int rc = grow(c, HOST_1, r_off + w)) return rc;
-    if (int rc = grow(c, HOST_2, p.work_elems * w)) return rc;
-    if (int rc = grow(c, HOST_3, ototal)) return rc;
-    const uint64_t *dt[SR_MLE_ROUND_MAX_TABLES];
-    uint64_t *dout[SR_MLE_ROUND_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) {
-        dt[j] = (const uint64_t *)((char *)c->buf[HOST_0] + off[j]);
-        dout[j] = (uint64_t *)((char *)c->buf[HOST_3] + ooff[j]);
-        if (n_evals[j]) HIP_TRY(hipMemcpyAsync((void *)dt[j], tables[j], n_evals[j] * w, hipMemcpyHostToDevice, c->stream));
-    }
-    uint64_t *dr = (uint64_t *)((char *)c->buf[HOST_1] + r_off);
-    HIP_TRY(hipMemcpyAsync(dr, r, w, hipMemcpyHostToDevice, c->stream));
-    if (int rc = dev_mle_round_fold(c, p, order, (uint64_t *)c->buf[HOST_1], dout, n_evals_out, dt, n_evals, n_tables, num_vars, dr,
-                                    (uint64_t *)c->buf[HOST_2], c->stream)) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out, c->buf[HOST_1], p.np_total * w, hipMemcpyDeviceToHost, c->stream));
-    for (int j = 0; j < n_tables; j++)
-        if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SR_OK;
+    size_t n_out[SR_MLE_ROUND_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
+    const TableSlot in(n_evals, n_tables, w), folded(n_out, n_tables, w);
+    // HOST_0: the tables; HOST_1: the message; HOST_2: the workspace; HOST_3: the folded tables; HOST_4: r
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {nullptr, nullptr, folded.total},
+                      {r, nullptr, w}},
+                  [&](void *const *d) -> int {
+                      uint64_t *dt[SR_MLE_ROUND_MAX_TABLES], *dout[SR_MLE_ROUND_MAX_TABLES];
+                      in.at(d[0], n_tables, dt);
+                      folded.at(d[3], n_tables, dout);
+                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
+                      if (int rc = dev_mle_round_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dt, n_evals, n_tables, num_vars,
+                                                      (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
+                          return rc;
+                      for (int j = 0; j < n_tables; j++)
+                          if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
+                      return SR_OK;
+                  });
 }
 int sr_eq_table_dev(sr_ctx *c, uint64_t *out, const uint64_t *point, size_t n_vars, void *stream) {
     if (int rc = check(c, {out, n_vars ? (const void *)point : (const void *)1})) return rc;

@@ -16,6 +16,9 @@
 // scheme of gram_kernel / sum_parts_kernel (symmetric.hpp); the number of records is host arithmetic on the shape alone (plan), so
 // the plan needs no device.
 //
+// The host side below the kernels is shared with sumcheck_fold.hpp and sumcheck_vpoly.hpp: the records of a shape (plan_records), the
+// geometry of a launch (Geometry, geometry_of) and the launches of a plan (launch_plan); a family adds its own shape and launches.
+//
 // Truncated storage: a pair whose first element lies beyond the stored part of ANY table has a zero factor at every t and is never
 // visited (the loop ends at the shortest table); a second element beyond a table's stored part is zero and is not loaded.
 #pragma once
@@ -316,12 +319,32 @@ inline int log2_units(int ring, int k) {
         default: return 2;
     }
 }
+// lane-groups of a record for elements of 2^lu units
+inline size_t groups_per_record(int lu) { return lu < 8 ? (size_t)256 >> lu : 1; }
+
 struct Plan {
     size_t count = 0;   // pairs (round modes) or indices (sum) of the full table
     size_t groups = 1;  // records
     int np_total = 1, np_launch = 1, launches = 1;
     size_t work_elems = 0;
 };
+// The records of a shape, for all three families (sumcheck_fold.hpp, sumcheck_vpoly.hpp): groups, launches and work_elems of a plan
+// whose count and np_total are set and whose points go in point_launches launches.
+inline void plan_records(int ring, int k, int point_launches, Plan *p) {
+    const int lu = log2_units(ring, k);
+    const size_t per_record = groups_per_record(lu);      // lane-groups of a record
+    const size_t lanes = lu < 8 ? 256 : (size_t)1 << lu;  // lanes of a record
+    size_t want = lanes >= kFillLanes ? 1 : kFillLanes / lanes;
+    if (want > p->count / (kMinPairs * per_record)) want = p->count / (kMinPairs * per_record);
+    if (want > kMaxGroups) want = kMaxGroups;
+    if (want < 1) want = 1;
+    // the points in several launches: the launches meet in the workspace as well (at least two records, the second possibly empty), so
+    // that a plan without a workspace is always a single launch
+    if (point_launches > 1 && want < 2) want = 2;
+    p->groups = want;
+    p->launches = point_launches + (want > 1 ? 1 : 0);
+    p->work_elems = want > 1 ? want * (size_t)p->np_total : 0;
+}
 inline bool plan(int ring, int k, size_t num_vars, int n_tables, int mode, Plan *p) {
     if (ring < 0 || ring > 5 || num_vars > MAX_VARS || n_tables < 1 || n_tables > MAX_TABLES || mode < MODE_LEADING || mode > MODE_SUM) return false;
     if (mode != MODE_SUM && num_vars == 0) return false;
@@ -329,23 +352,66 @@ inline bool plan(int ring, int k, size_t num_vars, int n_tables, int mode, Plan 
     p->count = mode == MODE_SUM ? (size_t)1 << num_vars : (size_t)1 << (num_vars - 1);
     p->np_total = mode == MODE_SUM ? 1 : n_tables + 1;
     p->np_launch = mode == MODE_SUM ? 1 : points_per_launch(ring, n_tables);
-    const int lu = log2_units(ring, k);
-    const size_t per_record = lu < 8 ? (size_t)256 >> lu : 1;  // lane-groups of a record
-    const size_t lanes = lu < 8 ? 256 : (size_t)1 << lu;       // lanes of a record
-    size_t want = lanes >= kFillLanes ? 1 : kFillLanes / lanes;
-    if (want > p->count / (kMinPairs * per_record)) want = p->count / (kMinPairs * per_record);
-    if (want > kMaxGroups) want = kMaxGroups;
-    if (want < 1) want = 1;
-    // the points in several launches: the launches meet in the workspace as well (at least two records, the second possibly empty), so
-    // that a plan without a workspace is always a single launch
-    if (p->np_launch < p->np_total && want < 2) want = 2;
-    p->groups = want;
-    p->launches = (p->np_total + p->np_launch - 1) / p->np_launch + (want > 1 ? 1 : 0);
-    p->work_elems = want > 1 ? want * (size_t)p->np_total : 0;
+    plan_records(ring, k, (p->np_total + p->np_launch - 1) / p->np_launch, p);
     return true;
 }
 
-// ---- launchers ----------------------------------------------------------------------------------------------------------------------
+// ---- the launch skeleton of all three families --------------------------------------------------------------------------------------
+// A family type T is a field (the power-of-two rings) or a slot type (goldilocks24 / babybear72 / frog16); the slot kernels take the
+// ring's constants SL::K first, the field kernels take k and pair instead.
+template <class T>
+constexpr bool kSlot = std::is_same<T, SlotG24>::value || std::is_same<T, SlotB72>::value || std::is_same<T, SlotFrog>::value;
+struct NoConsts {};
+template <class T, bool = kSlot<T>>
+struct Family {
+    using F = T;
+    using K = NoConsts;
+};
+template <class T>
+struct Family<T, true> {
+    using F = typename T::F;
+    using K = typename T::K;
+};
+// The geometry of a call.  pair: a lane owns a 16-byte pair of coefficients -- a one-limb field, k >= 1, and every buffer of the call
+// starts on a 16-byte boundary.  An unaligned call has twice the units the plan counted: the same records, at 256 units and above
+// twice the lanes.  A slot ring has 8 or 4 units (slots) whatever the alignment; its kernels take neither k nor pair.
+struct Geometry {
+    int k, pair, lu;  // lu: log2 of the units of an element
+    size_t words;     // 64-bit words of an element
+    size_t groups(size_t records) const { return records * groups_per_record(lu); }  // lane-groups of the launch
+    dim3 grid(size_t records) const { return dim3((unsigned)(lu < 8 ? records : records << (lu - 8))); }
+};
+template <class T>
+inline Geometry geometry_of(int k, bool aligned) {
+    if constexpr (kSlot<T>) {
+        return {0, 0, T::D / T::W == 8 ? 3 : 2, (size_t)T::D};
+    } else {
+        const int pair = sizeof(typename T::storage) == 8 && k >= 1 && aligned;
+        return {k, pair, pair ? k - 1 : k, ((size_t)1 << k) * (sizeof(typename T::storage) / 8)};
+    }
+}
+// The launches of a plan, one after the other on `s`.  Nothing to visit: one launch that zeroes `out`.  Otherwise points(dst) enqueues
+// the family's own launches, which leave record r at element r * np_total of dst -- the workspace, or `out` when there is one record --
+// and the sum over the records follows.
+template <class T, class Points>
+inline hipError_t launch_plan(const Plan &p, const Geometry &ge, bool nothing, uint64_t *out, uint64_t *work, hipStream_t s, Points points) {
+    using F = typename Family<T>::F;
+    using S = typename F::storage;
+    const size_t words = (size_t)p.np_total * ge.words;
+    if (nothing) {
+        hipLaunchKernelGGL(zero_kernel, dim3(mle::blocks_for(words)), dim3(256), 0, s, out, words);
+        return hipGetLastError();
+    }
+    points(p.groups > 1 ? work : out);
+    if (p.groups > 1) {
+        const size_t total = words / (sizeof(S) / 8);
+        hipLaunchKernelGGL((sum_groups_kernel<F>), dim3(mle::blocks_for(total)), dim3(256), 0, s, reinterpret_cast<S *>(out),
+                           reinterpret_cast<const S *>(work), total, p.groups);
+    }
+    return hipGetLastError();
+}
+
+// ---- the launches of a round message --------------------------------------------------------------------------------------------------
 struct Shape {
     size_t count, sb, st;  // pairs to visit (already cut to the shortest table), element strides of a pair
 };
@@ -357,31 +423,25 @@ inline Shape shape_of(int mode, size_t num_vars, const size_t *n_evals, int n_ta
     if (mode == MODE_LEADING) return {(nmin + 1) / 2, 2, 1};
     return {nmin < half ? nmin : half, 1, half};
 }
-// lane-groups of a record for elements of 2^lu units
-inline size_t groups_per_record(int lu) { return lu < 8 ? (size_t)256 >> lu : 1; }
-
-// np is the launch's chunk of points: points_of (P) or the remainder of d + 1 (R) -- the only two kernels a (field, d) pair reaches
-template <class F, int NT, bool PAIR>
-inline void launch_np(int np, uint64_t *dst, const Tables &tb, const Shape &sh, int k, int pair, size_t records, unsigned t0, unsigned np_total,
-                      hipStream_t s) {
-    // an unaligned call has twice the units the plan counted: the same records, at 256 units and above twice the lanes
-    const int lu = pair ? k - 1 : k;
-    const size_t groups = records * groups_per_record(lu);
-    const dim3 g((unsigned)(lu < 8 ? records : records << (lu - 8))), b(256);
-    constexpr int P = PAIR ? points_of<F>(NT) : 1, R = PAIR ? (NT + 1) % P : 0;
-    if (np == P) hipLaunchKernelGGL((round_kernel<F, NT, P, PAIR>), g, b, 0, s, dst, tb, sh.count, sh.sb, sh.st, k, pair, groups, t0, np_total);
-    if constexpr (R != 0)
-        if (np == R) hipLaunchKernelGGL((round_kernel<F, NT, R, PAIR>), g, b, 0, s, dst, tb, sh.count, sh.sb, sh.st, k, pair, groups, t0, np_total);
+// one launch: NP points from t0 on (sumcheck_fold.hpp takes its remaining points from here as well)
+template <class T, int NT, int NP, bool PAIR>
+inline void launch_round(const typename Family<T>::K &kc, const Geometry &ge, size_t records, uint64_t *dst, const Tables &tb, const Shape &sh,
+                         unsigned t0, unsigned np_total, hipStream_t s) {
+    const dim3 g = ge.grid(records), b(256);
+    if constexpr (kSlot<T>)
+        hipLaunchKernelGGL((slot_round_kernel<T, NT, NP, PAIR>), g, b, 0, s, kc, dst, tb, sh.count, sh.sb, sh.st, ge.groups(records), t0, np_total);
+    else
+        hipLaunchKernelGGL((round_kernel<T, NT, NP, PAIR>), g, b, 0, s, dst, tb, sh.count, sh.sb, sh.st, ge.k, ge.pair, ge.groups(records), t0,
+                           np_total);
 }
-template <class SL, int NT, bool PAIR>
-inline void launch_slot_np(const typename SL::K &kc, int np, uint64_t *dst, const Tables &tb, const Shape &sh, size_t records, unsigned t0,
-                           unsigned np_total, hipStream_t s) {
-    const size_t groups = records * (256 / (SL::D / SL::W));
-    const dim3 g((unsigned)records), b(256);
-    constexpr int P = PAIR ? points_of<SL>(NT) : 1, R = PAIR ? (NT + 1) % P : 0;
-    if (np == P) hipLaunchKernelGGL((slot_round_kernel<SL, NT, P, PAIR>), g, b, 0, s, kc, dst, tb, sh.count, sh.sb, sh.st, groups, t0, np_total);
+// np is the launch's chunk of points: points_of (P) or the remainder of d + 1 (R) -- the only two kernels a (family type, d) pair reaches
+template <class T, int NT, bool PAIR>
+inline void launch_np(const typename Family<T>::K &kc, const Geometry &ge, int np, size_t records, uint64_t *dst, const Tables &tb, const Shape &sh,
+                      unsigned t0, unsigned np_total, hipStream_t s) {
+    constexpr int P = PAIR ? points_of<T>(NT) : 1, R = PAIR ? (NT + 1) % P : 0;
+    if (np == P) launch_round<T, NT, P, PAIR>(kc, ge, records, dst, tb, sh, t0, np_total, s);
     if constexpr (R != 0)
-        if (np == R) hipLaunchKernelGGL((slot_round_kernel<SL, NT, R, PAIR>), g, b, 0, s, kc, dst, tb, sh.count, sh.sb, sh.st, groups, t0, np_total);
+        if (np == R) launch_round<T, NT, R, PAIR>(kc, ge, records, dst, tb, sh, t0, np_total, s);
 }
 // fn(integral_constant NT) for n_tables in 1 .. 4
 template <class Fn>
@@ -393,55 +453,21 @@ inline void with_tables(int n_tables, Fn fn) {
         default: fn(std::integral_constant<int, 4>{}); break;
     }
 }
-// The launches of a plan, one after the other on `s`: the points in chunks of np_launch, then the sum over the records.
-// pair: every table, out and work start on a 16-byte boundary.  An empty table: one launch that zeroes `out`.
-template <class F>
-inline hipError_t launch(const Plan &p, int mode, uint64_t *out, const Tables &tb, int n_tables, size_t num_vars, const size_t *n_evals, int k,
-                         bool aligned, uint64_t *work, hipStream_t s) {
-    const size_t w = ((size_t)1 << k) * (sizeof(typename F::storage) / 8);
-    const Shape sh = shape_of(mode, num_vars, n_evals, n_tables);
-    if (sh.count == 0) {
-        hipLaunchKernelGGL(zero_kernel, dim3(mle::blocks_for(p.np_total * w)), dim3(256), 0, s, out, p.np_total * w);
-        return hipGetLastError();
-    }
-    const int pair = sizeof(typename F::storage) == 8 && k >= 1 && aligned;
-    uint64_t *dst = p.groups > 1 ? work : out;
-    for (int t0 = 0; t0 < p.np_total; t0 += p.np_launch) {
-        const int np = p.np_total - t0 < p.np_launch ? p.np_total - t0 : p.np_launch;
-        with_tables(n_tables, [&](auto nt) {
-            if (mode == MODE_SUM) launch_np<F, decltype(nt)::value, false>(np, dst, tb, sh, k, pair, p.groups, (unsigned)t0, (unsigned)p.np_total, s);
-            else launch_np<F, decltype(nt)::value, true>(np, dst, tb, sh, k, pair, p.groups, (unsigned)t0, (unsigned)p.np_total, s);
-        });
-    }
-    if (p.groups > 1) {
-        using S = typename F::storage;
-        const size_t total = (size_t)p.np_total << k;
-        hipLaunchKernelGGL((sum_groups_kernel<F>), dim3(mle::blocks_for(total)), dim3(256), 0, s, reinterpret_cast<S *>(out),
-                           reinterpret_cast<const S *>(work), total, p.groups);
-    }
-    return hipGetLastError();
-}
-template <class SL>
-inline hipError_t launch_slot(const typename SL::K &kc, const Plan &p, int mode, uint64_t *out, const Tables &tb, int n_tables, size_t num_vars,
-                              const size_t *n_evals, uint64_t *work, hipStream_t s) {
-    const Shape sh = shape_of(mode, num_vars, n_evals, n_tables);
-    if (sh.count == 0) {
-        hipLaunchKernelGGL(zero_kernel, dim3(mle::blocks_for((size_t)p.np_total * SL::D)), dim3(256), 0, s, out, (size_t)p.np_total * SL::D);
-        return hipGetLastError();
-    }
-    uint64_t *dst = p.groups > 1 ? work : out;
-    for (int t0 = 0; t0 < p.np_total; t0 += p.np_launch) {
-        const int np = p.np_total - t0 < p.np_launch ? p.np_total - t0 : p.np_launch;
-        with_tables(n_tables, [&](auto nt) {
-            if (mode == MODE_SUM) launch_slot_np<SL, decltype(nt)::value, false>(kc, np, dst, tb, sh, p.groups, (unsigned)t0, (unsigned)p.np_total, s);
-            else launch_slot_np<SL, decltype(nt)::value, true>(kc, np, dst, tb, sh, p.groups, (unsigned)t0, (unsigned)p.np_total, s);
-        });
-    }
-    if (p.groups > 1) {
-        const size_t total = (size_t)p.np_total * SL::D;
-        hipLaunchKernelGGL((sum_groups_kernel<typename SL::F>), dim3(mle::blocks_for(total)), dim3(256), 0, s, out, work, total, p.groups);
-    }
-    return hipGetLastError();
+// The points in chunks of np_launch.  aligned: every table, out and work start on a 16-byte boundary.  An empty table: nothing to visit.
+template <class T>
+inline hipError_t launch(const typename Family<T>::K &kc, const Plan &p, int mode, uint64_t *out, const Tables &tb, int n_tables, size_t num_vars,
+                         int k, bool aligned, uint64_t *work, hipStream_t s) {
+    const Geometry ge = geometry_of<T>(k, aligned);
+    const Shape sh = shape_of(mode, num_vars, tb.n, n_tables);
+    return launch_plan<T>(p, ge, sh.count == 0, out, work, s, [&](uint64_t *dst) {
+        for (int t0 = 0; t0 < p.np_total; t0 += p.np_launch) {
+            const int np = p.np_total - t0 < p.np_launch ? p.np_total - t0 : p.np_launch;
+            with_tables(n_tables, [&](auto nt) {
+                if (mode == MODE_SUM) launch_np<T, decltype(nt)::value, false>(kc, ge, np, p.groups, dst, tb, sh, (unsigned)t0, (unsigned)p.np_total, s);
+                else launch_np<T, decltype(nt)::value, true>(kc, ge, np, p.groups, dst, tb, sh, (unsigned)t0, (unsigned)p.np_total, s);
+            });
+        }
+    });
 }
 
 }  // namespace sumcheck

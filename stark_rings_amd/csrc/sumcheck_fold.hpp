@@ -12,7 +12,8 @@
 // launch and takes the QUADS b = g, g + groups, ...: f[4b .. 4b + 3] in leading order, f[b], f[b + Q], f[b + 2Q], f[b + 3Q] in trailing
 // order.  Table by table it loads the quad, folds it to the two elements of pair b, stores both; then it multiplies as round_units does.
 // The records, the lazy sums (kFlush) and the last launch (sum_groups_kernel) are those of sumcheck.hpp; the plan is the plan of a round
-// in num_vars - 1 variables.
+// in num_vars - 1 variables.  The launch skeleton (geometry, destination, sum over the records) is sumcheck::launch_plan; this file adds
+// the shape of a fold, the fused launch and the remaining points.
 //
 // Truncated storage: every table is folded to ITS OWN length -- n_out = (n + 1) / 2 (leading) or min(n, 2^(num_vars-1)) (trailing)
 // elements are written, nothing beyond them -- while the product stops at the shortest folded table: the fold loop and the product loop
@@ -322,28 +323,17 @@ inline int fused_points(int ring, int n_tables) {
         default: return fused_points_of<SlotFrog>(n_tables);
     }
 }
-struct Plan {
-    size_t groups = 1;  // records
-    int np_total = 2, np_fused = 2, np_launch = 2, launches = 1;
-    size_t work_elems = 0;
-};
+using Plan = sumcheck::Plan;
 // the records of a round in num_vars - 1 variables; the fused launch, the launches of the remaining points, the sum over the records
 inline bool plan(int ring, int k, size_t num_vars, int n_tables, int order, Plan *p) {
     if (num_vars < 2 || (order != sumcheck::MODE_LEADING && order != sumcheck::MODE_TRAILING)) return false;
-    sumcheck::Plan rp;
-    if (!sumcheck::plan(ring, k, num_vars - 1, n_tables, order, &rp)) return false;
-    *p = Plan{};
-    p->np_total = rp.np_total;
-    p->np_launch = rp.np_launch;
-    p->np_fused = fused_points(ring, n_tables);
-    const int rest = p->np_total - p->np_fused;
-    p->groups = rest > 0 && rp.groups < 2 ? 2 : rp.groups;  // several launches meet in the workspace
-    p->launches = 1 + (rest + p->np_launch - 1) / p->np_launch + (p->groups > 1 ? 1 : 0);
-    p->work_elems = p->groups > 1 ? p->groups * (size_t)p->np_total : 0;
+    if (!sumcheck::plan(ring, k, num_vars - 1, n_tables, order, p)) return false;
+    const int rest = p->np_total - fused_points(ring, n_tables);
+    sumcheck::plan_records(ring, k, 1 + (rest + p->np_launch - 1) / p->np_launch, p);
     return true;
 }
 
-// ---- launchers ----------------------------------------------------------------------------------------------------------------------
+// ---- launchers: the skeleton is sumcheck::launch_plan -------------------------------------------------------------------------------
 struct Shape {
     size_t count, qmax, sb, st, fst;  // quads in the product, quads to fold, strides (see fold_round_units)
 };
@@ -361,32 +351,17 @@ inline bool shape_of(int order, size_t num_vars, const size_t *n_evals, int n_ta
     }
     return sh->qmax != 0;
 }
-// the points t0 .. of the remaining launches, from the existing round kernels over the folded tables: chunks of points_of, then the rest
-template <class F, int NT>
-inline void launch_rest(uint64_t *dst, const Tables &ftb, const Shape &sh, int k, int pair, const dim3 &g, size_t groups, unsigned np_total, hipStream_t s) {
-    constexpr int FP = fused_points_of<F>(NT), P = sumcheck::points_of<F>(NT), REST = NT + 1 - FP, R = REST % P;
+// the points t0 .. of the remaining launches, from the round kernels of sumcheck.hpp over the folded tables: chunks of points_of, then
+// the rest
+template <class T, int NT>
+inline void launch_rest(const typename sumcheck::Family<T>::K &kc, const sumcheck::Geometry &ge, size_t records, uint64_t *dst, const Tables &ftb,
+                        const sumcheck::Shape &sh, unsigned np_total, hipStream_t s) {
+    constexpr int FP = fused_points_of<T>(NT), P = sumcheck::points_of<T>(NT), REST = NT + 1 - FP, R = REST % P;
     if constexpr (REST > 0) {
         unsigned t0 = FP;
         if constexpr (REST >= P)
-            for (int i = 0; i < REST / P; i++, t0 += P)
-                hipLaunchKernelGGL((sumcheck::round_kernel<F, NT, P, true>), g, dim3(256), 0, s, dst, ftb, sh.count, sh.sb, sh.st, k, pair, groups, t0,
-                                   np_total);
-        if constexpr (R != 0)
-            hipLaunchKernelGGL((sumcheck::round_kernel<F, NT, R, true>), g, dim3(256), 0, s, dst, ftb, sh.count, sh.sb, sh.st, k, pair, groups, t0, np_total);
-    }
-}
-template <class SL, int NT>
-inline void launch_slot_rest(const typename SL::K &kc, uint64_t *dst, const Tables &ftb, const Shape &sh, const dim3 &g, size_t groups, unsigned np_total,
-                             hipStream_t s) {
-    constexpr int FP = fused_points_of<SL>(NT), P = sumcheck::points_of<SL>(NT), REST = NT + 1 - FP, R = REST % P;
-    if constexpr (REST > 0) {
-        unsigned t0 = FP;
-        if constexpr (REST >= P)
-            for (int i = 0; i < REST / P; i++, t0 += P)
-                hipLaunchKernelGGL((sumcheck::slot_round_kernel<SL, NT, P, true>), g, dim3(256), 0, s, kc, dst, ftb, sh.count, sh.sb, sh.st, groups, t0,
-                                   np_total);
-        if constexpr (R != 0)
-            hipLaunchKernelGGL((sumcheck::slot_round_kernel<SL, NT, R, true>), g, dim3(256), 0, s, kc, dst, ftb, sh.count, sh.sb, sh.st, groups, t0, np_total);
+            for (int i = 0; i < REST / P; i++, t0 += P) sumcheck::launch_round<T, NT, P, true>(kc, ge, records, dst, ftb, sh, t0, np_total, s);
+        if constexpr (R != 0) sumcheck::launch_round<T, NT, R, true>(kc, ge, records, dst, ftb, sh, t0, np_total, s);
     }
 }
 inline Tables folded_as_tables(const Folded &fo, int n_tables) {
@@ -397,65 +372,30 @@ inline Tables folded_as_tables(const Folded &fo, int n_tables) {
     }
     return t;
 }
-// The launches of a plan, one after the other on `s`.  fo.p holds the output pointers; n_out receives the elements written per table.
-// aligned: every table, folded table, r, out and work start on a 16-byte boundary.  Every table empty: one launch that zeroes `out`.
-template <class F>
-inline hipError_t launch(const Plan &p, int order, uint64_t *out, const Tables &tb, Folded fo, const uint64_t *r, int n_tables, size_t num_vars,
-                         size_t *n_out, int k, bool aligned, uint64_t *work, hipStream_t s) {
-    const size_t w = ((size_t)1 << k) * (sizeof(typename F::storage) / 8);
+// The fused launch, then the remaining points.  fo.p holds the output pointers; n_out receives the elements written per table.
+// aligned: every table, folded table, r, out and work start on a 16-byte boundary.  Every table empty: nothing to visit.
+template <class T>
+inline hipError_t launch(const typename sumcheck::Family<T>::K &kc, const Plan &p, int order, uint64_t *out, const Tables &tb, Folded fo,
+                         const uint64_t *r, int n_tables, size_t num_vars, size_t *n_out, int k, bool aligned, uint64_t *work, hipStream_t s) {
     Shape sh;
     const bool any = shape_of(order, num_vars, tb.n, n_tables, &fo, &sh);
     for (int j = 0; j < n_tables; j++) n_out[j] = fo.n[j];
-    if (!any) {
-        hipLaunchKernelGGL(sumcheck::zero_kernel, dim3(mle::blocks_for(p.np_total * w)), dim3(256), 0, s, out, p.np_total * w);
-        return hipGetLastError();
-    }
-    const int pair = sizeof(typename F::storage) == 8 && k >= 1 && aligned;
-    // an unaligned call has twice the units the plan counted: the same records, at 256 units and above twice the lanes
-    const int lu = pair ? k - 1 : k;
-    const size_t groups = p.groups * sumcheck::groups_per_record(lu);
-    const dim3 g((unsigned)(lu < 8 ? p.groups : p.groups << (lu - 8))), b(256);
-    uint64_t *dst = p.groups > 1 ? work : out;
-    const Tables ftb = folded_as_tables(fo, n_tables);
-    sumcheck::with_tables(n_tables, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((fold_round_kernel<F, NT, fused_points_of<F>(NT)>), g, b, 0, s, dst, tb, fo, r, sh.count, sh.qmax, sh.sb, sh.st, sh.fst, k, pair,
-                           groups, (unsigned)p.np_total);
-        launch_rest<F, NT>(dst, ftb, sh, k, pair, g, groups, (unsigned)p.np_total, s);
+    const sumcheck::Geometry ge = sumcheck::geometry_of<T>(k, aligned);
+    return sumcheck::launch_plan<T>(p, ge, !any, out, work, s, [&](uint64_t *dst) {
+        const dim3 g = ge.grid(p.groups), b(256);
+        const size_t groups = ge.groups(p.groups);
+        const Tables ftb = folded_as_tables(fo, n_tables);
+        sumcheck::with_tables(n_tables, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value, FP = fused_points_of<T>(NT);
+            if constexpr (sumcheck::kSlot<T>)
+                hipLaunchKernelGGL((slot_fold_round_kernel<T, NT, FP>), g, b, 0, s, kc, dst, tb, fo, r, sh.count, sh.qmax, sh.sb, sh.st, sh.fst, groups,
+                                   (unsigned)p.np_total);
+            else
+                hipLaunchKernelGGL((fold_round_kernel<T, NT, FP>), g, b, 0, s, dst, tb, fo, r, sh.count, sh.qmax, sh.sb, sh.st, sh.fst, ge.k, ge.pair,
+                                   groups, (unsigned)p.np_total);
+            launch_rest<T, NT>(kc, ge, p.groups, dst, ftb, {sh.count, sh.sb, sh.st}, (unsigned)p.np_total, s);
+        });
     });
-    if (p.groups > 1) {
-        using S = typename F::storage;
-        const size_t total = (size_t)p.np_total << k;
-        hipLaunchKernelGGL((sumcheck::sum_groups_kernel<F>), dim3(mle::blocks_for(total)), dim3(256), 0, s, reinterpret_cast<S *>(out),
-                           reinterpret_cast<const S *>(work), total, p.groups);
-    }
-    return hipGetLastError();
-}
-template <class SL>
-inline hipError_t launch_slot(const typename SL::K &kc, const Plan &p, int order, uint64_t *out, const Tables &tb, Folded fo, const uint64_t *r,
-                              int n_tables, size_t num_vars, size_t *n_out, uint64_t *work, hipStream_t s) {
-    Shape sh;
-    const bool any = shape_of(order, num_vars, tb.n, n_tables, &fo, &sh);
-    for (int j = 0; j < n_tables; j++) n_out[j] = fo.n[j];
-    if (!any) {
-        hipLaunchKernelGGL(sumcheck::zero_kernel, dim3(mle::blocks_for((size_t)p.np_total * SL::D)), dim3(256), 0, s, out, (size_t)p.np_total * SL::D);
-        return hipGetLastError();
-    }
-    const size_t groups = p.groups * (256 / (SL::D / SL::W));
-    const dim3 g((unsigned)p.groups), b(256);
-    uint64_t *dst = p.groups > 1 ? work : out;
-    const Tables ftb = folded_as_tables(fo, n_tables);
-    sumcheck::with_tables(n_tables, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((slot_fold_round_kernel<SL, NT, fused_points_of<SL>(NT)>), g, b, 0, s, kc, dst, tb, fo, r, sh.count, sh.qmax, sh.sb, sh.st, sh.fst,
-                           groups, (unsigned)p.np_total);
-        launch_slot_rest<SL, NT>(kc, dst, ftb, sh, g, groups, (unsigned)p.np_total, s);
-    });
-    if (p.groups > 1) {
-        const size_t total = (size_t)p.np_total * SL::D;
-        hipLaunchKernelGGL((sumcheck::sum_groups_kernel<typename SL::F>), dim3(mle::blocks_for(total)), dim3(256), 0, s, out, work, total, p.groups);
-    }
-    return hipGetLastError();
 }
 
 }  // namespace sumcheck_fold

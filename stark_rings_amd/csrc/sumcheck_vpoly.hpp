@@ -9,8 +9,8 @@
 //
 // One pass reads every DISTINCT table once, however many terms it is in.  The lane mapping, the records, the meeting of lane-groups in
 // LDS and the sum over the records are those of sumcheck.hpp (mle::Lane, sum_groups_kernel, zero_kernel are used from there, not
-// copied).  Per pair a lane loads lo / hi of its unit of every table, and per point t it walks the terms with v_j(t) = v_j(t - 1) +
-// (hi_j - lo_j) as sumcheck.hpp does.
+// copied), and so are the records of the plan and the launch skeleton (plan_records, launch_plan).  Per pair a lane loads lo / hi of
+// its unit of every table, and per point t it walks the terms with v_j(t) = v_j(t - 1) + (hi_j - lo_j) as sumcheck.hpp does.
 //
 // The term walk.  The table count of a kernel is a template parameter (4 or 8; a slot j >= n_tables is never loaded), the term
 // structure is runtime data: 16 bits per term -- n_factors in bits 0-2, table[s] in bits 3 + 3 s .. 5 + 3 s -- in two 64-bit kernel
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void slot_round_kernel(typename SL::K kc, uint
 }
 
 // ---- the plan: pure host arithmetic -------------------------------------------------------------------------------------------------
-// The records are those of sumcheck::plan (kFillLanes, kMaxGroups, kMinPairs); only the points differ: d + 1 of them for the largest
+// The records are those of sumcheck.hpp (plan_records); only the points differ: d + 1 of them for the largest
 // term, in launches of points_of<T>(table slots of the kernel).  tests/test_vpoly_isa.py holds the register count of every kernel.
 inline int table_slots(int n_tables) { return n_tables <= 4 ? 4 : 8; }
 template <class T>
@@ -423,22 +423,11 @@ inline bool plan(int ring, int k, size_t num_vars, int n_tables, int degree, int
     p->np_total = mode == MODE_SUM ? 1 : degree + 1;
     p->np_launch = mode == MODE_SUM ? 1 : points_per_launch(ring, table_slots(n_tables));
     if (p->np_launch > p->np_total) p->np_launch = p->np_total;
-    const int lu = sumcheck::log2_units(ring, k);
-    const size_t per_record = lu < 8 ? (size_t)256 >> lu : 1;  // lane-groups of a record
-    const size_t lanes = lu < 8 ? 256 : (size_t)1 << lu;       // lanes of a record
-    size_t want = lanes >= sumcheck::kFillLanes ? 1 : sumcheck::kFillLanes / lanes;
-    if (want > p->count / (sumcheck::kMinPairs * per_record)) want = p->count / (sumcheck::kMinPairs * per_record);
-    if (want > sumcheck::kMaxGroups) want = sumcheck::kMaxGroups;
-    if (want < 1) want = 1;
-    // the points in several launches meet in the workspace as well, so that a plan without a workspace is always a single launch
-    if (p->np_launch < p->np_total && want < 2) want = 2;
-    p->groups = want;
-    p->launches = (p->np_total + p->np_launch - 1) / p->np_launch + (want > 1 ? 1 : 0);
-    p->work_elems = want > 1 ? want * (size_t)p->np_total : 0;
+    sumcheck::plan_records(ring, k, (p->np_total + p->np_launch - 1) / p->np_launch, p);
     return true;
 }
 
-// ---- launchers ----------------------------------------------------------------------------------------------------------------------
+// ---- launchers: the skeleton is sumcheck::launch_plan -------------------------------------------------------------------------------
 using Shape = sumcheck::Shape;
 // pairs (or indices) of one table in this mode
 inline size_t pairs_of(int mode, size_t num_vars, size_t n) {
@@ -460,84 +449,53 @@ inline Shape shape_of(int mode, size_t num_vars, const size_t *n_evals, const Te
     if (mode == MODE_LEADING) return {count, 2, 1};
     return {count, 1, (size_t)1 << (num_vars - 1)};
 }
-// dynamic LDS of round_kernel: the coefficient stash, and at least the meeting place of the lane-groups (256 lanes x RW words)
-template <class F>
+// dynamic LDS of round_kernel: the coefficient stash, and at least the meeting place of the lane-groups (256 lanes x RW words); the slot
+// kernels keep both in static LDS
+template <class T>
 inline size_t lds_bytes(int n_terms, bool has_coef, int pair) {
-    const size_t rw = sizeof(typename F::storage) == 8 ? (pair ? 2 : 1) : sizeof(typename F::storage) / 8;
-    return (size_t)(has_coef ? n_terms : 1) * 256 * rw * 8;
+    if constexpr (sumcheck::kSlot<T>) {
+        return 0;
+    } else {
+        const size_t rw = sizeof(typename T::storage) == 8 ? (pair ? 2 : 1) : sizeof(typename T::storage) / 8;
+        return (size_t)(has_coef ? n_terms : 1) * 256 * rw * 8;
+    }
 }
 template <class Fn>
 inline void with_slots(int n_tables, Fn fn) {
     if (table_slots(n_tables) == 4) fn(std::integral_constant<int, 4>{});
     else fn(std::integral_constant<int, 8>{});
 }
-// The launches of a plan, one after the other on `s`: the points in chunks of np_launch, then the sum over the records.
-// aligned: every table, the coefficients, out and work start on a 16-byte boundary.  Every term empty: one launch that zeroes `out`.
-template <class F>
-inline hipError_t launch(const Plan &p, int mode, uint64_t *out, const Tables &tb, int n_tables, const Term *terms, int n_terms, const uint64_t *coef,
-                         size_t num_vars, const size_t *n_evals, int k, bool aligned, uint64_t *work, hipStream_t s) {
-    const size_t w = ((size_t)1 << k) * (sizeof(typename F::storage) / 8);
-    const Shape sh = shape_of(mode, num_vars, n_evals, terms, n_terms);
-    if (sh.count == 0) {
-        hipLaunchKernelGGL(sumcheck::zero_kernel, dim3(mle::blocks_for(p.np_total * w)), dim3(256), 0, s, out, p.np_total * w);
-        return hipGetLastError();
-    }
-    const int pair = sizeof(typename F::storage) == 8 && k >= 1 && aligned;
-    const int lu = pair ? k - 1 : k;
-    const size_t groups = p.groups * sumcheck::groups_per_record(lu);
-    const dim3 g((unsigned)(lu < 8 ? p.groups : p.groups << (lu - 8))), b(256);
-    const Terms tm = pack_terms(terms, n_terms, n_tables);
-    const size_t lds = lds_bytes<F>(n_terms, coef != nullptr, pair);
-    uint64_t *dst = p.groups > 1 ? work : out;
-    for (int t0 = 0; t0 < p.np_total; t0 += p.np_launch) {
-        const int np = p.np_total - t0 < p.np_launch ? p.np_total - t0 : p.np_launch;
-        with_slots(n_tables, [&](auto nt) {
-            constexpr int NT = decltype(nt)::value;
-            if (mode == MODE_SUM)
-                hipLaunchKernelGGL((round_kernel<F, NT, 1, false>), g, b, lds, s, dst, tb, tm, coef, sh.count, sh.sb, sh.st, k, pair, groups, (unsigned)t0,
-                                   (unsigned)np, (unsigned)p.np_total);
-            else
-                hipLaunchKernelGGL((round_kernel<F, NT, points_of<F>(NT), true>), g, b, lds, s, dst, tb, tm, coef, sh.count, sh.sb, sh.st, k, pair, groups,
-                                   (unsigned)t0, (unsigned)np, (unsigned)p.np_total);
-        });
-    }
-    if (p.groups > 1) {
-        using S = typename F::storage;
-        const size_t total = (size_t)p.np_total << k;
-        hipLaunchKernelGGL((sumcheck::sum_groups_kernel<F>), dim3(mle::blocks_for(total)), dim3(256), 0, s, reinterpret_cast<S *>(out),
-                           reinterpret_cast<const S *>(work), total, p.groups);
-    }
-    return hipGetLastError();
-}
-template <class SL>
-inline hipError_t launch_slot(const typename SL::K &kc, const Plan &p, int mode, uint64_t *out, const Tables &tb, int n_tables, const Term *terms,
-                              int n_terms, const uint64_t *coef, size_t num_vars, const size_t *n_evals, uint64_t *work, hipStream_t s) {
-    const Shape sh = shape_of(mode, num_vars, n_evals, terms, n_terms);
-    if (sh.count == 0) {
-        hipLaunchKernelGGL(sumcheck::zero_kernel, dim3(mle::blocks_for((size_t)p.np_total * SL::D)), dim3(256), 0, s, out, (size_t)p.np_total * SL::D);
-        return hipGetLastError();
-    }
-    const size_t groups = p.groups * (256 / (SL::D / SL::W));
-    const dim3 g((unsigned)p.groups), b(256);
-    const Terms tm = pack_terms(terms, n_terms, n_tables);
-    uint64_t *dst = p.groups > 1 ? work : out;
-    for (int t0 = 0; t0 < p.np_total; t0 += p.np_launch) {
-        const int np = p.np_total - t0 < p.np_launch ? p.np_total - t0 : p.np_launch;
-        with_slots(n_tables, [&](auto nt) {
-            constexpr int NT = decltype(nt)::value;
-            if (mode == MODE_SUM)
-                hipLaunchKernelGGL((slot_round_kernel<SL, NT, 1, false>), g, b, 0, s, kc, dst, tb, tm, coef, sh.count, sh.sb, sh.st, groups, (unsigned)t0,
-                                   (unsigned)np, (unsigned)p.np_total);
-            else
-                hipLaunchKernelGGL((slot_round_kernel<SL, NT, points_of<SL>(NT), true>), g, b, 0, s, kc, dst, tb, tm, coef, sh.count, sh.sb, sh.st, groups,
-                                   (unsigned)t0, (unsigned)np, (unsigned)p.np_total);
-        });
-    }
-    if (p.groups > 1) {
-        const size_t total = (size_t)p.np_total * SL::D;
-        hipLaunchKernelGGL((sumcheck::sum_groups_kernel<typename SL::F>), dim3(mle::blocks_for(total)), dim3(256), 0, s, out, work, total, p.groups);
-    }
-    return hipGetLastError();
+// The points in chunks of np_launch: np of the kernel's NP points from t0 on.  aligned: every table, the coefficients, out and work
+// start on a 16-byte boundary.  Every term empty: nothing to visit.
+template <class T>
+inline hipError_t launch(const typename sumcheck::Family<T>::K &kc, const Plan &p, int mode, uint64_t *out, const Tables &tb, int n_tables,
+                         const Term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int k, bool aligned, uint64_t *work, hipStream_t s) {
+    const sumcheck::Geometry ge = sumcheck::geometry_of<T>(k, aligned);
+    const Shape sh = shape_of(mode, num_vars, tb.n, terms, n_terms);
+    return sumcheck::launch_plan<T>(p, ge, sh.count == 0, out, work, s, [&](uint64_t *dst) {
+        const dim3 g = ge.grid(p.groups), b(256);
+        const size_t groups = ge.groups(p.groups), lds = lds_bytes<T>(n_terms, coef != nullptr, ge.pair);
+        const Terms tm = pack_terms(terms, n_terms, n_tables);
+        const unsigned np_total = (unsigned)p.np_total;
+        for (unsigned t0 = 0; t0 < np_total; t0 += (unsigned)p.np_launch) {
+            const unsigned np = np_total - t0 < (unsigned)p.np_launch ? np_total - t0 : (unsigned)p.np_launch;
+            const auto one = [&](auto nt, auto round) {  // round: a round message (PAIR) or the plain sum
+                constexpr int NT = decltype(nt)::value;
+                constexpr bool PAIR = decltype(round)::value;
+                constexpr int NP = PAIR ? points_of<T>(NT) : 1;
+                if constexpr (sumcheck::kSlot<T>)
+                    hipLaunchKernelGGL((slot_round_kernel<T, NT, NP, PAIR>), g, b, lds, s, kc, dst, tb, tm, coef, sh.count, sh.sb, sh.st, groups, t0, np,
+                                       np_total);
+                else
+                    hipLaunchKernelGGL((round_kernel<T, NT, NP, PAIR>), g, b, lds, s, dst, tb, tm, coef, sh.count, sh.sb, sh.st, ge.k, ge.pair, groups,
+                                       t0, np, np_total);
+            };
+            with_slots(n_tables, [&](auto nt) {
+                if (mode == MODE_SUM) one(nt, std::false_type{});
+                else one(nt, std::true_type{});
+            });
+        }
+    });
 }
 
 }  // namespace vpoly

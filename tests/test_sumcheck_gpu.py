@@ -227,10 +227,16 @@ def test_all_p_minus_one_tables_pass_two_lazy_reduction_intervals(torch_cuda, na
     torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize("name,k,nv", [("goldilocks", 6, 10), ("babybear", 5, 9)])
+# The last two plan two records and sit on the boundaries of the launch geometry: aligned, an element of 2^8 Goldilocks coefficients
+# is 128 units and two lane-groups of a workgroup meet in LDS, shifted it is 256 units and a lane-group is a record of its own;
+# aligned, an element of 2^9 BabyBear coefficients is 256 units, shifted 512, the same two records with twice the lanes.
+OFF_BY_EIGHT = [("goldilocks", 6, 10), ("babybear", 5, 9), ("goldilocks", 8, 7), ("babybear", 9, 6)]
+
+
+@pytest.mark.parametrize("name,k,nv", OFF_BY_EIGHT)
 def test_tables_off_by_eight_bytes_take_the_one_coefficient_path_to_the_same_result(torch_cuda, name, k, nv):
     torch = torch_cuda
-    ring = ring_for(name, k)
+    m, ring = model_for(name, k), ring_for(name, k)
     tabs = tables_for(name, k, nv)[:3]
     aligned = [dev(torch, t) for t in tabs]
     shifted = []
@@ -241,6 +247,7 @@ def test_tables_off_by_eight_bytes_take_the_one_coefficient_path_to_the_same_res
         shifted.append(buf[1:])
     for mode in MODES:
         a = host(round_dev(torch, ring, aligned, nv, mode))
+        assert agrees(m, a, elems_for(name, k, nv)[:3], nv, mode), (name, mode)  # equal to each other could hide a common error
         assert np.array_equal(host(round_dev(torch, ring, shifted, nv, mode)), a), (name, mode)
         assert np.array_equal(host(round_dev(torch, ring, [aligned[0], shifted[1], aligned[2]], nv, mode)), a), (name, mode)
 

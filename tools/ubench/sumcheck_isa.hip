@@ -5,15 +5,14 @@
 #include "../../stark_rings_amd/csrc/stark_lazy.hpp"
 #include "../../stark_rings_amd/csrc/sumcheck.hpp"
 using namespace sr;
-#define POW2(F)                                                                                                                          \
-    template hipError_t sumcheck::launch<F>(const sumcheck::Plan &, int, uint64_t *, const sumcheck::Tables &, int, size_t, const size_t *, int, \
-                                            bool, uint64_t *, hipStream_t);
+#define LAUNCHER(T)                                                                                                                   \
+    template hipError_t sumcheck::launch<T>(const sumcheck::Family<T>::K &, const sumcheck::Plan &, int, uint64_t *, const sumcheck::Tables &, int, \
+                                            size_t, int, bool, uint64_t *, hipStream_t);
+#define POW2(F) LAUNCHER(F)
 POW2(Goldilocks)
 POW2(BabyBear)
 POW2(Stark)
-#define SLOT(SL)                                                                                                                         \
-    template hipError_t sumcheck::launch_slot<SL>(const SL::K &, const sumcheck::Plan &, int, uint64_t *, const sumcheck::Tables &, int, size_t, \
-                                                  const size_t *, uint64_t *, hipStream_t);
+#define SLOT(SL) LAUNCHER(SL)
 SLOT(SlotG24)
 SLOT(SlotB72)
 SLOT(SlotFrog)
