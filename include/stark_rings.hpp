@@ -30,7 +30,9 @@
 //     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations;
 //                                                                      round_evals / product_sum: a sum-check round's message (sr_mle_round_evals)
 //   a sum of products of dense MLEs      (HyperPlonk's VirtualPolynomial) class VirtualPolynomial: add_mle_list, mul_by_mle, degree, round_evals, sum
-//                                                                      (sr_vpoly_round_evals: one pass, every distinct table read once)
+//                                                                      (sr_vpoly_round_evals: one pass, every distinct table read once),
+//                                                                      fold_round_evals (sr_vpoly_round_fold_evals: fold at the challenge
+//                                                                      and the next message in one pass), fixed_variables
 //   SparseMultilinearExtension<RqNTT>    crates/poly mle/sparse.rs   class SparseMultilinearExtension: from_slice, from_matrix, fix_variables,
 //     precompute_eq                      sparse.rs:381-394             fixed_variables, evaluate, to_evaluations; eq_table(point); device
 //                                                                      pointers: CyclotomicConfig::eq_table_dev / smle_plan / smle_fix_variables_dev
@@ -577,8 +579,79 @@ public:
     }
     // sum_b g(b) over the hypercube: the claimed sum of the sum-check, one ring element
     RqNTTVec sum() const { return call(SR_MLE_ROUND_SUM); }
+    // One prover round in one pass over the distinct tables (sr_vpoly_round_fold_evals): every table slot with its next variable fixed at
+    // the ring element r, and the message of the round that follows: {message, the polynomial of the same terms and coefficients over
+    // the folded tables in num_vars() - 1 variables} -- what fixed_variables(r) followed by round_evals returns, bit for bit.  The
+    // returned polynomial owns its tables; the slots stay deduplicated.  Throws where the C call refuses (num_vars() < 2: the last round
+    // folds with fixed_variables).
+    std::pair<RqNTTVec, VirtualPolynomial> fold_round_evals(const RqNTTVec &r, int order = SR_MLE_LEADING) const {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("fold_round_evals: unknown order");
+        if (terms_.empty()) throw std::length_error("VirtualPolynomial: no product has been added");
+        if (r.len() != 1) throw std::length_error("fold_round_evals: r is not one ring element");
+        if (nv_ < 2) throw std::length_error("fold_round_evals: num_vars >= 2");
+        const size_t w = cfg_.words_per_elem();
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        std::vector<std::vector<uint64_t>> folded;
+        std::vector<uint64_t *> optrs;
+        for (const DenseMultilinearExtension *t : tables_) {
+            ptrs.push_back(t->words().empty() ? nullptr : t->words().data());
+            sizes.push_back(t->len());
+            folded.emplace_back(t->words().size());  // never shorter than the folded table
+        }
+        for (auto &f : folded) optrs.push_back(f.empty() ? nullptr : f.data());
+        std::vector<size_t> n_out(tables_.size());
+        std::vector<uint64_t> out(w * (degree() + 1));
+        const std::vector<uint64_t> coeffs = coeff_words();
+        CyclotomicConfig::check(sr_vpoly_round_fold_evals(cfg_.raw(), out.data(), optrs.data(), n_out.data(), ptrs.data(), sizes.data(),
+                                                          (int)tables_.size(), terms_.data(), (int)terms_.size(),
+                                                          coeffs.empty() ? nullptr : coeffs.data(), nv_, r.words().data(), order),
+                                "sr_vpoly_round_fold_evals");
+        std::vector<DenseMultilinearExtension> g;
+        for (size_t j = 0; j < tables_.size(); j++) {
+            folded[j].resize(n_out[j] * w);
+            g.emplace_back(cfg_, nv_ - 1, std::move(folded[j]));
+        }
+        return {RqNTTVec(cfg_, std::move(out)), over(std::move(g), nv_ - 1)};
+    }
+    // The polynomial of the same terms and coefficients with the variables of `point` fixed in every distinct table: fixed_variables
+    // (SR_MLE_LEADING) or fix_last_variables (SR_MLE_TRAILING) per table slot -- the last round of a sum-check, and callers that want no
+    // message.  The returned polynomial owns its tables.
+    VirtualPolynomial fixed_variables(const RqNTTVec &point, int order = SR_MLE_LEADING) const {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("fixed_variables: unknown order");
+        if (point.len() > nv_) throw std::length_error("too many partial points");
+        std::vector<DenseMultilinearExtension> g;
+        for (const DenseMultilinearExtension *t : tables_) g.push_back(order == SR_MLE_LEADING ? t->fixed_variables(point) : t->fix_last_variables(point));
+        return over(std::move(g), nv_ - point.len());
+    }
 
 private:
+    // the same terms and coefficients over `tables`, one per table slot, owned by the result
+    VirtualPolynomial over(std::vector<DenseMultilinearExtension> tables, size_t num_vars) const {
+        VirtualPolynomial g(cfg_, num_vars);
+        g.owned_ = std::make_shared<std::vector<DenseMultilinearExtension>>(std::move(tables));
+        for (const DenseMultilinearExtension &t : *g.owned_) g.tables_.push_back(&t);
+        g.terms_ = terms_;
+        g.has_coeff_ = has_coeff_;
+        g.coeffs_ = coeffs_;
+        return g;
+    }
+    // the coefficients of a call: empty where every coefficient is one() and none is passed
+    std::vector<uint64_t> coeff_words() const {
+        std::vector<uint64_t> coeffs;
+        bool any = false;
+        for (bool h : has_coeff_) any = any || h;
+        if (any) {
+            const uint64_t dummy = 0;
+            std::vector<uint64_t> one(cfg_.words_per_elem());  // the eq table of no variables is the single element one()
+            CyclotomicConfig::check(sr_eq_table(cfg_.raw(), one.data(), &dummy, 0), "sr_eq_table");
+            for (size_t k = 0; k < terms_.size(); k++) {
+                const std::vector<uint64_t> &c = has_coeff_[k] ? coeffs_[k] : one;
+                coeffs.insert(coeffs.end(), c.begin(), c.end());
+            }
+        }
+        return coeffs;
+    }
     int slot_of(std::vector<const DenseMultilinearExtension *> &slots, const DenseMultilinearExtension *m) const {
         if (m->config().raw() != cfg_.raw() || m->num_vars() != nv_) throw std::length_error("VirtualPolynomial: the MLEs differ in ring or num_vars");
         for (size_t j = 0; j < slots.size(); j++)
@@ -596,21 +669,10 @@ private:
             ptrs.push_back(t->words().empty() ? nullptr : t->words().data());
             sizes.push_back(t->len());
         }
-        std::vector<uint64_t> coeffs;  // empty: every coefficient is one() and none is passed
-        bool any = false;
-        for (bool h : has_coeff_) any = any || h;
-        if (any) {
-            const uint64_t dummy = 0;
-            std::vector<uint64_t> one(w);  // the eq table of no variables is the single element one()
-            CyclotomicConfig::check(sr_eq_table(cfg_.raw(), one.data(), &dummy, 0), "sr_eq_table");
-            for (size_t k = 0; k < terms_.size(); k++) {
-                const std::vector<uint64_t> &c = has_coeff_[k] ? coeffs_[k] : one;
-                coeffs.insert(coeffs.end(), c.begin(), c.end());
-            }
-        }
+        const std::vector<uint64_t> coeffs = coeff_words();
         std::vector<uint64_t> out(w * (mode == SR_MLE_ROUND_SUM ? 1 : degree() + 1));
         CyclotomicConfig::check(sr_vpoly_round_evals(cfg_.raw(), out.data(), ptrs.data(), sizes.data(), (int)tables_.size(), terms_.data(),
-                                                     (int)terms_.size(), any ? coeffs.data() : nullptr, nv_, mode),
+                                                     (int)terms_.size(), coeffs.empty() ? nullptr : coeffs.data(), nv_, mode),
                                 "sr_vpoly_round_evals");
         return RqNTTVec(cfg_, std::move(out));
     }
@@ -620,6 +682,7 @@ private:
     std::vector<sr_vpoly_term> terms_;
     std::vector<bool> has_coeff_;
     std::vector<std::vector<uint64_t>> coeffs_;
+    std::shared_ptr<std::vector<DenseMultilinearExtension>> owned_;  // the tables of a polynomial that fold_round_evals / fixed_variables made
 };
 
 // SparseMultilinearExtension<RqNTT> of crates/poly (src/mle/sparse.rs): the stored evaluations as ascending indices and their values

@@ -358,6 +358,42 @@ int sr_vpoly_round_evals_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *const
                              size_t work_elems, void *stream);
 int sr_vpoly_round_evals(sr_ctx *ctx, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                          const sr_vpoly_term *terms, int n_terms, const uint64_t *coeffs, size_t num_vars, int mode);
+/* A sum-check round of a SUM OF PRODUCTS in one pass (csrc/sumcheck_vpoly_fold.hpp): fold every distinct table slot at the challenge
+ * of the round that has just ended and compute the message of the round that follows while the folded neighbours are still in
+ * registers.  The contract is the conjunction of sr_mle_round_fold_evals_dev and sr_vpoly_round_evals_dev above:
+ *   d_out_tables[j]  exactly what sr_mle_fix_variables_dev(.., n_fixed = 1, order) writes for slot j at *d_r, in truncated storage:
+ *                    n_evals_out[j] = (n_evals[j] + 1) / 2 elements in leading order, min(n_evals[j], 2^(num_vars-1)) in trailing
+ *                    order; nothing beyond them is touched.  Every table is folded to ITS OWN length.
+ *   d_out[t]         t = 0 .. degree: bit-identical to sr_vpoly_round_evals_dev on the folded tables at num_vars - 1 with the same
+ *                    terms, coefficients and order.  One term with d_coeffs == NULL gives sr_mle_round_fold_evals_dev's message and
+ *                    tables bit for bit.
+ * order: SR_MLE_LEADING or SR_MLE_TRAILING; 2 <= num_vars < 48; the limits are SR_VPOLY_MAX_TABLES, SR_VPOLY_MAX_TERMS and
+ * SR_VPOLY_MAX_FACTORS; every ring id; canonical in, canonical out.  terms, d_tables, d_out_tables and n_evals are HOST arrays consumed
+ * at call time; n_evals_out is a HOST array filled at call time by host arithmetic.
+ * Empty tables: a term with an empty table contributes zero and the other tables are still folded and written; if every term has one
+ * the message is zero and no table is loaded for the products; if every table is empty one launch zeroes d_out.
+ * Aliasing: outputs may not overlap inputs, each other, d_r, d_coeffs, d_out or d_work, with one exception: in SR_MLE_TRAILING
+ * d_out_tables[j] == d_tables[j] folds slot j in place.  Two slots may hold the same input pointer; each then gets its own output and
+ * neither may be folded in place.
+ * The call allocates nothing and touches no context scratch; every workspace word is written before it is read; the launches are one
+ * linear chain on one stream, so the call is capturable on a fresh context.
+ * SR_E_INVALID (nothing launched, the reason in sr_last_error): every refusal of the two calls above, and d_coeffs overlapping a
+ * folded table.
+ * sr_vpoly_round_fold_plan: pure host arithmetic, no device, no context; the records are those of sr_vpoly_round_plan at
+ * num_vars - 1.  *work_elems == 0 exactly when *launches == 1; *work_elems <= SR_MLE_ROUND_MAX_GROUPS * (degree + 1).  The fused launch
+ * takes the first points -- over 4 / 8 table slots: Goldilocks 5 / 4, BabyBear 5 / 3, Stark 2 / 1, goldilocks24 2 / 1, babybear72 1 / 0
+ * (over 8 slots the fused launch only folds), frog16 1 / 1 -- and the remaining ones come from the round kernels of
+ * sr_vpoly_round_evals_dev over the FOLDED tables (half the size), into the same records; such a plan always uses the workspace.
+ * The host-pointer form stages like sr_mle_round_fold_evals. */
+int sr_vpoly_round_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order,
+                             size_t *work_elems, int *launches);
+int sr_vpoly_round_fold_evals_dev(sr_ctx *ctx, uint64_t *d_out, uint64_t *const *d_out_tables, size_t *n_evals_out,
+                                  const uint64_t *const *d_tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
+                                  int n_terms, const uint64_t *d_coeffs, size_t num_vars, const uint64_t *d_r, int order, uint64_t *d_work,
+                                  size_t work_elems, void *stream);
+int sr_vpoly_round_fold_evals(sr_ctx *ctx, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
+                              const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coeffs,
+                              size_t num_vars, const uint64_t *r, int order);
 /* Sparse multilinear extensions: the arithmetic of crates/poly's SparseMultilinearExtension (mle/sparse.rs) on device-resident
  * values.  Elements are ring elements in CRT / NTT form in the usual flat layout, canonical in and canonical out, for every ring id.
  *

@@ -36,6 +36,7 @@
 #include "sumcheck.hpp"
 #include "sumcheck_fold.hpp"
 #include "sumcheck_vpoly.hpp"
+#include "sumcheck_vpoly_fold.hpp"
 
 namespace {
 
@@ -1589,15 +1590,15 @@ int check_mle(sr_ctx *c, const void *out, const void *evals, size_t n_evals, siz
     return check_count(c, p.work_elems);
 }
 
-// ---- sum-check round messages (csrc/sumcheck.hpp, sumcheck_fold.hpp, sumcheck_vpoly.hpp): every launch under K_POINTWISE, nothing
-// allocated, no context scratch.  The three families share the ring dispatch, the table collector and the argument checks.
+// ---- sum-check round messages (csrc/sumcheck.hpp, sumcheck_fold.hpp, sumcheck_vpoly.hpp, sumcheck_vpoly_fold.hpp): every launch under
+// K_POINTWISE, nothing allocated, no context scratch.  The four families share the ring dispatch, the table collector and the argument checks.
 struct RoundFamily {
     const char *name;  // the prefix of every message
     int max_tables;
     bool terms, fold;  // a sum of products (n_terms, degree); a fold as well (an order, no SR_MLE_ROUND_SUM, two variables)
 };
 const RoundFamily kMleRound{"mle_round", SR_MLE_ROUND_MAX_TABLES, false, false}, kVpolyRound{"vpoly_round", SR_VPOLY_MAX_TABLES, true, false},
-    kMleRoundFold{"mle_round_fold", SR_MLE_ROUND_MAX_TABLES, false, true};
+    kMleRoundFold{"mle_round_fold", SR_MLE_ROUND_MAX_TABLES, false, true}, kVpolyRoundFold{"vpoly_round_fold", SR_VPOLY_MAX_TABLES, true, true};
 extern "C++" {
 template <class T> struct FamilyType {
     using type = T;
@@ -1669,6 +1670,27 @@ int dev_mle_round_fold(sr_ctx *c, const sr::sumcheck_fold::Plan &p, int order, u
                                                                      work, st);
     });
 }
+// a sum of products: fold every distinct table slot at the challenge and the next round's message in one pass
+int dev_vpoly_round_fold(sr_ctx *c, const sr::vpoly_fold::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
+                         const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
+                         const uint64_t *coef, size_t num_vars, const uint64_t *r, uint64_t *work, hipStream_t st) {
+    sr::vpoly::Tables tb{};
+    sr::vpoly_fold::Folded fo{};
+    sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
+    uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)r | (uintptr_t)coef | (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int j = 0; j < n_tables; j++) {
+        fo.p[j] = out_tables[j];
+        bits |= (uintptr_t)out_tables[j];
+    }
+    for (int k = 0; k < n_terms; k++) {
+        tm[k].n_factors = terms[k].n_factors;
+        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
+    }
+    return round_dispatch(c, st, "vpoly round fold", [&](auto t, const auto &kc) {
+        return sr::vpoly_fold::launch<typename decltype(t)::type>(kc, p, order, out, tb, fo, r, n_tables, tm, n_terms, coef, num_vars, n_out, c->k,
+                                                                  (bits & 15u) == 0, work, st);
+    });
+}
 // a refusal of family f: the message is assembled here, on the failing path only
 int refuse(const RoundFamily &f, const std::string &what) { return fail(SR_E_INVALID, std::string(f.name) + ": " + what); }
 // the shape checks the *_plan call and the two forms of the *_evals call of a family share (n_terms, degree: families with terms)
@@ -1683,12 +1705,13 @@ int round_plan_for(const RoundFamily &f, int ring, int k, size_t num_vars, int n
     if (num_vars >= 48) return refuse(f, "num_vars must be below 48");
     if (f.fold && num_vars < 2) return refuse(f, "num_vars >= 2 (the folded tables need a variable for the next round)");
     if (num_vars == 0 && mode != SR_MLE_ROUND_SUM) return refuse(f, "a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
-    const bool ok = f.fold    ? sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, mode, p)
+    const bool ok = f.fold    ? (f.terms ? sr::vpoly_fold::plan(ring, k, num_vars, n_tables, degree, mode, p)
+                                         : sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, mode, p))
                     : f.terms ? sr::vpoly::plan(ring, k, num_vars, n_tables, degree, mode, p)
                               : sr::sumcheck::plan(ring, k, num_vars, n_tables, mode, p);
     return ok ? (int)SR_OK : refuse(f, "no plan for these arguments");
 }
-// the body of the three *_plan entry points
+// the body of the four *_plan entry points
 int round_plan_entry(const RoundFamily &f, int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int mode,
                      size_t *work_elems, int *launches) {
     if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
@@ -1700,7 +1723,7 @@ int round_plan_entry(const RoundFamily &f, int ring, int log2_degree, size_t num
     *launches = p.launches;
     return SR_OK;
 }
-// the per-table checks of the three families; out_tables: the fold's outputs, null otherwise
+// the per-table checks of the four families; out_tables: the fold's outputs, null otherwise
 int check_round_tables(sr_ctx *c, const RoundFamily &f, const uint64_t *const *tables, uint64_t *const *out_tables, const size_t *n_evals,
                        int n_tables, size_t num_vars) {
     for (int j = 0; j < n_tables; j++) {
@@ -1718,12 +1741,12 @@ int check_mle_round(sr_ctx *c, const void *out, const uint64_t *const *tables, c
     if (int rc = round_plan_for(kMleRound, c->ring, c->k, num_vars, n_tables, 0, 0, mode, p)) return rc;
     return check_round_tables(c, kMleRound, tables, nullptr, n_evals, n_tables, num_vars);
 }
-// the argument checks the two forms of sr_vpoly_round_evals share
-int check_vpoly_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
-                      int n_terms, size_t num_vars, int mode, sr::vpoly::Plan *p) {
-    const RoundFamily &f = kVpolyRound;
+// the argument checks of the two families with terms (f: kVpolyRound, or kVpolyRoundFold with its outputs and r)
+int check_vpoly_terms(sr_ctx *c, const RoundFamily &f, const void *out, uint64_t *const *out_tables, const size_t *n_out, const void *r,
+                      const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, size_t num_vars,
+                      int mode, sr::vpoly::Plan *p) {
     if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !tables || !n_evals || !terms) return refuse(f, "null pointer");
+    if (!out || !tables || !n_evals || !terms || (f.fold && (!out_tables || !n_out || !r))) return refuse(f, "null pointer");
     if (n_tables < 1 || n_tables > f.max_tables) return refuse(f, "n_tables must be 1 .. " + std::to_string(f.max_tables));
     if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return refuse(f, "n_terms must be 1 .. 8");
     int degree = 0;
@@ -1740,7 +1763,18 @@ int check_vpoly_round(sr_ctx *c, const void *out, const uint64_t *const *tables,
     }
     if (used != (1u << n_tables) - 1) return refuse(f, "a table that no term uses");
     if (int rc = round_plan_for(f, c->ring, c->k, num_vars, n_tables, n_terms, degree, mode, p)) return rc;
-    return check_round_tables(c, f, tables, nullptr, n_evals, n_tables, num_vars);
+    return check_round_tables(c, f, tables, f.fold ? out_tables : nullptr, n_evals, n_tables, num_vars);
+}
+// the argument checks the two forms of sr_vpoly_round_evals share
+int check_vpoly_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
+                      int n_terms, size_t num_vars, int mode, sr::vpoly::Plan *p) {
+    return check_vpoly_terms(c, kVpolyRound, out, nullptr, nullptr, nullptr, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, p);
+}
+// the argument checks the two forms of sr_vpoly_round_fold_evals share
+int check_vpoly_round_fold(sr_ctx *c, const void *out, uint64_t *const *out_tables, const size_t *n_out, const uint64_t *const *tables,
+                           const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, size_t num_vars, const void *r, int order,
+                           sr::vpoly_fold::Plan *p) {
+    return check_vpoly_terms(c, kVpolyRoundFold, out, out_tables, n_out, r, tables, n_evals, n_tables, terms, n_terms, num_vars, order, p);
 }
 // the argument checks the two forms of sr_mle_round_fold_evals share
 int check_mle_round_fold(sr_ctx *c, const void *out, uint64_t *const *out_tables, const size_t *n_out, const uint64_t *const *tables,
@@ -1761,6 +1795,43 @@ int check_round_work(const RoundFamily &f, const sr::sumcheck::Plan &p, const ui
 size_t round_fold_n_out(size_t n, size_t num_vars, int order) {
     const size_t half = (size_t)1 << (num_vars - 1);
     return order == SR_MLE_LEADING ? (n + 1) / 2 : (n < half ? n : half);
+}
+
+// the aliasing rules of the two fold families: outputs overlap nothing but, in trailing order, their own input (coef, cw: the
+// coefficients of a sum of products and their bytes, or null and 0)
+int check_fold_overlaps(const RoundFamily &f, const sr::sumcheck::Plan &p, size_t w, const uint64_t *out, uint64_t *const *out_tables,
+                        const size_t *n_out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const uint64_t *coef, size_t cw,
+                        const uint64_t *r, int order, const uint64_t *work) {
+    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return refuse(f, "d_out overlaps d_work");
+    if (ranges_overlap(out, p.np_total * w, r, w)) return refuse(f, "d_out overlaps d_r");
+    if (ranges_overlap(work, p.work_elems * w, r, w)) return refuse(f, "d_work overlaps d_r");
+    if (ranges_overlap(out, p.np_total * w, coef, cw)) return refuse(f, "d_out overlaps d_coeffs");
+    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return refuse(f, "d_work overlaps d_coeffs");
+    if (ranges_overlap(r, w, coef, cw)) return refuse(f, "d_r overlaps d_coeffs");
+    for (int j = 0; j < n_tables; j++) {
+        if (ranges_overlap(coef, cw, tables[j], n_evals[j] * w)) return refuse(f, "d_coeffs overlaps a table");
+        if (ranges_overlap(coef, cw, out_tables[j], n_out[j] * w)) return refuse(f, "d_coeffs overlaps a folded table");
+        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return refuse(f, "d_out overlaps a table");
+        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return refuse(f, "d_work overlaps a table");
+        if (ranges_overlap(r, w, tables[j], n_evals[j] * w)) return refuse(f, "d_r overlaps a table");
+        if (ranges_overlap(out, p.np_total * w, out_tables[j], n_out[j] * w)) return refuse(f, "d_out overlaps a folded table");
+        if (ranges_overlap(work, p.work_elems * w, out_tables[j], n_out[j] * w))
+            return refuse(f, "d_work overlaps a folded table");
+        if (ranges_overlap(r, w, out_tables[j], n_out[j] * w)) return refuse(f, "d_r overlaps a folded table");
+        for (int i = 0; i < j; i++)
+            if (ranges_overlap(out_tables[i], n_out[i] * w, out_tables[j], n_out[j] * w))
+                return refuse(f, "two folded tables overlap");
+        for (int i = 0; i < n_tables; i++) {
+            if (!ranges_overlap(out_tables[j], n_out[j] * w, tables[i], n_evals[i] * w)) continue;
+            // in place: the table's own output only, trailing order only, and no other input may be that table (it would be folded twice)
+            if (order != SR_MLE_TRAILING || out_tables[j] != tables[j])
+                return refuse(f,
+                            "a folded table overlaps an input table (only a trailing-order fold may run in place, with "
+                            "d_out_tables[j] == d_tables[j])");
+            if (i != j) return refuse(f, "an input table that appears twice cannot be folded in place");
+        }
+    }
+    return SR_OK;
 }
 
 // ---- sparse multilinear extensions (csrc/sparse_mle.hpp): nothing allocated, no context scratch ----------------------------------
@@ -2645,30 +2716,7 @@ int sr_mle_round_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_t
     const size_t w = (size_t)c->degree * c->limbs * 8;
     size_t n_out[SR_MLE_ROUND_MAX_TABLES];
     for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
-    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps d_work");
-    if (ranges_overlap(out, p.np_total * w, r, w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps d_r");
-    if (ranges_overlap(work, p.work_elems * w, r, w)) return fail(SR_E_INVALID, "mle_round_fold: d_work overlaps d_r");
-    for (int j = 0; j < n_tables; j++) {
-        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps a table");
-        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_work overlaps a table");
-        if (ranges_overlap(r, w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_r overlaps a table");
-        if (ranges_overlap(out, p.np_total * w, out_tables[j], n_out[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_out overlaps a folded table");
-        if (ranges_overlap(work, p.work_elems * w, out_tables[j], n_out[j] * w))
-            return fail(SR_E_INVALID, "mle_round_fold: d_work overlaps a folded table");
-        if (ranges_overlap(r, w, out_tables[j], n_out[j] * w)) return fail(SR_E_INVALID, "mle_round_fold: d_r overlaps a folded table");
-        for (int i = 0; i < j; i++)
-            if (ranges_overlap(out_tables[i], n_out[i] * w, out_tables[j], n_out[j] * w))
-                return fail(SR_E_INVALID, "mle_round_fold: two folded tables overlap");
-        for (int i = 0; i < n_tables; i++) {
-            if (!ranges_overlap(out_tables[j], n_out[j] * w, tables[i], n_evals[i] * w)) continue;
-            // in place: the table's own output only, trailing order only, and no other input may be that table (it would be folded twice)
-            if (order != SR_MLE_TRAILING || out_tables[j] != tables[j])
-                return fail(SR_E_INVALID,
-                            "mle_round_fold: a folded table overlaps an input table (only a trailing-order fold may run in place, with "
-                            "d_out_tables[j] == d_tables[j])");
-            if (i != j) return fail(SR_E_INVALID, "mle_round_fold: an input table that appears twice cannot be folded in place");
-        }
-    }
+    if (int rc = check_fold_overlaps(kMleRoundFold, p, w, out, out_tables, n_out, tables, n_evals, n_tables, nullptr, 0, r, order, work)) return rc;
     const Call call(c, stream);
     return dev_mle_round_fold(c, p, order, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, work, call.st);
 }
@@ -2691,6 +2739,56 @@ int sr_mle_round_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_table
                       if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
                       if (int rc = dev_mle_round_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dt, n_evals, n_tables, num_vars,
                                                       (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
+                          return rc;
+                      for (int j = 0; j < n_tables; j++)
+                          if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
+                      return SR_OK;
+                  });
+}
+int sr_vpoly_round_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order, size_t *work_elems,
+                             int *launches) {
+    return round_plan_entry(kVpolyRoundFold, ring, log2_degree, num_vars, n_tables, n_terms, degree, order, work_elems, launches);
+}
+int sr_vpoly_round_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
+                                  const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef,
+                                  size_t num_vars, const uint64_t *r, int order, uint64_t *work, size_t work_elems, void *stream) {
+    sr::vpoly_fold::Plan p;
+    if (int rc = check_vpoly_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, terms, n_terms, num_vars, r, order, &p)) return rc;
+    if (int rc = check_round_work(kVpolyRoundFold, p, work, work_elems)) return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    size_t n_out[SR_VPOLY_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
+    if (int rc = check_fold_overlaps(kVpolyRoundFold, p, w, out, out_tables, n_out, tables, n_evals, n_tables, coef, coef ? n_terms * w : 0, r, order,
+                                     work))
+        return rc;
+    const Call call(c, stream);
+    return dev_vpoly_round_fold(c, p, order, out, out_tables, n_evals_out, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, r, work, call.st);
+}
+int sr_vpoly_round_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
+                              const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars,
+                              const uint64_t *r, int order) {
+    sr::vpoly_fold::Plan p;
+    if (int rc = check_vpoly_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, terms, n_terms, num_vars, r, order, &p)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    size_t n_out[SR_VPOLY_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
+    const TableSlot in(n_evals, n_tables, w), folded(n_out, n_tables, w);
+    // HOST_0: the tables; HOST_1: the message; HOST_2: the workspace; HOST_3: the folded tables; HOST_4: r, then (on the next 16-byte
+    // boundary) the coefficients
+    const size_t coef_at = (w + 15) & ~(size_t)15, cw = coef ? n_terms * w : 0;
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {nullptr, nullptr, folded.total},
+                      {nullptr, nullptr, coef_at + cw}},
+                  [&](void *const *d) -> int {
+                      uint64_t *dt[SR_VPOLY_MAX_TABLES], *dout[SR_VPOLY_MAX_TABLES];
+                      in.at(d[0], n_tables, dt);
+                      folded.at(d[3], n_tables, dout);
+                      const uint64_t *dcoef = coef ? (const uint64_t *)((const char *)d[4] + coef_at) : nullptr;
+                      HIP_TRY(hipMemcpyAsync(d[4], r, w, hipMemcpyHostToDevice, c->stream));
+                      if (coef) HIP_TRY(hipMemcpyAsync((void *)dcoef, coef, cw, hipMemcpyHostToDevice, c->stream));
+                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
+                      if (int rc = dev_vpoly_round_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dt, n_evals, n_tables, terms, n_terms, dcoef,
+                                                        num_vars, (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
                           return rc;
                       for (int j = 0; j < n_tables; j++)
                           if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));

@@ -294,6 +294,57 @@ class VirtualPolynomial:
         """sum_b g(b) over the hypercube as one ring element: the claimed sum of the sum-check."""
         return self._call(MLE_ROUND_SUM, stream)
 
+    def _over(self, tables, num_vars):
+        """the same terms and coefficients over `tables`, one per table slot of this polynomial: the slots stay deduplicated"""
+        g = VirtualPolynomial(self.ring, num_vars)
+        g.tables = list(tables)
+        g.terms = [list(t) for t in self.terms]
+        g.coeffs = list(self.coeffs)
+        g._slot = {(t.evaluations.data_ptr() if len(t) else ("empty", id(t))): j for j, t in enumerate(g.tables)}
+        return g
+
+    def fold_round_evals(self, r, order=MLE_LEADING, stream=None):
+        """One prover round in one pass over the distinct tables (sr_vpoly_round_fold_evals_dev): every table slot with the variable
+        fix_variables (MLE_LEADING) or fix_last_variables (MLE_TRAILING) fixes next set to the ring element `r`, and the message of
+        the round that follows.  Returns (message, the polynomial of the same terms and coefficients over the folded tables, in
+        num_vars - 1 variables): what fixed_variables(r) followed by round_evals returns, bit for bit.  num_vars >= 2; the last
+        round folds with fixed_variables."""
+        import torch
+
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("fold_round_evals: unknown order")
+        if not self.terms:
+            raise RingError("VirtualPolynomial: no product has been added")
+        ring, nv = self.ring, self._num_vars
+        if nv < 2:
+            raise RingError("fold_round_evals: num_vars >= 2 (the last round folds with fixed_variables)")
+        like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
+        w = ring.words_per_elem
+        out = torch.empty((self.degree + 1) * w, dtype=like.dtype, device=like.device)
+        sizes = [(len(t) + 1) // 2 if order == MLE_LEADING else min(len(t), 1 << (nv - 1)) for t in self.tables]
+        folded = [torch.empty(n * w, dtype=like.dtype, device=like.device) for n in sizes]
+        need = ring.vpoly_round_fold_plan(nv, len(self.tables), len(self.terms), self.degree, order)[0]
+        work = torch.empty(need * w, dtype=like.dtype, device=like.device) if need else None
+        coeffs = self._coeff_tensor(like, stream)
+        if stream is not None:
+            for t in folded + [work, coeffs]:
+                if t is not None:
+                    t.record_stream(stream)
+        ring.vpoly_round_fold_evals_dev(out, folded, [t.evaluations for t in self.tables], self.terms, coeffs, nv, r, order, work, stream)
+        return out, self._over([DenseMultilinearExtension(ring, nv - 1, f) for f in folded], nv - 1)
+
+    def fixed_variables(self, point, order=MLE_LEADING, stream=None):
+        """The polynomial of the same terms and coefficients with the variables of `point` fixed in every distinct table:
+        fixed_variables (MLE_LEADING) or fix_last_variables (MLE_TRAILING) per table slot -- the last round of a sum-check, and
+        callers that want no message."""
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("fixed_variables: unknown order")
+        n_fixed = self.ring._batch_of(point.numel())
+        if n_fixed > self._num_vars:
+            raise RingError("fixed_variables: the point has more entries than the polynomial has variables")
+        fold = (lambda t: t.fixed_variables(point, stream)) if order == MLE_LEADING else (lambda t: t.fix_last_variables(point, stream))
+        return self._over([fold(t) for t in self.tables], self._num_vars - n_fixed)
+
 
 def _next_pow2(n):
     return 1 if n <= 1 else 1 << (n - 1).bit_length()

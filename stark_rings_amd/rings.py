@@ -1101,6 +1101,90 @@ class CyclotomicRing:
                                                       int(order)))
         return out, [f[:int(osizes[j]) * w] for j, f in enumerate(folded)]
 
+    def vpoly_round_fold_plan(self, num_vars, n_tables, n_terms, degree, order=MLE_LEADING):
+        """sr_vpoly_round_fold_plan: (work_elems, launches) of the fused fold-and-round call over a sum of n_terms products of at
+        most `degree` of n_tables tables of num_vars >= 2 variables -- host arithmetic only."""
+        work = ctypes.c_size_t()
+        launches = ctypes.c_int()
+        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
+        self._check(self._lib.sr_vpoly_round_fold_plan(self.ring, k, int(num_vars), int(n_tables), int(n_terms), int(degree), int(order),
+                                                       ctypes.byref(work), ctypes.byref(launches)))
+        return work.value, launches.value
+
+    def vpoly_round_fold_evals_dev(self, out, out_tables, tables, terms, coeffs, num_vars, r, order=MLE_LEADING, work=None, stream=None):
+        """sr_vpoly_round_fold_evals_dev: one pass that folds every table slot of `tables` (1 .. 8 CUDA tensors of n_evals <=
+        2^num_vars elements, num_vars >= 2) at the ring element `r` into out_tables[j] -- what mle_fix_variables_dev gives for one
+        variable, in truncated storage -- and writes to out[t], t = 0 .. d (d the longest term), the message of the next round of
+        g = sum_k c_k prod_s f_{terms[k][s]} over the folded tables (vpoly_round_evals_dev on them).  terms, coeffs: as in
+        vpoly_round_evals_dev.  out_tables[j] must hold at least the folded length; MLE_TRAILING may fold in place (out_tables[j] is
+        tables[j]).  Returns the list of elements written per table; nothing beyond them is touched.  work: a tensor of at least
+        vpoly_round_fold_plan()[0] elements (None only where the plan needs none).  Allocates nothing."""
+        po, no = self._dev(out)
+        n = len(tables)
+        arr, n_terms, d = self._vpoly_terms(terms)
+        if len(out_tables) != n:
+            raise RingError("vpoly_round_fold_evals: one output table per table")
+        if no != self.words_per_elem * (d + 1):
+            raise RingError("vpoly_round_fold_evals: out must hold d + 1 elements, d the longest term")
+        pr, nr = self._dev(r)
+        if nr != self.words_per_elem:
+            raise RingError("vpoly_round_fold_evals: r is not one ring element")
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        optrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        osizes = (ctypes.c_size_t * max(n, 1))()
+        for j, (t, o) in enumerate(zip(tables, out_tables)):
+            sizes[j] = self._batch_of(t.numel())
+            ptrs[j] = self._dev(t)[0] if t.numel() else None
+            optrs[j] = self._dev(o)[0] if o.numel() else None
+            if 2 <= num_vars < 48:
+                need = (sizes[j] + 1) // 2 if order == MLE_LEADING else min(sizes[j], 1 << (num_vars - 1))
+                if o.numel() < need * self.words_per_elem:
+                    raise RingError("vpoly_round_fold_evals: an output table is shorter than the folded table")
+        if coeffs is None:
+            pc = ctypes.c_void_p(0)
+        else:
+            pc, nc = self._dev(coeffs)
+            if nc != n_terms * self.words_per_elem:
+                raise RingError("vpoly_round_fold_evals: one coefficient per term")
+        if work is None:
+            pw, nw = ctypes.c_void_p(0), 0
+        else:
+            pw, nw = self._dev(work)
+            nw //= self.words_per_elem
+        self._check(self._lib.sr_vpoly_round_fold_evals_dev(self._ctx, po, optrs, osizes, ptrs, sizes, n, arr, n_terms, pc, int(num_vars), pr,
+                                                            int(order), pw, nw, self._stream(stream)))
+        return [int(osizes[j]) for j in range(n)]
+
+    def vpoly_round_fold_evals(self, tables, terms, coeffs, num_vars, r, order=MLE_LEADING):
+        """Host buffers: sr_vpoly_round_fold_evals (see vpoly_round_fold_evals_dev); returns (message, list of folded tables)."""
+        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+        r = np.ascontiguousarray(r, dtype=np.uint64)
+        n, w = len(tables), self.words_per_elem
+        arr, n_terms, d = self._vpoly_terms(terms)
+        if r.size != w:
+            raise RingError("vpoly_round_fold_evals: r is not one ring element")
+        out = np.empty(w * (max(d, 1) + 1), dtype=np.uint64)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        optrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        osizes = (ctypes.c_size_t * max(n, 1))()
+        folded = []
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.size)
+            ptrs[j] = t.ctypes.data if t.size else None
+            folded.append(np.empty(t.size, dtype=np.uint64))  # never shorter than the folded table
+            optrs[j] = folded[j].ctypes.data if t.size else None
+        pc = None
+        if coeffs is not None:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+            if coeffs.size != n_terms * w:
+                raise RingError("vpoly_round_fold_evals: one coefficient per term")
+            pc = coeffs.ctypes.data
+        self._check(self._lib.sr_vpoly_round_fold_evals(self._ctx, _np_ptr(out), optrs, osizes, ptrs, sizes, n, arr, n_terms, pc, int(num_vars),
+                                                        _np_ptr(r), int(order)))
+        return out, [f[:int(osizes[j]) * w] for j, f in enumerate(folded)]
+
     def eq_table_dev(self, out, point, stream=None):
         """sr_eq_table_dev: out[b] = prod_i (bit i of b ? point[i] : 1 - point[i]) for the n = len(point) elements of `point`
         (None or empty: out is the single element one()); out holds 2^n elements.  One launch, no workspace; capturable."""
