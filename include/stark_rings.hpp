@@ -531,6 +531,76 @@ inline RqNTTVec eq_table(const RqNTTVec &point) {
     return RqNTTVec(cfg, std::move(out));
 }
 
+// Every layer of the binary product tree over a table of ring elements in CRT/NTT form (sr_prod_tree): the circuit of the
+// division-free, layered grand-product argument.  Layer 0 is the 2^num_vars leaves (those beyond the stored ones are one()), layer k
+// has 2^(num_vars - k) elements, the root is layer num_vars.  SR_MLE_TRAILING: L_k[i] = L_{k-1}[i] * L_{k-1}[i + half], so the two
+// operands of a layer are the lower and upper halves of the layer below; SR_MLE_LEADING: L_k[i] = L_{k-1}[2i] * L_{k-1}[2i+1].
+// Host buffers; throws where the Python class raises.
+class ProductTree {
+public:
+    ProductTree(CyclotomicConfig cfg, std::vector<uint64_t> leaf_words, size_t num_vars, int order = SR_MLE_TRAILING)
+        : cfg_(std::move(cfg)), num_vars_(num_vars), order_(order), leaves_(std::move(leaf_words)) {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("ProductTree: unknown order");
+        if (leaves_.size() % cfg_.words_per_elem()) throw std::length_error("Should be of correct length");
+        if (num_vars_ >= 48 || n_leaves() > ((size_t)1 << num_vars_)) throw std::length_error("ProductTree: more leaves than 2^num_vars");
+        layers_.resize(cfg_.words_per_elem() * (((size_t)1 << num_vars_) - 1));
+        const uint64_t dummy = 0;
+        CyclotomicConfig::check(sr_prod_tree(cfg_.raw(), layers_.empty() ? nullptr : layers_.data(), leaves_.empty() ? &dummy : leaves_.data(),
+                                             n_leaves(), num_vars_, order_),
+                                "sr_prod_tree");
+    }
+    size_t num_vars() const { return num_vars_; }
+    size_t n_leaves() const { return leaves_.size() / cfg_.words_per_elem(); }  // stored leaves
+    int order() const { return order_; }
+    const std::vector<uint64_t> &layer_words() const { return layers_; }  // layers 1 .. num_vars, one behind the other
+    // element offset of layer k (1 <= k <= num_vars) in layer_words(): layer 1 first, the root last
+    size_t layer_offset(size_t k) const {
+        if (k < 1 || k > num_vars_) throw std::out_of_range("ProductTree: layer index out of range");
+        return ((size_t)1 << num_vars_) - ((size_t)1 << (num_vars_ - k + 1));
+    }
+    // layer k as an MLE in num_vars - k variables; k = 0 gives the leaves (every leaf must be stored: an MLE's missing tail is zero)
+    DenseMultilinearExtension layer(size_t k) const {
+        if (k > num_vars_) throw std::out_of_range("ProductTree: layer index out of range");
+        return DenseMultilinearExtension(cfg_, num_vars_ - k, table(k));
+    }
+    // the product of all leaves, one ring element
+    RqNTTVec root() const {
+        if (num_vars_ == 0 && leaves_.empty()) throw std::length_error("ProductTree: a tree of no variables and no stored leaf holds no element");
+        return RqNTTVec(cfg_, num_vars_ ? table(num_vars_) : leaves_);
+    }
+    // {lo, hi}: the lower and upper halves of layer k - 1 as MLEs in num_vars - k variables, layer(k) = lo * hi element by element
+    std::pair<DenseMultilinearExtension, DenseMultilinearExtension> halves(size_t k) const {
+        if (order_ != SR_MLE_TRAILING) throw std::invalid_argument("ProductTree::halves: only a trailing-order tree has contiguous operands");
+        if (k < 1 || k > num_vars_) throw std::out_of_range("ProductTree: layer index out of range");
+        const std::vector<uint64_t> below = table(k - 1);
+        const auto mid = below.begin() + below.size() / 2;
+        return {DenseMultilinearExtension(cfg_, num_vars_ - k, std::vector<uint64_t>(below.begin(), mid)),
+                DenseMultilinearExtension(cfg_, num_vars_ - k, std::vector<uint64_t>(mid, below.end()))};
+    }
+    // sr_prod_tree_plan: {elements of the layers, kernel launches} of the device form
+    static std::pair<size_t, int> plan(sr_ring ring, int log2_degree, size_t num_vars, int order = SR_MLE_TRAILING) {
+        size_t elems = 0;
+        int launches = 0;
+        CyclotomicConfig::check(sr_prod_tree_plan(ring, log2_degree, num_vars, order, &elems, &launches), "sr_prod_tree_plan");
+        return {elems, launches};
+    }
+
+private:
+    std::vector<uint64_t> table(size_t k) const {
+        if (k == 0) {
+            if (n_leaves() != ((size_t)1 << num_vars_))
+                throw std::length_error("ProductTree: layer 0 of a truncated tree is not a table (its missing leaves are one())");
+            return leaves_;
+        }
+        const size_t w = cfg_.words_per_elem(), off = layer_offset(k);
+        return std::vector<uint64_t>(layers_.begin() + off * w, layers_.begin() + (off + ((size_t)1 << (num_vars_ - k))) * w);
+    }
+    CyclotomicConfig cfg_;
+    size_t num_vars_;
+    int order_;
+    std::vector<uint64_t> leaves_, layers_;
+};
+
 // A sum of products of dense MLEs with ring coefficients, g = sum_k c_k prod_s f_{k,s}, after HyperPlonk's VirtualPolynomial (the code
 // crates/poly's polynomials/multilinear_polynomial.rs was adapted from): the object a sum-check is run on -- eq (a b - c),
 // sum_i alpha_i eq prod_j (...).  The MLEs are referred to, not copied, and must outlive the polynomial; an MLE that is in several

@@ -442,6 +442,27 @@ int sr_smle_fix_variables_dev(sr_ctx *ctx, uint64_t *d_out_vals, const uint64_t 
                               size_t work_elems, void *stream);
 int sr_smle_fix_variables(sr_ctx *ctx, uint64_t *out_vals, uint64_t *out_idx, size_t *n_out, const uint64_t *vals, const uint64_t *idx,
                           size_t nnz, size_t num_vars, const uint64_t *point, size_t n_fixed);
+/* Grand products (csrc/prod_tree.hpp): every layer of the binary product tree over a table of 2^num_vars ring elements in CRT/NTT form,
+ * the circuit of the division-free, layered product argument (each layer is proved from the one below by one sum-check of
+ * eq(z, .) * lo * hi; sr_vpoly_round_fold_evals_dev runs that claim).  `*` is the slot product of the ring, as in sr_product_batch.
+ * Layer 0 is the leaves; layer k (1 <= k <= num_vars) has half = 2^(num_vars - k) elements:
+ *   SR_MLE_LEADING   L_k[i] = L_{k-1}[2i] * L_{k-1}[2i+1]       the pairs sr_mle_fix_variables folds in leading order
+ *   SR_MLE_TRAILING  L_k[i] = L_{k-1}[i] * L_{k-1}[i + half]    the pairs it folds in trailing order: the two operands of a layer are the
+ *                    contiguous lower and upper halves of the layer below, usable as MLE tables as they lie
+ * d_leaves: n_leaves <= 2^num_vars elements; the leaves from n_leaves up to 2^num_vars are one() (what sr_product_batch returns for
+ * n = 0) and are NOT read; a group of leaves that begins at or beyond n_leaves is written as one() without any load.
+ * d_layers receives 2^num_vars - 1 elements, every layer in full, ones included: layer k at element offset
+ * 2^num_vars - 2^(num_vars - k + 1), layer 1 first, the root last.  Canonical inputs give canonical results.  The leaves are never
+ * written, and any overlap of d_layers and the stored leaves is SR_E_INVALID.
+ * The library allocates nothing and touches no context scratch (later launches read the layer an earlier launch of the same call
+ * wrote), so the call can be captured into a HIP graph on any stream without a warm-up.
+ * sr_prod_tree_plan: pure host arithmetic, no device, no context -- *layer_elems = 2^num_vars - 1 and the kernel launches of the call:
+ * a launch reads each group of leaves once and writes up to three levels (two for babybear72: registers), full launches first, the
+ * remainder last.  num_vars < 48; num_vars = 0 is no launch and nothing written.
+ * The host-pointer form stages like sr_sum_batch: leaves and layers live in context-owned device temporaries for the call. */
+int sr_prod_tree_plan(int ring, int log2_degree, size_t num_vars, int order, size_t *layer_elems, int *launches);
+int sr_prod_tree_dev(sr_ctx *ctx, uint64_t *d_layers, const uint64_t *d_leaves, size_t n_leaves, size_t num_vars, int order, void *stream);
+int sr_prod_tree(sr_ctx *ctx, uint64_t *layers, const uint64_t *leaves, size_t n_leaves, size_t num_vars, int order);
 /* Norms of a coefficient slice on the device: WithLinfNorm::linf_norm / WithL2Norm::l2_norm_squared over [Fq]
  * (crates/ring/src/traits.rs:6-36; per element balanced_decomposition/convertible_ring.rs:49-66; the signed representative of
  * fq_convertible.rs:20-34 and stark_prime/decomposition.rs:40-52).

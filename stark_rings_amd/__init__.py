@@ -8,6 +8,7 @@ Layout:
   wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix / SymmetricMatrix around the device codec
   mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values,
                         with the round message of a sum-check over a product, or a sum of products (VirtualPolynomial), of dense MLEs
+  grand_product.py      ProductTree: every layer of a table's binary product tree, the circuit of the layered grand-product argument
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
   sparse.py             SparseMatrix of crates/linear_algebra with device-resident values: transpose, sparse x sparse product
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
@@ -26,5 +27,6 @@ from .rings import (  # noqa: F401
     RingError,
 )
 from .mle import DenseMultilinearExtension, SparseMultilinearExtension, VirtualPolynomial  # noqa: F401
+from .grand_product import ProductTree  # noqa: F401
 from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401
 from .sparse import SparseMatrixNTT  # noqa: F401

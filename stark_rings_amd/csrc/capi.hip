@@ -37,6 +37,7 @@
 #include "sumcheck_fold.hpp"
 #include "sumcheck_vpoly.hpp"
 #include "sumcheck_vpoly_fold.hpp"
+#include "prod_tree.hpp"
 
 namespace {
 
@@ -2064,6 +2065,50 @@ int check_fold(sr_ctx *c, const uint64_t *out, const uint64_t *in, size_t n) {
     if (n && po + w > pi && pi + n * w > po) return fail(SR_E_INVALID, "sum / product: out must not overlap the input elements");
     return SR_OK;
 }
+// ---- grand products (csrc/prod_tree.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch ----------------------
+// The launches of sr::ptree::plan, one after the other on `st`: launch l reads the last layer launch l - 1 wrote (the leaves for the
+// first) and writes its levels behind it.  Every layer is written in full, so only the first launch sees a truncated input.
+int dev_prod_tree(sr_ctx *c, uint64_t *layers, const uint64_t *leaves, size_t n_leaves, size_t num_vars, int order, hipStream_t st) {
+    sr::ptree::Plan p;
+    if (!sr::ptree::plan(c->ring, num_vars, order, &p)) return fail(SR_E_INVALID, "prod_tree: no plan for these arguments");
+    const size_t w = (size_t)c->degree * c->limbs;
+    const bool tr = order == sr::mle::ORDER_TRAILING;
+    const sr::smle::One one = smle_one(c);
+    const uint64_t *src = leaves;
+    size_t n_in = n_leaves, done = 0;
+    for (int l = 0; l < p.launches; l++) {
+        const int j = p.j[l], m = (int)(num_vars - done);
+        uint64_t *dst = layers + sr::ptree::layer_offset(num_vars, done + 1) * w;
+        ProfScope ps(c, st, K_POINTWISE);
+        hipError_t e;
+        switch (c->ring) {
+            case SR_RING_GOLDILOCKS_POW2: e = sr::ptree::launch_tree<sr::Goldilocks>(j, dst, src, one, n_in, m, tr, c->k, st); break;
+            case SR_RING_BABYBEAR_POW2: e = sr::ptree::launch_tree<sr::BabyBear>(j, dst, src, one, n_in, m, tr, c->k, st); break;
+            case SR_RING_STARK_POW2: e = sr::ptree::launch_tree<sr::Stark>(j, dst, src, one, n_in, m, tr, c->k, st); break;
+            case SR_RING_GOLDILOCKS_24: e = sr::ptree::launch_slot_tree<sr::SlotG24>(c->small, j, dst, src, one, n_in, m, tr, st); break;
+            case SR_RING_BABYBEAR_72: e = sr::ptree::launch_slot_tree<sr::SlotB72>(c->small, j, dst, src, one, n_in, m, tr, st); break;
+            default: e = sr::ptree::launch_slot_tree<sr::SlotFrog>(c->frog, j, dst, src, one, n_in, m, tr, st); break;
+        }
+        if (e != hipSuccess) return fail(SR_E_HIP, std::string("prod_tree launch: ") + hipGetErrorString(e));
+        done += j;
+        src = layers + sr::ptree::layer_offset(num_vars, done) * w;  // the last level of this launch
+        n_in = (size_t)1 << (num_vars - done);
+    }
+    return SR_OK;
+}
+// the argument checks the two forms of sr_prod_tree share
+int check_prod_tree(sr_ctx *c, const void *layers, const void *leaves, size_t n_leaves, size_t num_vars, int order) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) return fail(SR_E_INVALID, "prod_tree: unknown order");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "prod_tree: num_vars must be below 48");
+    if (n_leaves > (size_t)1 << num_vars) return fail(SR_E_INVALID, "prod_tree: n_leaves exceeds 2^num_vars");
+    if (int rc = check_count(c, (size_t)1 << num_vars)) return rc;
+    if ((num_vars && !layers) || (n_leaves && !leaves)) return fail(SR_E_INVALID, "prod_tree: null buffer");
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    if (ranges_overlap(layers, (((size_t)1 << num_vars) - 1) * w, leaves, n_leaves * w))
+        return fail(SR_E_INVALID, "prod_tree: d_layers overlaps d_leaves");
+    return SR_OK;
+}
 // d_counter[i] (sr_ctx_create_ex) to the host, then cleared
 int read_counter(sr_ctx *c, int i, unsigned long long *out, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(out, c->d_counter + i, sizeof *out, hipMemcpyDeviceToHost, st));
@@ -2632,6 +2677,30 @@ int sr_mle_fix_variables(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t
                       return dev_mle_fix(c, (uint64_t *)d[2], (const uint64_t *)d[0], n_evals, num_vars, (const uint64_t *)d[1], n_fixed, order,
                                          (uint64_t *)d[3], c->stream);
                   });
+}
+int sr_prod_tree_plan(int ring, int log2_degree, size_t num_vars, int order, size_t *layer_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!layer_elems || !launches) return fail(SR_E_INVALID, "prod_tree_plan: null result pointer");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "prod_tree_plan: num_vars must be below 48");
+    sr::ptree::Plan p;
+    if (!sr::ptree::plan(ring, num_vars, order, &p)) return fail(SR_E_INVALID, "prod_tree_plan: unknown order");
+    *layer_elems = p.layer_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_prod_tree_dev(sr_ctx *c, uint64_t *layers, const uint64_t *leaves, size_t n_leaves, size_t num_vars, int order, void *stream) {
+    if (int rc = check_prod_tree(c, layers, leaves, n_leaves, num_vars, order)) return rc;
+    const Call call(c, stream);
+    return dev_prod_tree(c, layers, leaves, n_leaves, num_vars, order, call.st);
+}
+int sr_prod_tree(sr_ctx *c, uint64_t *layers, const uint64_t *leaves, size_t n_leaves, size_t num_vars, int order) {
+    if (int rc = check_prod_tree(c, layers, leaves, n_leaves, num_vars, order)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    return staged(c, {{leaves, nullptr, n_leaves * w}, {nullptr, layers, (((size_t)1 << num_vars) - 1) * w}}, [&](void *const *d) {
+        return dev_prod_tree(c, (uint64_t *)d[1], (const uint64_t *)d[0], n_leaves, num_vars, order, c->stream);
+    });
 }
 int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches) {
     return round_plan_entry(kMleRound, ring, log2_degree, num_vars, n_tables, 0, 0, mode, work_elems, launches);

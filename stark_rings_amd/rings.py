@@ -915,6 +915,46 @@ class CyclotomicRing:
                                                        self._stream(stream)))
         return out
 
+    def prod_tree_plan(self, num_vars, order=MLE_TRAILING):
+        """sr_prod_tree_plan: (layer_elems, launches) of the product tree over 2^num_vars leaves on this ring -- host arithmetic only."""
+        elems = ctypes.c_size_t()
+        launches = ctypes.c_int()
+        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
+        self._check(self._lib.sr_prod_tree_plan(self.ring, k, int(num_vars), int(order), ctypes.byref(elems), ctypes.byref(launches)))
+        return elems.value, launches.value
+
+    def _prod_tree_sizes(self, leaf_words, num_vars, layer_words):
+        n_leaves = self._batch_of(leaf_words)
+        if num_vars < 0 or num_vars >= 48:
+            raise RingError("prod_tree: num_vars must be in [0, 48)")
+        if n_leaves > 1 << num_vars:
+            raise RingError("prod_tree: more leaves than 2^num_vars")
+        if layer_words != self.words_per_elem * ((1 << num_vars) - 1):
+            raise RingError("prod_tree: layers must hold 2^num_vars - 1 elements")
+        return n_leaves
+
+    def prod_tree_dev(self, layers, leaves, num_vars, order=MLE_TRAILING, stream=None):
+        """sr_prod_tree_dev: every layer of the product tree over `leaves` (n_leaves <= 2^num_vars elements in CRT/NTT form, the rest
+        one() and never read) into `layers` (2^num_vars - 1 elements: layer k at element offset 2^num_vars - 2^(num_vars - k + 1), the
+        root last).  MLE_LEADING pairs (2i, 2i + 1), MLE_TRAILING pairs (i, i + half).  Allocates nothing."""
+        null = ctypes.c_void_p(0)
+        n_words = leaves.numel() if leaves is not None else 0
+        n_leaves = self._prod_tree_sizes(n_words, num_vars, layers.numel())
+        pl = self._dev(layers)[0] if layers.numel() else null
+        pe = self._dev(leaves)[0] if n_words else null
+        self._check(self._lib.sr_prod_tree_dev(self._ctx, pl, pe, n_leaves, int(num_vars), int(order), self._stream(stream)))
+        return layers
+
+    def prod_tree(self, leaves, num_vars, order=MLE_TRAILING):
+        """Host buffers: sr_prod_tree (see prod_tree_dev); returns the 2^num_vars - 1 elements of the layers."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint64)
+        n_out = self.words_per_elem * ((1 << num_vars) - 1) if 0 <= num_vars < 48 else 0
+        n_leaves = self._prod_tree_sizes(leaves.size, num_vars, n_out)
+        out = np.empty(max(n_out, 1), dtype=np.uint64)
+        z = np.zeros(1, dtype=np.uint64)
+        self._check(self._lib.sr_prod_tree(self._ctx, _np_ptr(out), _np_ptr(leaves if n_leaves else z), n_leaves, int(num_vars), int(order)))
+        return out[:n_out]
+
     def mle_round_plan(self, num_vars, n_tables, mode=MLE_LEADING):
         """sr_mle_round_plan: (work_elems, launches) of a sum-check round message over n_tables tables -- host arithmetic only."""
         work = ctypes.c_size_t()
