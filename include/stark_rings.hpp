@@ -601,6 +601,117 @@ private:
     std::vector<uint64_t> leaves_, layers_;
 };
 
+// sr_frac_tree_plan: {elements of the layers per output, kernel launches} of the device form of a fraction tree
+inline std::pair<size_t, int> frac_tree_plan(sr_ring ring, int log2_degree, size_t num_vars, int order = SR_MLE_TRAILING) {
+    size_t elems = 0;
+    int launches = 0;
+    CyclotomicConfig::check(sr_frac_tree_plan(ring, log2_degree, num_vars, order, &elems, &launches), "sr_frac_tree_plan");
+    return {elems, launches};
+}
+// sr_frac_tree_dev on device pointers (d_p_leaves may be null: every stored numerator is one()); allocates nothing
+inline void frac_tree_dev(const CyclotomicConfig &cfg, uint64_t *d_p_layers, uint64_t *d_q_layers, const uint64_t *d_p_leaves,
+                          const uint64_t *d_q_leaves, size_t n_leaves, size_t num_vars, int order = SR_MLE_TRAILING, void *stream = nullptr) {
+    CyclotomicConfig::check(sr_frac_tree_dev(cfg.raw(), d_p_layers, d_q_layers, d_p_leaves, d_q_leaves, n_leaves, num_vars, order, stream),
+                            "sr_frac_tree_dev");
+}
+// sr_frac_tree on host words: {p_layers, q_layers}; p_leaf_words null: every stored numerator is one()
+inline std::pair<std::vector<uint64_t>, std::vector<uint64_t>> frac_tree(const CyclotomicConfig &cfg, const std::vector<uint64_t> *p_leaf_words,
+                                                                         const std::vector<uint64_t> &q_leaf_words, size_t num_vars,
+                                                                         int order = SR_MLE_TRAILING) {
+    const size_t w = cfg.words_per_elem();
+    if (q_leaf_words.size() % w || (p_leaf_words && p_leaf_words->size() != q_leaf_words.size()))
+        throw std::length_error("Should be of correct length");
+    const size_t n = q_leaf_words.size() / w;
+    if (num_vars >= 48 || n > ((size_t)1 << num_vars)) throw std::length_error("frac_tree: more leaves than 2^num_vars");
+    std::vector<uint64_t> p(w * (((size_t)1 << num_vars) - 1)), q(p.size());
+    const uint64_t dummy = 0;
+    CyclotomicConfig::check(sr_frac_tree(cfg.raw(), p.empty() ? nullptr : p.data(), q.empty() ? nullptr : q.data(),
+                                         p_leaf_words ? (n ? p_leaf_words->data() : &dummy) : nullptr, n ? q_leaf_words.data() : &dummy, n, num_vars,
+                                         order),
+                            "sr_frac_tree");
+    return {std::move(p), std::move(q)};
+}
+
+// Every layer of the binary tree that sums fractions p_i / q_i of ring elements in CRT/NTT form without dividing (sr_frac_tree): the
+// circuit of the layered fractional sum-check behind logUp lookup and range arguments.  A node is (p, q) = (p_l q_r + p_r q_l, q_l q_r)
+// with the children of ProductTree; the leaves beyond the stored ones are (zero(), one()); without stored numerators every stored
+// leaf has numerator one().  Host buffers; throws where the Python class raises.
+class FractionTree {
+public:
+    FractionTree(CyclotomicConfig cfg, std::vector<uint64_t> q_leaf_words, size_t num_vars, int order = SR_MLE_TRAILING)
+        : cfg_(std::move(cfg)), num_vars_(num_vars), order_(order), has_p_(false), q_leaves_(std::move(q_leaf_words)) {
+        build();
+    }
+    FractionTree(CyclotomicConfig cfg, std::vector<uint64_t> p_leaf_words, std::vector<uint64_t> q_leaf_words, size_t num_vars,
+                 int order = SR_MLE_TRAILING)
+        : cfg_(std::move(cfg)), num_vars_(num_vars), order_(order), has_p_(true), p_leaves_(std::move(p_leaf_words)),
+          q_leaves_(std::move(q_leaf_words)) {
+        build();
+    }
+    size_t num_vars() const { return num_vars_; }
+    size_t n_leaves() const { return q_leaves_.size() / cfg_.words_per_elem(); }  // stored leaves
+    int order() const { return order_; }
+    bool has_numerators() const { return has_p_; }
+    const std::vector<uint64_t> &p_layer_words() const { return p_layers_; }  // layers 1 .. num_vars, one behind the other
+    const std::vector<uint64_t> &q_layer_words() const { return q_layers_; }
+    // element offset of layer k (1 <= k <= num_vars) in either output: layer 1 first, the root last
+    size_t layer_offset(size_t k) const {
+        if (k < 1 || k > num_vars_) throw std::out_of_range("FractionTree: layer index out of range");
+        return ((size_t)1 << num_vars_) - ((size_t)1 << (num_vars_ - k + 1));
+    }
+    // {P_k, Q_k}: layer k as two MLEs in num_vars - k variables; k = 0 gives the leaves (every leaf and numerator must be stored)
+    std::pair<DenseMultilinearExtension, DenseMultilinearExtension> layer(size_t k) const {
+        if (k > num_vars_) throw std::out_of_range("FractionTree: layer index out of range");
+        return {DenseMultilinearExtension(cfg_, num_vars_ - k, table(true, k)), DenseMultilinearExtension(cfg_, num_vars_ - k, table(false, k))};
+    }
+    // {P, Q}: the numerator and the denominator of the sum of all fractions, one ring element each
+    std::pair<RqNTTVec, RqNTTVec> root() const {
+        if (num_vars_ == 0 && (q_leaves_.empty() || !has_p_))
+            throw std::length_error("FractionTree: a tree of no variables holds its root only as a stored leaf with a stored numerator");
+        return {RqNTTVec(cfg_, table(true, num_vars_)), RqNTTVec(cfg_, table(false, num_vars_))};
+    }
+    // {p_lo, p_hi, q_lo, q_hi}: the halves of layer k - 1 as MLEs in num_vars - k variables; P_k = p_lo q_hi + p_hi q_lo, Q_k = q_lo q_hi
+    std::vector<DenseMultilinearExtension> halves(size_t k) const {
+        if (order_ != SR_MLE_TRAILING) throw std::invalid_argument("FractionTree::halves: only a trailing-order tree has contiguous operands");
+        if (k < 1 || k > num_vars_) throw std::out_of_range("FractionTree: layer index out of range");
+        std::vector<DenseMultilinearExtension> out;
+        for (bool numer : {true, false}) {
+            const std::vector<uint64_t> below = table(numer, k - 1);
+            const auto mid = below.begin() + below.size() / 2;
+            out.emplace_back(cfg_, num_vars_ - k, std::vector<uint64_t>(below.begin(), mid));
+            out.emplace_back(cfg_, num_vars_ - k, std::vector<uint64_t>(mid, below.end()));
+        }
+        return out;
+    }
+    static std::pair<size_t, int> plan(sr_ring ring, int log2_degree, size_t num_vars, int order = SR_MLE_TRAILING) {
+        return frac_tree_plan(ring, log2_degree, num_vars, order);
+    }
+
+private:
+    void build() {
+        if (order_ != SR_MLE_LEADING && order_ != SR_MLE_TRAILING) throw std::invalid_argument("FractionTree: unknown order");
+        auto both = frac_tree(cfg_, has_p_ ? &p_leaves_ : nullptr, q_leaves_, num_vars_, order_);
+        p_layers_ = std::move(both.first);
+        q_layers_ = std::move(both.second);
+    }
+    std::vector<uint64_t> table(bool numer, size_t k) const {
+        if (k == 0) {
+            if (n_leaves() != ((size_t)1 << num_vars_))
+                throw std::length_error("FractionTree: layer 0 of a truncated tree is not a table (its missing leaves are (zero(), one()))");
+            if (!has_p_) throw std::length_error("FractionTree: layer 0 of a tree without stored numerators is not a table (they are one())");
+            return numer ? p_leaves_ : q_leaves_;
+        }
+        const std::vector<uint64_t> &src = numer ? p_layers_ : q_layers_;
+        const size_t w = cfg_.words_per_elem(), off = layer_offset(k);
+        return std::vector<uint64_t>(src.begin() + off * w, src.begin() + (off + ((size_t)1 << (num_vars_ - k))) * w);
+    }
+    CyclotomicConfig cfg_;
+    size_t num_vars_;
+    int order_;
+    bool has_p_;
+    std::vector<uint64_t> p_leaves_, q_leaves_, p_layers_, q_layers_;
+};
+
 // A sum of products of dense MLEs with ring coefficients, g = sum_k c_k prod_s f_{k,s}, after HyperPlonk's VirtualPolynomial (the code
 // crates/poly's polynomials/multilinear_polynomial.rs was adapted from): the object a sum-check is run on -- eq (a b - c),
 // sum_i alpha_i eq prod_j (...).  The MLEs are referred to, not copied, and must outlive the polynomial; an MLE that is in several

@@ -463,6 +463,33 @@ int sr_smle_fix_variables(sr_ctx *ctx, uint64_t *out_vals, uint64_t *out_idx, si
 int sr_prod_tree_plan(int ring, int log2_degree, size_t num_vars, int order, size_t *layer_elems, int *launches);
 int sr_prod_tree_dev(sr_ctx *ctx, uint64_t *d_layers, const uint64_t *d_leaves, size_t n_leaves, size_t num_vars, int order, void *stream);
 int sr_prod_tree(sr_ctx *ctx, uint64_t *layers, const uint64_t *leaves, size_t n_leaves, size_t num_vars, int order);
+/* Fraction trees (csrc/frac_tree.hpp): every layer of the binary tree that sums 2^num_vars fractions p_i / q_i of ring elements in
+ * CRT/NTT form without dividing, the circuit of the layered (GKR) fractional sum-check behind logUp lookup and range arguments.  A node
+ * is a pair (p, q); with the children (l, r) of sr_prod_tree -- (2i, 2i+1) in SR_MLE_LEADING, (i, i + half) in SR_MLE_TRAILING --
+ *   p = p_l * q_r + p_r * q_l        q = q_l * q_r
+ * `*` the slot product of sr_product_batch, `+` the slot sum of sr_add_batch.  The root (P, Q) is P = sum_i p_i prod_{j != i} q_j,
+ * Q = prod_j q_j, so P / Q = sum_i p_i / q_i wherever the q_i are units.
+ * d_p_leaves, d_q_leaves: n_leaves <= 2^num_vars elements each; the leaves beyond them are the neutral fraction (zero(), one()) and are
+ * NOT read.  d_p_leaves = NULL: every stored leaf has numerator one() (sum 1 / q_i), and no numerator is read; the general formula
+ * still defines every node (a stored left child with an absent right one gives (p_l, q_l)).
+ * d_p_layers, d_q_layers: 2^num_vars - 1 elements each in the layout of sr_prod_tree (layer k at element offset
+ * 2^num_vars - 2^(num_vars - k + 1), the root last), every layer in full, every word canonical.  d_q_layers is, word for word, what
+ * sr_prod_tree_dev writes for d_q_leaves.  In trailing order the four operands of a layer (p_lo, p_hi, q_lo, q_hi) are contiguous halves
+ * of the two layers below, usable as MLE tables as they lie:
+ *   P_k(z) + l Q_k(z) = sum_b eq(z, b) (p_lo(b) q_hi(b) + p_hi(b) q_lo(b) + l q_lo(b) q_hi(b))
+ * SR_E_INVALID, each with its own message: unknown order, num_vars >= 48, too many elements, n_leaves > 2^num_vars, a null output with
+ * num_vars > 0, null d_q_leaves with n_leaves > 0, any overlap of an output with a stored input or of the two outputs (back-to-back
+ * buffers and leaves that are not stored do not overlap).
+ * The library allocates nothing and touches no context scratch: one chain of launches on `stream`, capturable on a fresh context.
+ * sr_frac_tree_plan: pure host arithmetic -- *layer_elems = 2^num_vars - 1 (per output) and the kernel launches of the call: a launch
+ * forms up to three levels on BabyBear, two on Goldilocks, Stark, goldilocks24 and frog16, one on babybear72 (registers), full launches
+ * first, the remainder last.  num_vars = 0 is no launch and nothing written.
+ * The host-pointer form stages like sr_prod_tree. */
+int sr_frac_tree_plan(int ring, int log2_degree, size_t num_vars, int order, size_t *layer_elems, int *launches);
+int sr_frac_tree_dev(sr_ctx *ctx, uint64_t *d_p_layers, uint64_t *d_q_layers, const uint64_t *d_p_leaves, const uint64_t *d_q_leaves,
+                     size_t n_leaves, size_t num_vars, int order, void *stream);
+int sr_frac_tree(sr_ctx *ctx, uint64_t *p_layers, uint64_t *q_layers, const uint64_t *p_leaves, const uint64_t *q_leaves, size_t n_leaves,
+                 size_t num_vars, int order);
 /* Norms of a coefficient slice on the device: WithLinfNorm::linf_norm / WithL2Norm::l2_norm_squared over [Fq]
  * (crates/ring/src/traits.rs:6-36; per element balanced_decomposition/convertible_ring.rs:49-66; the signed representative of
  * fq_convertible.rs:20-34 and stark_prime/decomposition.rs:40-52).

@@ -9,6 +9,7 @@ Layout:
   mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values,
                         with the round message of a sum-check over a product, or a sum of products (VirtualPolynomial), of dense MLEs
   grand_product.py      ProductTree: every layer of a table's binary product tree, the circuit of the layered grand-product argument
+  frac_tree.py          FractionTree: every layer of a sum of fractions p/q, the circuit of the layered logUp (lookup, range) argument
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
   sparse.py             SparseMatrix of crates/linear_algebra with device-resident values: transpose, sparse x sparse product
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
@@ -28,5 +29,6 @@ from .rings import (  # noqa: F401
 )
 from .mle import DenseMultilinearExtension, SparseMultilinearExtension, VirtualPolynomial  # noqa: F401
 from .grand_product import ProductTree  # noqa: F401
+from .frac_tree import FractionTree, frac_tree_dev, frac_tree_plan  # noqa: F401  (the host-pointer form: frac_tree.frac_tree)
 from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401
 from .sparse import SparseMatrixNTT  # noqa: F401

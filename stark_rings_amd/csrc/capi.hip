@@ -38,6 +38,7 @@
 #include "sumcheck_vpoly.hpp"
 #include "sumcheck_vpoly_fold.hpp"
 #include "prod_tree.hpp"
+#include "frac_tree.hpp"
 
 namespace {
 
@@ -2109,6 +2110,65 @@ int check_prod_tree(sr_ctx *c, const void *layers, const void *leaves, size_t n_
         return fail(SR_E_INVALID, "prod_tree: d_layers overlaps d_leaves");
     return SR_OK;
 }
+// ---- fraction trees (csrc/frac_tree.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch ----------------------
+// The launches of sr::ftree::plan, as in dev_prod_tree, on the two planar outputs at once.  Only the first launch sees truncated leaves
+// or absent numerators (HP = false); every later one reads the full layers the one before it wrote.
+extern "C++" {
+template <bool HP>
+hipError_t launch_frac_tree(sr_ctx *c, int j, uint64_t *pd, uint64_t *qd, const uint64_t *ps, const uint64_t *qs, const sr::smle::One &one,
+                            size_t n_in, int m, bool tr, hipStream_t st) {
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: return sr::ftree::launch_tree<sr::Goldilocks, HP>(j, pd, qd, ps, qs, one, n_in, m, tr, c->k, st);
+        case SR_RING_BABYBEAR_POW2: return sr::ftree::launch_tree<sr::BabyBear, HP>(j, pd, qd, ps, qs, one, n_in, m, tr, c->k, st);
+        case SR_RING_STARK_POW2: return sr::ftree::launch_tree<sr::Stark, HP>(j, pd, qd, ps, qs, one, n_in, m, tr, c->k, st);
+        case SR_RING_GOLDILOCKS_24: return sr::ftree::launch_slot_tree<sr::SlotG24, HP>(c->small, j, pd, qd, ps, qs, one, n_in, m, tr, st);
+        case SR_RING_BABYBEAR_72: return sr::ftree::launch_slot_tree<sr::SlotB72, HP>(c->small, j, pd, qd, ps, qs, one, n_in, m, tr, st);
+        default: return sr::ftree::launch_slot_tree<sr::SlotFrog, HP>(c->frog, j, pd, qd, ps, qs, one, n_in, m, tr, st);
+    }
+}
+}  // extern "C++"
+int dev_frac_tree(sr_ctx *c, uint64_t *p_layers, uint64_t *q_layers, const uint64_t *p_leaves, const uint64_t *q_leaves, size_t n_leaves,
+                  size_t num_vars, int order, hipStream_t st) {
+    sr::ftree::Plan p;
+    if (!sr::ftree::plan(c->ring, num_vars, order, &p)) return fail(SR_E_INVALID, "frac_tree: no plan for these arguments");
+    const size_t w = (size_t)c->degree * c->limbs;
+    const bool tr = order == sr::mle::ORDER_TRAILING;
+    const sr::smle::One one = smle_one(c);
+    const uint64_t *ps = p_leaves, *qs = q_leaves;
+    size_t n_in = n_leaves, done = 0;
+    for (int l = 0; l < p.launches; l++) {
+        const int j = p.j[l], m = (int)(num_vars - done);
+        const size_t off = sr::ftree::layer_offset(num_vars, done + 1) * w;
+        ProfScope prof(c, st, K_POINTWISE);
+        const hipError_t e = (l == 0 && !p_leaves) ? launch_frac_tree<false>(c, j, p_layers + off, q_layers + off, ps, qs, one, n_in, m, tr, st)
+                                                   : launch_frac_tree<true>(c, j, p_layers + off, q_layers + off, ps, qs, one, n_in, m, tr, st);
+        if (e != hipSuccess) return fail(SR_E_HIP, std::string("frac_tree launch: ") + hipGetErrorString(e));
+        done += j;
+        const size_t last = sr::ftree::layer_offset(num_vars, done) * w;  // the last level of this launch
+        ps = p_layers + last;
+        qs = q_layers + last;
+        n_in = (size_t)1 << (num_vars - done);
+    }
+    return SR_OK;
+}
+// the argument checks the two forms of sr_frac_tree share
+int check_frac_tree(sr_ctx *c, const void *p_layers, const void *q_layers, const void *p_leaves, const void *q_leaves, size_t n_leaves,
+                    size_t num_vars, int order) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) return fail(SR_E_INVALID, "frac_tree: unknown order");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "frac_tree: num_vars must be below 48");
+    if (n_leaves > (size_t)1 << num_vars) return fail(SR_E_INVALID, "frac_tree: n_leaves exceeds 2^num_vars");
+    if (int rc = check_count(c, (size_t)1 << num_vars)) return rc;
+    if (num_vars && (!p_layers || !q_layers)) return fail(SR_E_INVALID, "frac_tree: null output buffer");
+    if (n_leaves && !q_leaves) return fail(SR_E_INVALID, "frac_tree: null denominator leaves");
+    const size_t w = (size_t)c->degree * c->limbs * 8, out = (((size_t)1 << num_vars) - 1) * w, in = n_leaves * w;
+    if (ranges_overlap(p_layers, out, q_layers, out)) return fail(SR_E_INVALID, "frac_tree: d_p_layers overlaps d_q_layers");
+    if (ranges_overlap(p_layers, out, q_leaves, in)) return fail(SR_E_INVALID, "frac_tree: d_p_layers overlaps d_q_leaves");
+    if (ranges_overlap(q_layers, out, q_leaves, in)) return fail(SR_E_INVALID, "frac_tree: d_q_layers overlaps d_q_leaves");
+    if (p_leaves && ranges_overlap(p_layers, out, p_leaves, in)) return fail(SR_E_INVALID, "frac_tree: d_p_layers overlaps d_p_leaves");
+    if (p_leaves && ranges_overlap(q_layers, out, p_leaves, in)) return fail(SR_E_INVALID, "frac_tree: d_q_layers overlaps d_p_leaves");
+    return SR_OK;
+}
 // d_counter[i] (sr_ctx_create_ex) to the host, then cleared
 int read_counter(sr_ctx *c, int i, unsigned long long *out, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(out, c->d_counter + i, sizeof *out, hipMemcpyDeviceToHost, st));
@@ -2701,6 +2761,34 @@ int sr_prod_tree(sr_ctx *c, uint64_t *layers, const uint64_t *leaves, size_t n_l
     return staged(c, {{leaves, nullptr, n_leaves * w}, {nullptr, layers, (((size_t)1 << num_vars) - 1) * w}}, [&](void *const *d) {
         return dev_prod_tree(c, (uint64_t *)d[1], (const uint64_t *)d[0], n_leaves, num_vars, order, c->stream);
     });
+}
+int sr_frac_tree_plan(int ring, int log2_degree, size_t num_vars, int order, size_t *layer_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!layer_elems || !launches) return fail(SR_E_INVALID, "frac_tree_plan: null result pointer");
+    if (num_vars >= 48) return fail(SR_E_INVALID, "frac_tree_plan: num_vars must be below 48");
+    sr::ftree::Plan p;
+    if (!sr::ftree::plan(ring, num_vars, order, &p)) return fail(SR_E_INVALID, "frac_tree_plan: unknown order");
+    *layer_elems = p.layer_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_frac_tree_dev(sr_ctx *c, uint64_t *p_layers, uint64_t *q_layers, const uint64_t *p_leaves, const uint64_t *q_leaves, size_t n_leaves,
+                     size_t num_vars, int order, void *stream) {
+    if (int rc = check_frac_tree(c, p_layers, q_layers, p_leaves, q_leaves, n_leaves, num_vars, order)) return rc;
+    const Call call(c, stream);
+    return dev_frac_tree(c, p_layers, q_layers, p_leaves, q_leaves, n_leaves, num_vars, order, call.st);
+}
+int sr_frac_tree(sr_ctx *c, uint64_t *p_layers, uint64_t *q_layers, const uint64_t *p_leaves, const uint64_t *q_leaves, size_t n_leaves,
+                 size_t num_vars, int order) {
+    if (int rc = check_frac_tree(c, p_layers, q_layers, p_leaves, q_leaves, n_leaves, num_vars, order)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8, out = (((size_t)1 << num_vars) - 1) * w;
+    return staged(c, {{q_leaves, nullptr, n_leaves * w}, {p_leaves, nullptr, p_leaves ? n_leaves * w : 0}, {nullptr, p_layers, out}, {nullptr, q_layers, out}},
+                  [&](void *const *d) {
+                      return dev_frac_tree(c, (uint64_t *)d[2], (uint64_t *)d[3], p_leaves ? (const uint64_t *)d[1] : nullptr, (const uint64_t *)d[0],
+                                           n_leaves, num_vars, order, c->stream);
+                  });
 }
 int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches) {
     return round_plan_entry(kMleRound, ring, log2_degree, num_vars, n_tables, 0, 0, mode, work_elems, launches);
