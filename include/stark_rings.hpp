@@ -32,7 +32,10 @@
 //   a sum of products of dense MLEs      (HyperPlonk's VirtualPolynomial) class VirtualPolynomial: add_mle_list, mul_by_mle, degree, round_evals, sum
 //                                                                      (sr_vpoly_round_evals: one pass, every distinct table read once),
 //                                                                      fold_round_evals (sr_vpoly_round_fold_evals: fold at the challenge
-//                                                                      and the next message in one pass), fixed_variables
+//                                                                      and the next message in one pass), fixed_variables,
+//                                                                      round_evals_weighted / fold_round_evals_weighted (sr_vpoly_wround_*:
+//                                                                      a per-pair weight, the eq factor without a table); class EqSumCheck:
+//                                                                      a whole sum-check of eq(z, .) g, message / next / final
 //   SparseMultilinearExtension<RqNTT>    crates/poly mle/sparse.rs   class SparseMultilinearExtension: from_slice, from_matrix, fix_variables,
 //     precompute_eq                      sparse.rs:381-394             fixed_variables, evaluate, to_evaluations; eq_table(point); device
 //                                                                      pointers: CyclotomicConfig::eq_table_dev / smle_plan / smle_fix_variables_dev
@@ -204,6 +207,36 @@ public:
     // smle_plan: {workspace elements, stream operations}; log2_degree as given to the constructor (0 for the reference's own rings)
     void eq_table_dev(uint64_t *out, const uint64_t *point, size_t n_vars, void *stream) const {
         check(sr_eq_table_dev(raw(), out, point, n_vars, stream), "eq_table_dev");
+    }
+    // sum-check rounds with a per-pair weight on device pointers (include/stark_rings_hip.h: sr_vpoly_wround_plan, sr_vpoly_wround_evals_dev,
+    // sr_vpoly_wround_fold_plan, sr_vpoly_wround_fold_evals_dev): {work_elems, launches} of the two plans, and the two device calls
+    std::pair<size_t, int> vpoly_wround_plan(int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order) const {
+        size_t work = 0;
+        int launches = 0;
+        check(sr_vpoly_wround_plan((int)ring_, log2_degree, num_vars, n_tables, n_terms, degree, order, &work, &launches), "vpoly_wround_plan");
+        return {work, launches};
+    }
+    std::pair<size_t, int> vpoly_wround_fold_plan(int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order) const {
+        size_t work = 0;
+        int launches = 0;
+        check(sr_vpoly_wround_fold_plan((int)ring_, log2_degree, num_vars, n_tables, n_terms, degree, order, &work, &launches),
+              "vpoly_wround_fold_plan");
+        return {work, launches};
+    }
+    void vpoly_wround_evals_dev(uint64_t *d_out, const uint64_t *d_weights, const uint64_t *const *d_tables, const size_t *n_evals, int n_tables,
+                                const sr_vpoly_term *terms, int n_terms, const uint64_t *d_coeffs, size_t num_vars, int order, uint64_t *d_work,
+                                size_t work_elems, void *stream) const {
+        check(sr_vpoly_wround_evals_dev(raw(), d_out, d_weights, d_tables, n_evals, n_tables, terms, n_terms, d_coeffs, num_vars, order, d_work,
+                                        work_elems, stream),
+              "vpoly_wround_evals_dev");
+    }
+    void vpoly_wround_fold_evals_dev(uint64_t *d_out, uint64_t *const *d_out_tables, size_t *n_evals_out, const uint64_t *d_weights,
+                                     const uint64_t *const *d_tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
+                                     const uint64_t *d_coeffs, size_t num_vars, const uint64_t *d_r, int order, uint64_t *d_work, size_t work_elems,
+                                     void *stream) const {
+        check(sr_vpoly_wround_fold_evals_dev(raw(), d_out, d_out_tables, n_evals_out, d_weights, d_tables, n_evals, n_tables, terms, n_terms,
+                                             d_coeffs, num_vars, d_r, order, d_work, work_elems, stream),
+              "vpoly_wround_fold_evals_dev");
     }
     std::pair<size_t, int> smle_plan(int log2_degree, size_t nnz, size_t n_out, size_t n_fixed) const {
         size_t work = 0;
@@ -805,6 +838,60 @@ public:
         for (const DenseMultilinearExtension *t : tables_) g.push_back(order == SR_MLE_LEADING ? t->fixed_variables(point) : t->fix_last_variables(point));
         return over(std::move(g), nv_ - point.len());
     }
+    // The round message with a per-pair weight (sr_vpoly_wround_evals): the degree() + 1 elements h(t) = sum_b weights[b] g(t, b), b over
+    // the 2^(num_vars() - 1) pairs of the round.  The weight is constant in the round's variable and is no factor: it is not counted in
+    // degree().  With eq(z_rest, .) as weights this is the eq(z, .) factor of a zero-check without a table (EqSumCheck below).
+    RqNTTVec round_evals_weighted(const RqNTTVec &weights, int order = SR_MLE_LEADING) const {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("round_evals_weighted: unknown order");
+        if (terms_.empty()) throw std::length_error("VirtualPolynomial: no product has been added");
+        if (nv_ < 1 || weights.len() != (size_t)1 << (nv_ - 1)) throw std::length_error("round_evals_weighted: one weight per pair");
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        for (const DenseMultilinearExtension *t : tables_) {
+            ptrs.push_back(t->words().empty() ? nullptr : t->words().data());
+            sizes.push_back(t->len());
+        }
+        const std::vector<uint64_t> coeffs = coeff_words();
+        std::vector<uint64_t> out(cfg_.words_per_elem() * (degree() + 1));
+        CyclotomicConfig::check(sr_vpoly_wround_evals(cfg_.raw(), out.data(), weights.words().data(), ptrs.data(), sizes.data(), (int)tables_.size(),
+                                                      terms_.data(), (int)terms_.size(), coeffs.empty() ? nullptr : coeffs.data(), nv_, order),
+                                "sr_vpoly_wround_evals");
+        return RqNTTVec(cfg_, std::move(out));
+    }
+    // fold_round_evals with a per-pair weight on the message (sr_vpoly_wround_fold_evals): every table slot folded at r, and
+    // round_evals_weighted(next_weights) of the folded polynomial, in one pass.  next_weights: 2^(num_vars() - 2) elements.
+    std::pair<RqNTTVec, VirtualPolynomial> fold_round_evals_weighted(const RqNTTVec &r, const RqNTTVec &next_weights, int order = SR_MLE_LEADING) const {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("fold_round_evals_weighted: unknown order");
+        if (terms_.empty()) throw std::length_error("VirtualPolynomial: no product has been added");
+        if (r.len() != 1) throw std::length_error("fold_round_evals_weighted: r is not one ring element");
+        if (nv_ < 2) throw std::length_error("fold_round_evals_weighted: num_vars >= 2");
+        if (next_weights.len() != (size_t)1 << (nv_ - 2)) throw std::length_error("fold_round_evals_weighted: one weight per pair of the folded tables");
+        const size_t w = cfg_.words_per_elem();
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        std::vector<std::vector<uint64_t>> folded;
+        std::vector<uint64_t *> optrs;
+        for (const DenseMultilinearExtension *t : tables_) {
+            ptrs.push_back(t->words().empty() ? nullptr : t->words().data());
+            sizes.push_back(t->len());
+            folded.emplace_back(t->words().size());  // never shorter than the folded table
+        }
+        for (auto &f : folded) optrs.push_back(f.empty() ? nullptr : f.data());
+        std::vector<size_t> n_out(tables_.size());
+        std::vector<uint64_t> out(w * (degree() + 1));
+        const std::vector<uint64_t> coeffs = coeff_words();
+        CyclotomicConfig::check(sr_vpoly_wround_fold_evals(cfg_.raw(), out.data(), optrs.data(), n_out.data(), next_weights.words().data(), ptrs.data(),
+                                                           sizes.data(), (int)tables_.size(), terms_.data(), (int)terms_.size(),
+                                                           coeffs.empty() ? nullptr : coeffs.data(), nv_, r.words().data(), order),
+                                "sr_vpoly_wround_fold_evals");
+        std::vector<DenseMultilinearExtension> g;
+        for (size_t j = 0; j < tables_.size(); j++) {
+            folded[j].resize(n_out[j] * w);
+            g.emplace_back(cfg_, nv_ - 1, std::move(folded[j]));
+        }
+        return {RqNTTVec(cfg_, std::move(out)), over(std::move(g), nv_ - 1)};
+    }
+    const CyclotomicConfig &config() const { return cfg_; }
 
 private:
     // the same terms and coefficients over `tables`, one per table slot, owned by the result
@@ -864,6 +951,103 @@ private:
     std::vector<bool> has_coeff_;
     std::vector<std::vector<uint64_t>> coeffs_;
     std::shared_ptr<std::vector<DenseMultilinearExtension>> owned_;  // the tables of a polynomial that fold_round_evals / fixed_variables made
+};
+
+// The prover of a whole sum-check of  sum_b eq(z, b) g(b)  -- a zero-check, R1CS, the layer claim of a product or fraction tree -- WITHOUT
+// an eq table.  In the round that binds variable v, with the challenges r of the earlier rounds bound,
+//     s(t) = [prod_{i bound} eq(z_i, r_i)] * eq(z_v, t) * h(t),   h(t) = sum_b w[b] g(t, b),   w = eq(z_rest, .)
+// with g folded at the challenges so far and w the eq table of the unbound coordinates of z only: one element per pair, never folded
+// (VirtualPolynomial::round_evals_weighted / fold_round_evals_weighted).  message() is s(0 .. degree + 1), bit-identical to what the
+// prover that holds eq(z, .) as one more table sends.  g is referred to, not copied, until the first next(); z: num_vars ring elements;
+// SR_MLE_LEADING binds variable 0 first, SR_MLE_TRAILING variable n - 1.
+class EqSumCheck {
+public:
+    EqSumCheck(const VirtualPolynomial &g, const RqNTTVec &z, int order = SR_MLE_LEADING)
+        : cfg_(g.config()), g_(g), z_(z), order_(order), n_(g.num_vars()), d_(g.degree()), round_(1), prefix_(one()), h_(one()) {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("EqSumCheck: unknown order");
+        if (n_ < 1 || d_ < 1) throw std::length_error("EqSumCheck: a polynomial of at least one variable and one product");
+        if (z.len() != n_) throw std::length_error("EqSumCheck: z must hold num_vars ring elements");
+        h_ = g_.round_evals_weighted(weights(1), order_);
+    }
+    size_t degree() const { return d_; }
+    size_t round() const { return round_; }  // 1 .. num_vars; num_vars + 1 once every variable is bound
+    // the weights of round j = 1 .. n: the eq table of z[j:] (leading) or z[:n - j] (trailing), 2^(n - j) elements
+    RqNTTVec weights(size_t j) const { return eq_table(order_ == SR_MLE_LEADING ? slice(z_, j, n_) : slice(z_, 0, n_ - j)); }
+    // s(0 .. degree + 1) of the current round: degree + 2 ring elements
+    RqNTTVec message() const {
+        if (round_ > n_) throw std::length_error("EqSumCheck: every variable is bound");
+        // h(d + 1) = sum_{i <= d} (-1)^(d - i) C(d + 1, i) h(i): the (d + 1)-th finite difference of a polynomial of degree d is zero
+        RqNTTVec next = zero();
+        size_t c = 1;
+        for (size_t i = 0; i <= d_; i++) {
+            const RqNTTVec hi = slice(h_, i, i + 1);
+            for (size_t q = 0; q < c; q++) {
+                if ((d_ - i) % 2 == 0) next += hi;
+                else next -= hi;
+            }
+            c = c * (d_ + 1 - i) / (i + 1);
+        }
+        const RqNTTVec zv = bound_coordinate(round_);
+        RqNTTVec e = one();
+        e -= zv;  // eq(z_v, 0)
+        RqNTTVec step = zv;
+        step -= e;  // 2 z_v - one()
+        std::vector<uint64_t> out;
+        for (size_t t = 0; t <= d_ + 1; t++) {
+            RqNTTVec s = (t <= d_ ? slice(h_, t, t + 1) : next) * e;
+            s *= prefix_;  // the prefix product last
+            out.insert(out.end(), s.words().begin(), s.words().end());
+            e += step;
+        }
+        return RqNTTVec(cfg_, std::move(out));
+    }
+    // binds the current round's variable to the challenge r and advances: the fused call while two variables are left, fixed_variables
+    // for the last round
+    void next(const RqNTTVec &r) {
+        if (round_ > n_) throw std::length_error("EqSumCheck: every variable is bound");
+        if (r.len() != 1) throw std::length_error("EqSumCheck: r is not one ring element");
+        if (g_.num_vars() >= 2) {
+            auto step = g_.fold_round_evals_weighted(r, weights(round_ + 1), order_);
+            h_ = std::move(step.first);
+            g_ = std::move(step.second);
+        } else {
+            g_ = g_.fixed_variables(r, order_);
+        }
+        const RqNTTVec zv = bound_coordinate(round_);
+        RqNTTVec e = one();
+        e -= zv;
+        RqNTTVec step = zv;
+        step -= e;
+        step *= r;
+        e += step;  // eq(z_v, r)
+        prefix_ *= e;
+        round_++;
+    }
+    // {the values of g's table slots at the challenges, one ring element each; eq(z, r)} once every variable is bound
+    std::pair<std::vector<RqNTTVec>, RqNTTVec> final() const {
+        if (round_ <= n_) throw std::length_error("EqSumCheck: variables are still unbound");
+        std::vector<RqNTTVec> vals;
+        for (const DenseMultilinearExtension *t : g_.tables()) vals.emplace_back(cfg_, t->words());
+        return {vals, prefix_};
+    }
+
+private:
+    RqNTTVec one() const { return eq_table(RqNTTVec(cfg_, std::vector<uint64_t>())); }
+    RqNTTVec zero() const { return RqNTTVec(cfg_, std::vector<uint64_t>(cfg_.words_per_elem(), 0)); }
+    RqNTTVec slice(const RqNTTVec &v, size_t from, size_t to) const {
+        const size_t w = cfg_.words_per_elem();
+        return RqNTTVec(cfg_, std::vector<uint64_t>(v.words().begin() + from * w, v.words().begin() + to * w));
+    }
+    RqNTTVec bound_coordinate(size_t j) const {
+        const size_t v = order_ == SR_MLE_LEADING ? j - 1 : n_ - j;
+        return slice(z_, v, v + 1);
+    }
+    CyclotomicConfig cfg_;
+    VirtualPolynomial g_;
+    RqNTTVec z_;
+    int order_;
+    size_t n_, d_, round_;
+    RqNTTVec prefix_, h_;
 };
 
 // SparseMultilinearExtension<RqNTT> of crates/poly (src/mle/sparse.rs): the stored evaluations as ascending indices and their values

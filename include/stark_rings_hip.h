@@ -394,6 +394,59 @@ int sr_vpoly_round_fold_evals_dev(sr_ctx *ctx, uint64_t *d_out, uint64_t *const 
 int sr_vpoly_round_fold_evals(sr_ctx *ctx, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
                               const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coeffs,
                               size_t num_vars, const uint64_t *r, int order);
+/* Sum-check rounds with a PER-PAIR WEIGHT (csrc/sumcheck_weighted.hpp): the eq(z, .) factor of a zero-check -- eq (a b - c), the layer
+ * claims L_k(z) = sum_b eq(z, b) lo(b) hi(b) of sr_prod_tree_dev and P_k(z) + lambda Q_k(z) of sr_frac_tree_dev -- as one ring element per
+ * pair that is constant in the round's variable, not as one more table.  In the round that binds variable v, with the challenges r
+ * of the earlier rounds bound,
+ *     s(t) = [prod_{i bound} eq(z_i, r_i)] * eq(z_v, t) * h(t),   h(t) = sum_b w[b] g(t, b),   w = eq(z_rest, .) (sr_eq_table_dev)
+ * where g is the claim without eq, folded at the challenges so far: w is never folded (the next round has its own, half as long), is
+ * read once per round, and h has one degree less than s.  The calls below compute h; the two factors in front are single elements.
+ *
+ * sr_vpoly_wround_evals_dev: the weighted sibling of sr_vpoly_round_evals_dev.
+ *   d_out[t] = sum_{b < half} w[b] * sum_k c_k prod_s ( lo_s[b] + t (hi_s[b] - lo_s[b]) ),  t = 0 .. degree
+ * with the pairs (lo, hi) of sr_vpoly_round_evals_dev in the same order (SR_MLE_LEADING: f[2b], f[2b+1]; SR_MLE_TRAILING: f[b],
+ * f[b + half]).  `degree` is the largest n_factors: the weight is not a factor and is not counted.  d_weights holds 2^(num_vars - 1) ring
+ * elements in CRT / NTT form, one per pair, indexed by the pair index b, stored in full, never written.  num_vars >= 1.
+ * SR_MLE_ROUND_SUM is SR_E_INVALID: a weight of a plain sum is just a table.  Truncated tables work as in the unweighted call: the pass
+ * ends at the longest term, and a weight whose pair is not visited is not read.  All arithmetic is exact on canonical values: the
+ * output depends on neither the grid, the split nor the association, and with every weight one() it equals
+ * sr_vpoly_round_evals_dev bit for bit.  terms, d_tables and n_evals are HOST arrays consumed at call time; nothing is allocated, no
+ * context scratch is touched, every workspace word is written before it is read, the launches are one linear chain on one stream
+ * (capturable on a fresh context); canonical in, canonical out; every ring id.
+ *
+ * sr_vpoly_wround_fold_evals_dev: the weighted sibling of sr_vpoly_round_fold_evals_dev.  d_out_tables and n_evals_out are exactly those
+ * of sr_vpoly_round_fold_evals_dev; d_out is bit-identical to sr_vpoly_wround_evals_dev on the folded tables at num_vars - 1 with the
+ * same d_weights, which therefore holds 2^(num_vars - 2) elements.  num_vars >= 2.  The aliasing rules are those of the unweighted fused
+ * call; in addition d_weights may not overlap any output or d_work.
+ *
+ * SR_E_INVALID (nothing launched, the reason in sr_last_error): every refusal of the unweighted calls, a null d_weights (refused before
+ * anything else), SR_MLE_ROUND_SUM, d_out or d_work overlapping d_weights, and for the fused call a folded table overlapping d_weights.
+ *
+ * The plans are pure host arithmetic (no device, no context): *work_elems == 0 exactly when *launches == 1, *work_elems <=
+ * SR_MLE_ROUND_MAX_GROUPS * (degree + 1); the records are those of sr_vpoly_round_plan (sr_vpoly_wround_fold_plan: at num_vars - 1).
+ * Points per launch over 4 / 8 table slots, the largest number that keeps a kernel without scratch within 256 registers (BabyBear 128):
+ *   the weighted round kernels   Goldilocks 5 / 5, BabyBear 5 / 5, Stark 4 / 1, goldilocks24 3 / 1, babybear72 1 / 1, frog16 1 / 1
+ *   the weighted fused launch    Goldilocks 5 / 4, BabyBear 5 / 3, Stark 2 / 1, goldilocks24 2 / 1, babybear72 1 / 0, frog16 1 / 1
+ * (babybear72 over 8 slots: the fused launch only folds).  The remaining points of a fused call come from the weighted round kernels
+ * over the FOLDED tables, into the same records; such a plan always uses the workspace.
+ * The host-pointer forms stage whole tables (and the weights) through context-owned temporaries as sr_vpoly_round_evals and
+ * sr_vpoly_round_fold_evals do; chunked staging is not implemented. */
+int sr_vpoly_wround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order, size_t *work_elems,
+                         int *launches);
+int sr_vpoly_wround_evals_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_weights, const uint64_t *const *d_tables, const size_t *n_evals,
+                              int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *d_coeffs, size_t num_vars, int order,
+                              uint64_t *d_work, size_t work_elems, void *stream);
+int sr_vpoly_wround_evals(sr_ctx *ctx, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
+                          int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coeffs, size_t num_vars, int order);
+int sr_vpoly_wround_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order,
+                              size_t *work_elems, int *launches);
+int sr_vpoly_wround_fold_evals_dev(sr_ctx *ctx, uint64_t *d_out, uint64_t *const *d_out_tables, size_t *n_evals_out, const uint64_t *d_weights,
+                                   const uint64_t *const *d_tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
+                                   int n_terms, const uint64_t *d_coeffs, size_t num_vars, const uint64_t *d_r, int order, uint64_t *d_work,
+                                   size_t work_elems, void *stream);
+int sr_vpoly_wround_fold_evals(sr_ctx *ctx, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
+                               const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
+                               const uint64_t *coeffs, size_t num_vars, const uint64_t *r, int order);
 /* Sparse multilinear extensions: the arithmetic of crates/poly's SparseMultilinearExtension (mle/sparse.rs) on device-resident
  * values.  Elements are ring elements in CRT / NTT form in the usual flat layout, canonical in and canonical out, for every ring id.
  *

@@ -7,7 +7,9 @@ Layout:
                         Flatten at batch granularity) on top of the C ABI
   wire.py               ark-serialize framing of Vec / Matrix / SparseMatrix / SymmetricMatrix around the device codec
   mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values,
-                        with the round message of a sum-check over a product, or a sum of products (VirtualPolynomial), of dense MLEs
+                        with the round message of a sum-check over a product, or a sum of products (VirtualPolynomial), of dense MLEs,
+                        and EqSumCheck: a whole sum-check of eq(z, .) g with eq as per-pair weights, not a table
+  wsumcheck.py          the device-pointer forms of the weighted sum-check rounds (sr_vpoly_wround_evals_dev, sr_vpoly_wround_fold_evals_dev)
   grand_product.py      ProductTree: every layer of a table's binary product tree, the circuit of the layered grand-product argument
   frac_tree.py          FractionTree: every layer of a sum of fractions p/q, the circuit of the layered logUp (lookup, range) argument
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
@@ -27,8 +29,9 @@ from .rings import (  # noqa: F401
     CyclotomicRing,
     RingError,
 )
-from .mle import DenseMultilinearExtension, SparseMultilinearExtension, VirtualPolynomial  # noqa: F401
+from .mle import DenseMultilinearExtension, EqSumCheck, SparseMultilinearExtension, VirtualPolynomial  # noqa: F401
 from .grand_product import ProductTree  # noqa: F401
+from .wsumcheck import vpoly_wround_evals_dev, vpoly_wround_fold_evals_dev  # noqa: F401
 from .frac_tree import FractionTree, frac_tree_dev, frac_tree_plan  # noqa: F401  (the host-pointer form: frac_tree.frac_tree)
 from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401
 from .sparse import SparseMatrixNTT  # noqa: F401

@@ -37,6 +37,7 @@
 #include "sumcheck_fold.hpp"
 #include "sumcheck_vpoly.hpp"
 #include "sumcheck_vpoly_fold.hpp"
+#include "sumcheck_weighted.hpp"
 #include "prod_tree.hpp"
 #include "frac_tree.hpp"
 
@@ -1598,9 +1599,11 @@ struct RoundFamily {
     const char *name;  // the prefix of every message
     int max_tables;
     bool terms, fold;  // a sum of products (n_terms, degree); a fold as well (an order, no SR_MLE_ROUND_SUM, two variables)
+    bool weighted = false;  // a per-pair weight (csrc/sumcheck_weighted.hpp): an order, no SR_MLE_ROUND_SUM
 };
 const RoundFamily kMleRound{"mle_round", SR_MLE_ROUND_MAX_TABLES, false, false}, kVpolyRound{"vpoly_round", SR_VPOLY_MAX_TABLES, true, false},
-    kMleRoundFold{"mle_round_fold", SR_MLE_ROUND_MAX_TABLES, false, true}, kVpolyRoundFold{"vpoly_round_fold", SR_VPOLY_MAX_TABLES, true, true};
+    kMleRoundFold{"mle_round_fold", SR_MLE_ROUND_MAX_TABLES, false, true}, kVpolyRoundFold{"vpoly_round_fold", SR_VPOLY_MAX_TABLES, true, true},
+    kVpolyWround{"vpoly_wround", SR_VPOLY_MAX_TABLES, true, false, true}, kVpolyWroundFold{"vpoly_wround_fold", SR_VPOLY_MAX_TABLES, true, true, true};
 extern "C++" {
 template <class T> struct FamilyType {
     using type = T;
@@ -1693,6 +1696,44 @@ int dev_vpoly_round_fold(sr_ctx *c, const sr::vpoly_fold::Plan &p, int order, ui
                                                                   (bits & 15u) == 0, work, st);
     });
 }
+// the weighted siblings of the two calls above (csrc/sumcheck_weighted.hpp): weights holds one element per pair
+int dev_vpoly_wround(sr_ctx *c, const sr::wsumcheck::Plan &p, int order, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables,
+                     const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars,
+                     uint64_t *work, hipStream_t st) {
+    sr::vpoly::Tables tb{};
+    sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
+    const uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)coef |
+                           (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int k = 0; k < n_terms; k++) {
+        tm[k].n_factors = terms[k].n_factors;
+        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
+    }
+    return round_dispatch(c, st, "vpoly wround", [&](auto t, const auto &kc) {
+        return sr::wsumcheck::launch<typename decltype(t)::type>(kc, p, order, out, weights, tb, n_tables, tm, n_terms, coef, num_vars, c->k,
+                                                                 (bits & 15u) == 0, work, st);
+    });
+}
+int dev_vpoly_wround_fold(sr_ctx *c, const sr::wsumcheck::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
+                          const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
+                          int n_terms, const uint64_t *coef, size_t num_vars, const uint64_t *r, uint64_t *work, hipStream_t st) {
+    sr::vpoly::Tables tb{};
+    sr::vpoly_fold::Folded fo{};
+    sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
+    uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)r | (uintptr_t)coef |
+                     (p.groups > 1 ? (uintptr_t)work : 0);
+    for (int j = 0; j < n_tables; j++) {
+        fo.p[j] = out_tables[j];
+        bits |= (uintptr_t)out_tables[j];
+    }
+    for (int k = 0; k < n_terms; k++) {
+        tm[k].n_factors = terms[k].n_factors;
+        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
+    }
+    return round_dispatch(c, st, "vpoly wround fold", [&](auto t, const auto &kc) {
+        return sr::wsumcheck::launch_fold<typename decltype(t)::type>(kc, p, order, out, weights, tb, fo, r, n_tables, tm, n_terms, coef, num_vars,
+                                                                      n_out, c->k, (bits & 15u) == 0, work, st);
+    });
+}
 // a refusal of family f: the message is assembled here, on the failing path only
 int refuse(const RoundFamily &f, const std::string &what) { return fail(SR_E_INVALID, std::string(f.name) + ": " + what); }
 // the shape checks the *_plan call and the two forms of the *_evals call of a family share (n_terms, degree: families with terms)
@@ -1702,12 +1743,16 @@ int round_plan_for(const RoundFamily &f, int ring, int k, size_t num_vars, int n
         if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return refuse(f, "n_terms must be 1 .. 8");
         if (degree < 1 || degree > SR_VPOLY_MAX_FACTORS) return refuse(f, "degree (the largest n_factors) must be 1 .. 4");
     }
-    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && (f.fold || mode != SR_MLE_ROUND_SUM))
-        return refuse(f, f.fold ? "unknown order" : "unknown mode");
+    if (f.weighted && !f.fold && mode == SR_MLE_ROUND_SUM)
+        return refuse(f, "SR_MLE_ROUND_SUM takes no weights (a weight of a plain sum is just a table)");
+    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && (f.fold || f.weighted || mode != SR_MLE_ROUND_SUM))
+        return refuse(f, f.fold || f.weighted ? "unknown order" : "unknown mode");
     if (num_vars >= 48) return refuse(f, "num_vars must be below 48");
     if (f.fold && num_vars < 2) return refuse(f, "num_vars >= 2 (the folded tables need a variable for the next round)");
     if (num_vars == 0 && mode != SR_MLE_ROUND_SUM) return refuse(f, "a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
-    const bool ok = f.fold    ? (f.terms ? sr::vpoly_fold::plan(ring, k, num_vars, n_tables, degree, mode, p)
+    const bool ok = f.weighted ? (f.fold ? sr::wsumcheck::fold_plan(ring, k, num_vars, n_tables, degree, mode, p)
+                                         : sr::wsumcheck::plan(ring, k, num_vars, n_tables, degree, mode, p))
+                    : f.fold  ? (f.terms ? sr::vpoly_fold::plan(ring, k, num_vars, n_tables, degree, mode, p)
                                          : sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, mode, p))
                     : f.terms ? sr::vpoly::plan(ring, k, num_vars, n_tables, degree, mode, p)
                               : sr::sumcheck::plan(ring, k, num_vars, n_tables, mode, p);
@@ -2946,6 +2991,116 @@ int sr_vpoly_round_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tab
                       if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
                       if (int rc = dev_vpoly_round_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dt, n_evals, n_tables, terms, n_terms, dcoef,
                                                         num_vars, (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
+                          return rc;
+                      for (int j = 0; j < n_tables; j++)
+                          if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
+                      return SR_OK;
+                  });
+}
+int sr_vpoly_wround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order, size_t *work_elems,
+                         int *launches) {
+    return round_plan_entry(kVpolyWround, ring, log2_degree, num_vars, n_tables, n_terms, degree, order, work_elems, launches);
+}
+int sr_vpoly_wround_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
+                              int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int order,
+                              uint64_t *work, size_t work_elems, void *stream) {
+    sr::wsumcheck::Plan p;
+    if (!weights) return refuse(kVpolyWround, "null pointer (d_weights)");
+    if (int rc = check_vpoly_terms(c, kVpolyWround, out, nullptr, nullptr, nullptr, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
+        return rc;
+    if (int rc = check_round_work(kVpolyWround, p, work, work_elems)) return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const size_t cw = coef ? n_terms * w : 0, ww = w << (num_vars - 1);
+    for (int j = 0; j < n_tables; j++) {
+        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return refuse(kVpolyWround, "d_out overlaps a table");
+        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return refuse(kVpolyWround, "d_work overlaps a table");
+        if (ranges_overlap(coef, cw, tables[j], n_evals[j] * w)) return refuse(kVpolyWround, "d_coeffs overlaps a table");
+    }
+    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return refuse(kVpolyWround, "d_out overlaps d_work");
+    if (ranges_overlap(out, p.np_total * w, coef, cw)) return refuse(kVpolyWround, "d_out overlaps d_coeffs");
+    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return refuse(kVpolyWround, "d_work overlaps d_coeffs");
+    if (ranges_overlap(out, p.np_total * w, weights, ww)) return refuse(kVpolyWround, "d_out overlaps d_weights");
+    if (ranges_overlap(work, p.work_elems * w, weights, ww)) return refuse(kVpolyWround, "d_work overlaps d_weights");
+    const Call call(c, stream);
+    return dev_vpoly_wround(c, p, order, out, weights, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, work, call.st);
+}
+int sr_vpoly_wround_evals(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                          const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int order) {
+    sr::wsumcheck::Plan p;
+    if (!weights) return refuse(kVpolyWround, "null pointer (weights)");
+    if (int rc = check_vpoly_terms(c, kVpolyWround, out, nullptr, nullptr, nullptr, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
+        return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const TableSlot in(n_evals, n_tables, w);
+    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients; HOST_4: the weights
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {coef, nullptr, coef ? n_terms * w : 0},
+                      {weights, nullptr, w << (num_vars - 1)}},
+                  [&](void *const *d) -> int {
+                      uint64_t *dt[SR_VPOLY_MAX_TABLES];
+                      in.at(d[0], n_tables, dt);
+                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
+                      return dev_vpoly_wround(c, p, order, (uint64_t *)d[1], (const uint64_t *)d[4], dt, n_evals, n_tables, terms, n_terms,
+                                              coef ? (const uint64_t *)d[3] : nullptr, num_vars, (uint64_t *)d[2], c->stream);
+                  });
+}
+int sr_vpoly_wround_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order, size_t *work_elems,
+                              int *launches) {
+    return round_plan_entry(kVpolyWroundFold, ring, log2_degree, num_vars, n_tables, n_terms, degree, order, work_elems, launches);
+}
+int sr_vpoly_wround_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
+                                   const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
+                                   const uint64_t *coef, size_t num_vars, const uint64_t *r, int order, uint64_t *work, size_t work_elems,
+                                   void *stream) {
+    sr::wsumcheck::Plan p;
+    if (!weights) return refuse(kVpolyWroundFold, "null pointer (d_weights)");
+    if (int rc = check_vpoly_terms(c, kVpolyWroundFold, out, out_tables, n_evals_out, r, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
+        return rc;
+    if (int rc = check_round_work(kVpolyWroundFold, p, work, work_elems)) return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8, ww = w << (num_vars - 2);
+    size_t n_out[SR_VPOLY_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
+    if (int rc = check_fold_overlaps(kVpolyWroundFold, p, w, out, out_tables, n_out, tables, n_evals, n_tables, coef, coef ? n_terms * w : 0, r, order,
+                                     work))
+        return rc;
+    if (ranges_overlap(out, p.np_total * w, weights, ww)) return refuse(kVpolyWroundFold, "d_out overlaps d_weights");
+    if (ranges_overlap(work, p.work_elems * w, weights, ww)) return refuse(kVpolyWroundFold, "d_work overlaps d_weights");
+    for (int j = 0; j < n_tables; j++)
+        if (ranges_overlap(out_tables[j], n_out[j] * w, weights, ww)) return refuse(kVpolyWroundFold, "a folded table overlaps d_weights");
+    const Call call(c, stream);
+    return dev_vpoly_wround_fold(c, p, order, out, out_tables, n_evals_out, weights, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, r, work,
+                                 call.st);
+}
+int sr_vpoly_wround_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
+                               const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
+                               const uint64_t *coef, size_t num_vars, const uint64_t *r, int order) {
+    sr::wsumcheck::Plan p;
+    if (!weights) return refuse(kVpolyWroundFold, "null pointer (weights)");
+    if (int rc = check_vpoly_terms(c, kVpolyWroundFold, out, out_tables, n_evals_out, r, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
+        return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    size_t n_out[SR_VPOLY_MAX_TABLES];
+    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
+    const TableSlot in(n_evals, n_tables, w), folded(n_out, n_tables, w);
+    // HOST_0: the tables; HOST_1: the message; HOST_2: the workspace; HOST_3: the folded tables; HOST_4: r, then (each on the next 16-byte
+    // boundary) the coefficients and the weights
+    const size_t coef_at = (w + 15) & ~(size_t)15, cw = coef ? n_terms * w : 0, weights_at = (coef_at + cw + 15) & ~(size_t)15,
+                 ww = w << (num_vars - 2);
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {nullptr, nullptr, folded.total},
+                      {nullptr, nullptr, weights_at + ww}},
+                  [&](void *const *d) -> int {
+                      uint64_t *dt[SR_VPOLY_MAX_TABLES], *dout[SR_VPOLY_MAX_TABLES];
+                      in.at(d[0], n_tables, dt);
+                      folded.at(d[3], n_tables, dout);
+                      const uint64_t *dcoef = coef ? (const uint64_t *)((const char *)d[4] + coef_at) : nullptr;
+                      const uint64_t *dweights = (const uint64_t *)((const char *)d[4] + weights_at);
+                      HIP_TRY(hipMemcpyAsync(d[4], r, w, hipMemcpyHostToDevice, c->stream));
+                      if (coef) HIP_TRY(hipMemcpyAsync((void *)dcoef, coef, cw, hipMemcpyHostToDevice, c->stream));
+                      HIP_TRY(hipMemcpyAsync((void *)dweights, weights, ww, hipMemcpyHostToDevice, c->stream));
+                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
+                      if (int rc = dev_vpoly_wround_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dweights, dt, n_evals, n_tables, terms,
+                                                         n_terms, dcoef, num_vars, (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
                           return rc;
                       for (int j = 0; j < n_tables; j++)
                           if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));

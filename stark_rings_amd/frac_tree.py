@@ -13,7 +13,7 @@ import ctypes
 
 import numpy as np
 
-from .mle import DenseMultilinearExtension
+from .mle import DenseMultilinearExtension, EqSumCheck, VirtualPolynomial
 from .rings import MLE_LEADING, MLE_TRAILING, STARK_POW2, RingError, _np_ptr
 
 
@@ -156,3 +156,15 @@ class FractionTree:
         half = q.numel() // 2
         nv = self._num_vars - k
         return tuple(DenseMultilinearExtension(self.ring, nv, t) for t in (p[:half], p[half:], q[:half], q[half:]))
+
+    def layer_claim(self, k, z, lam=None, stream=None):
+        """The sum-check of the layer claim P_k(z) + lam Q_k(z) = sum_b eq(z, b) (p_lo q_hi + p_hi q_lo + lam q_lo q_hi)(b) over
+        halves(k), as an EqSumCheck in trailing order: four tables and no eq table, where the explicit claim has five.  z:
+        num_vars - k ring elements, k < num_vars; lam: one ring element, or None for one().  The claimed sum message()[0] +
+        message()[1] is P_k(z) + lam Q_k(z) from evaluate of layer(k)."""
+        p_lo, p_hi, q_lo, q_hi = self.halves(k)
+        if q_lo.num_vars < 1:
+            raise RingError("FractionTree.layer_claim: the root's claim has no variable")
+        g = VirtualPolynomial(self.ring, q_lo.num_vars)
+        g.add_mle_list([p_lo, q_hi]).add_mle_list([p_hi, q_lo]).add_mle_list([q_lo, q_hi], lam)
+        return EqSumCheck(g, z, MLE_TRAILING, stream)

@@ -7,7 +7,7 @@ L_k[i] = L_{k-1}[i] * L_{k-1}[i + half]: the two operands of a layer are the con
 so the claim L_k(z) = sum_b eq(z, b) lo(b) hi(b) runs on VirtualPolynomial over views of the layers, nothing copied.  In leading
 order L_k[i] = L_{k-1}[2i] * L_{k-1}[2i+1].
 """
-from .mle import DenseMultilinearExtension
+from .mle import DenseMultilinearExtension, EqSumCheck, VirtualPolynomial
 from .rings import MLE_LEADING, MLE_TRAILING, RingError
 
 
@@ -80,3 +80,13 @@ class ProductTree:
         half = below.numel() // 2
         nv = self._num_vars - k
         return DenseMultilinearExtension(self.ring, nv, below[:half]), DenseMultilinearExtension(self.ring, nv, below[half:])
+
+    def layer_claim(self, k, z, lam=None, stream=None):
+        """The sum-check of the layer claim L_k(z) = sum_b eq(z, b) lo(b) hi(b) over halves(k), as an EqSumCheck in trailing order:
+        eq(z, .) is held as per-pair weights, not as a table.  z: num_vars - k ring elements, k < num_vars; the claimed sum
+        message()[0] + message()[1] is layer(k).evaluate(z).  lam is unused (the fraction tree's claim takes one)."""
+        lo, hi = self.halves(k)
+        if lo.num_vars < 1:
+            raise RingError("ProductTree.layer_claim: the root's claim has no variable (it is lo * hi)")
+        g = VirtualPolynomial(self.ring, lo.num_vars).add_mle_list([lo, hi])
+        return EqSumCheck(g, z, MLE_TRAILING, stream)

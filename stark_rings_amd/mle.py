@@ -333,6 +333,61 @@ class VirtualPolynomial:
         ring.vpoly_round_fold_evals_dev(out, folded, [t.evaluations for t in self.tables], self.terms, coeffs, nv, r, order, work, stream)
         return out, self._over([DenseMultilinearExtension(ring, nv - 1, f) for f in folded], nv - 1)
 
+    def round_evals_weighted(self, weights, order=MLE_LEADING, stream=None):
+        """The round message with a per-pair weight (sr_vpoly_wround_evals_dev): the degree + 1 elements
+        h(t) = sum_b weights[b] * g(t, b), t = 0 .. degree, b over the 2^(num_vars - 1) pairs of the round.  The weight is no factor:
+        it is constant in the round's variable and is not counted in the degree.  weights: a CUDA tensor of 2^(num_vars - 1) ring
+        elements, never written.  With eq(z_rest, .) as weights this is the eq(z, .) factor of a zero-check without a table
+        (EqSumCheck below)."""
+        import torch
+
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("round_evals_weighted: unknown order")
+        if not self.terms:
+            raise RingError("VirtualPolynomial: no product has been added")
+        ring, nv = self.ring, self._num_vars
+        like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
+        w = ring.words_per_elem
+        out = torch.empty((self.degree + 1) * w, dtype=like.dtype, device=like.device)
+        need = ring.vpoly_wround_plan(nv, len(self.tables), len(self.terms), self.degree, order)[0]
+        work = torch.empty(need * w, dtype=like.dtype, device=like.device) if need else None
+        coeffs = self._coeff_tensor(like, stream)
+        if stream is not None:
+            for t in (work, coeffs):
+                if t is not None:
+                    t.record_stream(stream)
+        ring._vpoly_wround_evals_dev(out, weights, [t.evaluations for t in self.tables], self.terms, coeffs, nv, order, work, stream)
+        return out
+
+    def fold_round_evals_weighted(self, r, next_weights, order=MLE_LEADING, stream=None):
+        """fold_round_evals with a per-pair weight on the message (sr_vpoly_wround_fold_evals_dev): every table slot folded at `r`,
+        and round_evals_weighted(next_weights) of the folded polynomial, in one pass.  next_weights: 2^(num_vars - 2) ring elements.
+        Returns (message, the polynomial over the folded tables in num_vars - 1 variables).  num_vars >= 2."""
+        import torch
+
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("fold_round_evals_weighted: unknown order")
+        if not self.terms:
+            raise RingError("VirtualPolynomial: no product has been added")
+        ring, nv = self.ring, self._num_vars
+        if nv < 2:
+            raise RingError("fold_round_evals_weighted: num_vars >= 2 (the last round folds with fixed_variables)")
+        like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
+        w = ring.words_per_elem
+        out = torch.empty((self.degree + 1) * w, dtype=like.dtype, device=like.device)
+        sizes = [(len(t) + 1) // 2 if order == MLE_LEADING else min(len(t), 1 << (nv - 1)) for t in self.tables]
+        folded = [torch.empty(n * w, dtype=like.dtype, device=like.device) for n in sizes]
+        need = ring.vpoly_wround_fold_plan(nv, len(self.tables), len(self.terms), self.degree, order)[0]
+        work = torch.empty(need * w, dtype=like.dtype, device=like.device) if need else None
+        coeffs = self._coeff_tensor(like, stream)
+        if stream is not None:
+            for t in folded + [work, coeffs]:
+                if t is not None:
+                    t.record_stream(stream)
+        ring._vpoly_wround_fold_evals_dev(out, folded, next_weights, [t.evaluations for t in self.tables], self.terms, coeffs, nv, r, order,
+                                         work, stream)
+        return out, self._over([DenseMultilinearExtension(ring, nv - 1, f) for f in folded], nv - 1)
+
     def fixed_variables(self, point, order=MLE_LEADING, stream=None):
         """The polynomial of the same terms and coefficients with the variables of `point` fixed in every distinct table:
         fixed_variables (MLE_LEADING) or fix_last_variables (MLE_TRAILING) per table slot -- the last round of a sum-check, and
@@ -344,6 +399,141 @@ class VirtualPolynomial:
             raise RingError("fixed_variables: the point has more entries than the polynomial has variables")
         fold = (lambda t: t.fixed_variables(point, stream)) if order == MLE_LEADING else (lambda t: t.fix_last_variables(point, stream))
         return self._over([fold(t) for t in self.tables], self._num_vars - n_fixed)
+
+
+class EqSumCheck:
+    """The prover of a whole sum-check of  sum_b eq(z, b) g(b)  -- a zero-check, R1CS, the layer claim of a product or fraction tree --
+    WITHOUT an eq table.  In the round that binds variable v, with the challenges r of the earlier rounds bound,
+        s(t) = [prod_{i bound} eq(z_i, r_i)] * eq(z_v, t) * h(t),   h(t) = sum_b w[b] g(t, b),   w = eq(z_rest, .)
+    where g is the claim without eq, folded at the challenges so far, and w the eq table of the unbound coordinates of z only: one
+    element per pair, constant in t, never folded (VirtualPolynomial.round_evals_weighted / fold_round_evals_weighted).  h has one
+    degree less than s; the message() is still the degree + 2 elements s(0 .. degree + 1), bit-identical to what the prover that holds
+    eq(z, .) as one more table sends (all arithmetic is exact on canonical values).
+
+    g: a VirtualPolynomial of n >= 1 variables (not modified); z: a CUDA tensor of n ring elements; order: MLE_LEADING binds variable
+    0 first, MLE_TRAILING variable n - 1.  The weights of all n rounds are built here with n eq_table_dev calls into one buffer of
+    2^n - 1 elements: round j = 1 .. n has 2^(n - j) elements, the eq table of z[j:] (leading) or z[:n - j] (trailing)."""
+
+    def __init__(self, g, z, order=MLE_LEADING, stream=None):
+        import torch
+
+        if order not in (MLE_LEADING, MLE_TRAILING):
+            raise RingError("EqSumCheck: unknown order")
+        ring, n = g.ring, g.num_vars
+        w = ring.words_per_elem
+        if n < 1 or not g.terms:
+            raise RingError("EqSumCheck: a polynomial of at least one variable and one product")
+        if z.numel() != n * w:
+            raise RingError("EqSumCheck: z must hold num_vars ring elements")
+        self.ring, self.order, self.stream, self.z = ring, order, stream, z
+        self._n, self._d = n, g.degree
+        self.g = g
+        self.round = 1
+        self.challenges = []
+        d = self._d
+        with self._on():
+            self.weights = torch.empty(((1 << n) - 1) * w, dtype=z.dtype, device=z.device)
+            consts = torch.zeros((2 * d + 5) * w, dtype=z.dtype, device=z.device)
+        for j in range(1, n + 1):
+            point = z[j * w:] if order == MLE_LEADING else z[:(n - j) * w]
+            ring.eq_table_dev(self._weights_of(j), point if point.numel() else None, stream)
+        # constants, from one() by additions only: R::from(t), t = 0 .. d + 1, and the signed binomials of the finite difference
+        self._one = consts[:w]
+        ring.eq_table_dev(self._one, None, stream)
+        self._t = consts[w:(d + 3) * w]  # zero, one, .., d + 1
+        for t in range(1, d + 2):
+            with self._on():
+                self._t[t * w:(t + 1) * w] = self._t[(t - 1) * w:t * w]
+            ring.add_dev(self._t[t * w:(t + 1) * w], self._one, stream)
+        self._binom = consts[(d + 3) * w:(2 * d + 4) * w]  # (-1)^(d - i) C(d + 1, i), i = 0 .. d
+        c = 1
+        for i in range(d + 1):
+            e = self._binom[i * w:(i + 1) * w]
+            for _ in range(c):
+                (ring.add_dev if (d - i) % 2 == 0 else ring.sub_dev)(e, self._one, stream)
+            c = c * (d + 1 - i) // (i + 1)
+        with self._on():
+            self._ones = self._one.repeat(d + 2)
+            self._prefix = self._one.clone()
+        self._h = g.round_evals_weighted(self._weights_of(1), order, stream)
+
+    def _on(self):
+        import contextlib
+
+        import torch
+
+        return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
+
+    def _weights_of(self, j):
+        """the weights of round j = 1 .. n: a view of 2^(n - j) elements"""
+        w, n = self.ring.words_per_elem, self._n
+        off = (1 << n) - (1 << (n - j + 1))
+        return self.weights[off * w:(off + (1 << (n - j))) * w]
+
+    def _z_of(self, j):
+        """the coordinate of z that round j binds"""
+        w = self.ring.words_per_elem
+        v = j - 1 if self.order == MLE_LEADING else self._n - j
+        return self.z[v * w:(v + 1) * w]
+
+    def _eq_line(self, j):
+        """(e0, step): eq(z_v, t) = e0 + t step with e0 = one() - z_v, step = 2 z_v - one()"""
+        with self._on():
+            e0 = self._one.clone()
+            step = self._z_of(j).clone()
+        self.ring.sub_dev(e0, self._z_of(j), self.stream)
+        self.ring.sub_dev(step, e0, self.stream)
+        return e0, step
+
+    @property
+    def degree(self):
+        """the degree of g; a message has degree + 2 elements"""
+        return self._d
+
+    def message(self):
+        """s(0 .. degree + 1) of the current round: degree + 2 ring elements"""
+        import torch
+
+        if self.round > self._n:
+            raise RingError("EqSumCheck: every variable is bound")
+        ring, st, w, d = self.ring, self.stream, self.ring.words_per_elem, self._d
+        with self._on():
+            s = torch.empty((d + 2) * w, dtype=self._h.dtype, device=self._h.device)
+            s[:(d + 1) * w] = self._h
+            hb = self._h.clone()
+        # h(d + 1) = sum_{i <= d} (-1)^(d - i) C(d + 1, i) h(i): the (d + 1)-th finite difference of a polynomial of degree d is zero
+        ring.ntt_mul_dev(hb, self._binom, st)
+        ring.sum_dev(s[(d + 1) * w:], hb, st)
+        e0, step = self._eq_line(self.round)
+        with self._on():
+            line = self._ones.clone()
+        ring.mul_elem_dev(line, e0, st)
+        ring.mul_elem_add_dev(line, self._t[:(d + 2) * w], step, st)
+        ring.ntt_mul_dev(s, line, st)
+        ring.mul_elem_dev(s, self._prefix, st)  # the prefix product last
+        return s
+
+    def next(self, r):
+        """binds the current round's variable to the challenge r (one ring element) and advances to the next round"""
+        if self.round > self._n:
+            raise RingError("EqSumCheck: every variable is bound")
+        ring, st, j = self.ring, self.stream, self.round
+        if self.g.num_vars >= 2:
+            self._h, self.g = self.g.fold_round_evals_weighted(r, self._weights_of(j + 1), self.order, st)
+        else:
+            self._h, self.g = None, self.g.fixed_variables(r, self.order, st)
+        e0, step = self._eq_line(j)
+        ring.mul_elem_add_dev(e0, step, r, st)  # eq(z_v, r)
+        ring.ntt_mul_dev(self._prefix, e0, st)
+        self.challenges.append(r)
+        self.round = j + 1
+        return self
+
+    def final(self):
+        """(the values of g's table slots at the challenges, one ring element each; eq(z, r)) once every variable is bound"""
+        if self.round <= self._n:
+            raise RingError("EqSumCheck: %d variables are still unbound" % (self._n - self.round + 1))
+        return [t.evaluations for t in self.g.tables], self._prefix
 
 
 def _next_pow2(n):

@@ -1225,6 +1225,140 @@ class CyclotomicRing:
                                                         _np_ptr(r), int(order)))
         return out, [f[:int(osizes[j]) * w] for j, f in enumerate(folded)]
 
+    def _plan_of(self, fn, num_vars, n_tables, n_terms, degree, order):
+        work = ctypes.c_size_t()
+        launches = ctypes.c_int()
+        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
+        self._check(fn(self.ring, k, int(num_vars), int(n_tables), int(n_terms), int(degree), int(order), ctypes.byref(work),
+                       ctypes.byref(launches)))
+        return work.value, launches.value
+
+    def vpoly_wround_plan(self, num_vars, n_tables, n_terms, degree, order=MLE_LEADING):
+        """sr_vpoly_wround_plan: (work_elems, launches) of a weighted round message (vpoly_wround_evals_dev) -- host arithmetic only."""
+        return self._plan_of(self._lib.sr_vpoly_wround_plan, num_vars, n_tables, n_terms, degree, order)
+
+    def vpoly_wround_fold_plan(self, num_vars, n_tables, n_terms, degree, order=MLE_LEADING):
+        """sr_vpoly_wround_fold_plan: (work_elems, launches) of the weighted fused fold-and-round call (vpoly_wround_fold_evals_dev),
+        num_vars >= 2 -- host arithmetic only."""
+        return self._plan_of(self._lib.sr_vpoly_wround_fold_plan, num_vars, n_tables, n_terms, degree, order)
+
+    def _wround_dev_args(self, what, out, weights, pairs_log2, tables, terms, coeffs, work):
+        """the arguments the two weighted device calls share: (po, pw8, ptrs, sizes, n, arr, n_terms, pc, pwork, nwork)"""
+        po, no = self._dev(out)
+        n = len(tables)
+        arr, n_terms, d = self._vpoly_terms(terms)
+        if no != self.words_per_elem * (d + 1):
+            raise RingError(what + ": out must hold d + 1 elements, d the longest term")
+        if weights is None:
+            pwt = ctypes.c_void_p(0)
+        else:
+            pwt, nwt = self._dev(weights)
+            if 0 <= pairs_log2 < 48 and nwt != self.words_per_elem << pairs_log2:
+                raise RingError(what + ": weights must hold one element per pair (2^%d)" % pairs_log2)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.numel())
+            ptrs[j] = self._dev(t)[0] if t.numel() else None
+        if coeffs is None:
+            pc = ctypes.c_void_p(0)
+        else:
+            pc, nc = self._dev(coeffs)
+            if nc != n_terms * self.words_per_elem:
+                raise RingError(what + ": one coefficient per term")
+        if work is None:
+            pw, nw = ctypes.c_void_p(0), 0
+        else:
+            pw, nw = self._dev(work)
+            nw //= self.words_per_elem
+        return po, pwt, ptrs, sizes, n, arr, n_terms, pc, pw, nw
+
+    def _vpoly_wround_evals_dev(self, out, weights, tables, terms, coeffs, num_vars, order=MLE_LEADING, work=None, stream=None):
+        """sr_vpoly_wround_evals_dev (public as stark_rings_amd.wsumcheck.vpoly_wround_evals_dev): the round message of
+        vpoly_round_evals_dev with a per-pair weight,
+        out[t] = sum_{b < half} weights[b] * sum_k c_k prod_s (lo_s[b] + t (hi_s[b] - lo_s[b])), t = 0 .. d (d the longest term; the
+        weight is not a factor).  weights: a CUDA tensor of 2^(num_vars - 1) ring elements, one per pair, never written; order:
+        MLE_LEADING or MLE_TRAILING.  The rest as vpoly_round_evals_dev.  work: at least vpoly_wround_plan()[0] elements."""
+        po, pwt, ptrs, sizes, n, arr, n_terms, pc, pw, nw = self._wround_dev_args("vpoly_wround_evals", out, weights, num_vars - 1, tables, terms,
+                                                                                  coeffs, work)
+        self._check(self._lib.sr_vpoly_wround_evals_dev(self._ctx, po, pwt, ptrs, sizes, n, arr, n_terms, pc, int(num_vars), int(order), pw, nw,
+                                                        self._stream(stream)))
+        return out
+
+    def _vpoly_wround_fold_evals_dev(self, out, out_tables, weights, tables, terms, coeffs, num_vars, r, order=MLE_LEADING, work=None,
+                                    stream=None):
+        """sr_vpoly_wround_fold_evals_dev (public as stark_rings_amd.wsumcheck.vpoly_wround_fold_evals_dev): vpoly_round_fold_evals_dev
+        with a per-pair weight on the message: the tables are folded at
+        `r` into out_tables exactly as there, and out[t], t = 0 .. d, is vpoly_wround_evals_dev on the folded tables at num_vars - 1
+        with the same `weights` (2^(num_vars - 2) ring elements).  Returns the list of elements written per table.  work: at least
+        vpoly_wround_fold_plan()[0] elements."""
+        po, pwt, ptrs, sizes, n, arr, n_terms, pc, pw, nw = self._wround_dev_args("vpoly_wround_fold_evals", out, weights, num_vars - 2, tables,
+                                                                                  terms, coeffs, work)
+        if len(out_tables) != n:
+            raise RingError("vpoly_wround_fold_evals: one output table per table")
+        pr, nr = self._dev(r)
+        if nr != self.words_per_elem:
+            raise RingError("vpoly_wround_fold_evals: r is not one ring element")
+        optrs = (ctypes.c_void_p * max(n, 1))()
+        osizes = (ctypes.c_size_t * max(n, 1))()
+        for j, o in enumerate(out_tables):
+            optrs[j] = self._dev(o)[0] if o.numel() else None
+            if 2 <= num_vars < 48:
+                need = (sizes[j] + 1) // 2 if order == MLE_LEADING else min(sizes[j], 1 << (num_vars - 1))
+                if o.numel() < need * self.words_per_elem:
+                    raise RingError("vpoly_wround_fold_evals: an output table is shorter than the folded table")
+        self._check(self._lib.sr_vpoly_wround_fold_evals_dev(self._ctx, po, optrs, osizes, pwt, ptrs, sizes, n, arr, n_terms, pc, int(num_vars),
+                                                             pr, int(order), pw, nw, self._stream(stream)))
+        return [int(osizes[j]) for j in range(n)]
+
+    def _wround_host_args(self, what, weights, tables, terms, coeffs):
+        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+        weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
+        n, w = len(tables), self.words_per_elem
+        arr, n_terms, d = self._vpoly_terms(terms)
+        out = np.empty(w * (max(d, 1) + 1), dtype=np.uint64)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.size)
+            ptrs[j] = t.ctypes.data if t.size else None
+        if coeffs is not None:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+            if coeffs.size != n_terms * w:
+                raise RingError(what + ": one coefficient per term")
+        # the arrays are returned so that they outlive the call
+        return tables, weights, coeffs, out, ptrs, sizes, n, arr, n_terms
+
+    def vpoly_wround_evals(self, weights, tables, terms, coeffs, num_vars, order=MLE_LEADING):
+        """Host buffers: sr_vpoly_wround_evals (see vpoly_wround_evals_dev); returns the d + 1 elements."""
+        tables, weights, coeffs, out, ptrs, sizes, n, arr, n_terms = self._wround_host_args("vpoly_wround_evals", weights, tables, terms, coeffs)
+        if weights is not None and 1 <= num_vars < 48 and weights.size != self.words_per_elem << (num_vars - 1):
+            raise RingError("vpoly_wround_evals: weights must hold one element per pair")
+        self._check(self._lib.sr_vpoly_wround_evals(self._ctx, _np_ptr(out), None if weights is None else weights.ctypes.data, ptrs, sizes, n, arr,
+                                                    n_terms, None if coeffs is None else coeffs.ctypes.data, int(num_vars), int(order)))
+        return out
+
+    def vpoly_wround_fold_evals(self, weights, tables, terms, coeffs, num_vars, r, order=MLE_LEADING):
+        """Host buffers: sr_vpoly_wround_fold_evals (see vpoly_wround_fold_evals_dev); returns (message, list of folded tables)."""
+        tables, weights, coeffs, out, ptrs, sizes, n, arr, n_terms = self._wround_host_args("vpoly_wround_fold_evals", weights, tables, terms,
+                                                                                            coeffs)
+        r = np.ascontiguousarray(r, dtype=np.uint64)
+        w = self.words_per_elem
+        if r.size != w:
+            raise RingError("vpoly_wround_fold_evals: r is not one ring element")
+        if weights is not None and 2 <= num_vars < 48 and weights.size != w << (num_vars - 2):
+            raise RingError("vpoly_wround_fold_evals: weights must hold one element per pair of the folded tables")
+        optrs = (ctypes.c_void_p * max(n, 1))()
+        osizes = (ctypes.c_size_t * max(n, 1))()
+        folded = []
+        for j, t in enumerate(tables):
+            folded.append(np.empty(t.size, dtype=np.uint64))  # never shorter than the folded table
+            optrs[j] = folded[j].ctypes.data if t.size else None
+        self._check(self._lib.sr_vpoly_wround_fold_evals(self._ctx, _np_ptr(out), optrs, osizes, None if weights is None else weights.ctypes.data,
+                                                         ptrs, sizes, n, arr, n_terms, None if coeffs is None else coeffs.ctypes.data,
+                                                         int(num_vars), _np_ptr(r), int(order)))
+        return out, [f[:int(osizes[j]) * w] for j, f in enumerate(folded)]
+
     def eq_table_dev(self, out, point, stream=None):
         """sr_eq_table_dev: out[b] = prod_i (bit i of b ? point[i] : 1 - point[i]) for the n = len(point) elements of `point`
         (None or empty: out is the single element one()); out holds 2^n elements.  One launch, no workspace; capturable."""
