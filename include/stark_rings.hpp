@@ -29,6 +29,10 @@
 //   DenseMultilinearExtension<RqNTT>     crates/poly mle/dense.rs    class DenseMultilinearExtension: fix_variables, fixed_variables,
 //     (fix_variables, evaluate, +=)                                    fix_last_variables, evaluate, add_assign_scaled, to_evaluations;
 //                                                                      round_evals / product_sum: a sum-check round's message (sr_mle_round_evals)
+//     AddAssign<(R, &Self)>, MulAssign<R>, dense.rs:288-317, 370-374, lincomb_plan / lincomb / lincomb_dev (sr_lincomb: the three composed, up to 16
+//     Add<R>, in one pass                  386-395                     tables and 4 outputs); DenseMultilinearExtension::linear_combination;
+//                                                                      fingerprint, permutation_leaves, class PermutationCheck / LookupCheck /
+//                                                                      LayerClaim: leaves, trees and layer claims of both arguments
 //   a sum of products of dense MLEs      (HyperPlonk's VirtualPolynomial) class VirtualPolynomial: add_mle_list, mul_by_mle, degree, round_evals, sum
 //                                                                      (sr_vpoly_round_evals: one pass, every distinct table read once),
 //                                                                      fold_round_evals (sr_vpoly_round_fold_evals: fold at the challenge
@@ -73,6 +77,7 @@
 // Errors: the reference panics (assert_eq!(len, D): goldilocks/ntt.rs:136, stark_prime/ntt.rs:122; "Wrong length":
 // coeff_form.rs:39); here std::length_error / std::runtime_error are thrown.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <optional>
@@ -427,6 +432,44 @@ private:
     std::vector<uint64_t> w_;
 };
 
+// sr_lincomb_plan: {kernel launches, outputs one launch produces} of a linear combination of n_tables tables into n_outputs outputs
+inline std::pair<int, int> lincomb_plan(sr_ring ring, int log2_degree, int n_tables, int n_outputs) {
+    int launches = 0, per = 0;
+    CyclotomicConfig::check(sr_lincomb_plan(ring, log2_degree, n_tables, n_outputs, &launches, &per), "sr_lincomb_plan");
+    return {launches, per};
+}
+// sr_lincomb_dev on device pointers: out_m[e] = [bit K of uses[m]] coef[m][K] + sum_{k < K, bit k of uses[m]} coef[m][k] * T_k[e] for
+// e < n, the composition of dense.rs's AddAssign<(R, &Self)> (:288-317), MulAssign<R> (:370-374) and Add<R> (:386-395) in one pass.
+// d_outs / d_tables / uses are host arrays; n_evals may be null (every table full); allocates nothing.  Throws where the C call refuses.
+inline void lincomb_dev(const CyclotomicConfig &cfg, uint64_t *const *d_outs, int n_outputs, const uint64_t *const *d_tables, const size_t *n_evals,
+                        int n_tables, const uint64_t *d_coef, const uint32_t *uses, size_t n, void *stream = nullptr) {
+    CyclotomicConfig::check(sr_lincomb_dev(cfg.raw(), d_outs, n_outputs, d_tables, n_evals, n_tables, d_coef, uses, n, stream), "sr_lincomb_dev");
+}
+// sr_lincomb on host words: tables[k] holds its stored elements (at most n, the rest of the table is zero), coef the uses.size() rows of
+// tables.size() + 1 elements (the constant last); returns the uses.size() outputs of n elements each
+inline std::vector<std::vector<uint64_t>> lincomb(const CyclotomicConfig &cfg, const std::vector<const std::vector<uint64_t> *> &tables,
+                                                  const std::vector<uint64_t> &coef, const std::vector<uint32_t> &uses, size_t n) {
+    const size_t w = cfg.words_per_elem();
+    if (tables.empty() || tables.size() > SR_LINCOMB_MAX_TABLES) throw std::length_error("lincomb: 1 .. 16 tables");
+    if (uses.empty() || uses.size() > SR_LINCOMB_MAX_OUTPUTS) throw std::length_error("lincomb: 1 .. 4 outputs");
+    if (coef.size() != uses.size() * (tables.size() + 1) * w) throw std::length_error("lincomb: coef must hold n_outputs x (n_tables + 1) elements");
+    std::vector<std::vector<uint64_t>> outs(uses.size(), std::vector<uint64_t>(n * w));
+    const uint64_t dummy = 0;
+    uint64_t sink = 0;
+    std::vector<const uint64_t *> pt;
+    std::vector<size_t> sizes;
+    std::vector<uint64_t *> po;
+    for (const std::vector<uint64_t> *t : tables) {
+        if (t->size() % w) throw std::length_error("Should be of correct length");
+        pt.push_back(t->empty() ? &dummy : t->data());
+        sizes.push_back(t->size() / w);
+    }
+    for (auto &o : outs) po.push_back(o.empty() ? &sink : o.data());
+    CyclotomicConfig::check(sr_lincomb(cfg.raw(), po.data(), (int)uses.size(), pt.data(), sizes.data(), (int)tables.size(), coef.data(), uses.data(), n),
+                            "sr_lincomb");
+    return outs;
+}
+
 // DenseMultilinearExtension<RqNTT> of crates/poly (src/mle/dense.rs): a table of 2^num_vars ring elements in CRT/NTT form, of which
 // only the first len() are stored -- the rest is zero (dense.rs:35-54, 397-407).  Host buffers over sr_mle_fix_variables /
 // sr_mul_elem_add_batch; `r * a` is the slot product of the ring.  Throws where the reference asserts.
@@ -465,6 +508,32 @@ public:
             CyclotomicConfig::check(sr_mul_elem_add_batch(cfg_.raw(), w_.data(), other.w_.data(), r.words().data(), other.len()),
                                     "DenseMultilinearExtension +=");
         return *this;
+    }
+    // sum_k coeffs[k] * mles[k] (+ constant) from 1 .. 16 MLEs of one ring and one num_vars in one pass (sr_lincomb): MulAssign<R>,
+    // AddAssign<(R, &Self)> and Add<R> of dense.rs composed.  coeffs: one ring element per MLE; constant: one ring element or null.  The
+    // inputs may be truncated; the result stores the longest input's evaluations, or all 2^num_vars with a constant (which goes to every
+    // evaluation, where the reference's Add<R> touches only the stored ones).
+    static DenseMultilinearExtension linear_combination(const std::vector<const DenseMultilinearExtension *> &mles, const RqNTTVec &coeffs,
+                                                        const RqNTTVec *constant = nullptr) {
+        if (mles.empty() || mles.size() > SR_LINCOMB_MAX_TABLES) throw std::length_error("linear_combination: 1 .. 16 MLEs");
+        const DenseMultilinearExtension &first = *mles[0];
+        const size_t w = first.cfg_.words_per_elem();
+        if (coeffs.len() != mles.size() || (constant && constant->len() != 1))
+            throw std::length_error("linear_combination: one coefficient per MLE, and a constant of one ring element");
+        std::vector<const std::vector<uint64_t> *> tables;
+        size_t n = 0;
+        for (const DenseMultilinearExtension *m : mles) {
+            if (m->cfg_.raw() != first.cfg_.raw() || m->nv_ != first.nv_) throw std::length_error("linear_combination: the MLEs differ in ring or num_vars");
+            tables.push_back(&m->w_);
+            n = std::max(n, m->len());
+        }
+        if (constant) n = (size_t)1 << first.nv_;
+        std::vector<uint64_t> coef(coeffs.words());
+        if (constant) coef.insert(coef.end(), constant->words().begin(), constant->words().end());
+        else coef.resize(coef.size() + w, 0);
+        const uint32_t mask = (((uint32_t)1 << mles.size()) - 1) | (constant ? (uint32_t)1 << mles.size() : 0);
+        auto outs = lincomb(first.cfg_, tables, coef, {mask}, n);
+        return DenseMultilinearExtension(first.cfg_, first.nv_, std::move(outs[0]));
     }
     RqNTTVec to_evaluations() const {  // all 2^num_vars elements
         std::vector<uint64_t> all(w_);
@@ -1048,6 +1117,105 @@ private:
     int order_;
     size_t n_, d_, round_;
     RqNTTVec prefix_, h_;
+};
+
+// The leaves of a permutation argument from ONE call over the three tables (K = 3, M = 2): {num, den} = {beta + f + gamma id,
+// beta + f + gamma sigma}; the mask of each row leaves out the table it does not use.  beta, gamma, one: one ring element each.
+inline std::pair<std::vector<uint64_t>, std::vector<uint64_t>> permutation_leaves(const CyclotomicConfig &cfg, const std::vector<uint64_t> &f,
+                                                                                  const std::vector<uint64_t> &ident, const std::vector<uint64_t> &sigma,
+                                                                                  const RqNTTVec &beta, const RqNTTVec &gamma, const RqNTTVec &one) {
+    const size_t w = cfg.words_per_elem();
+    if (ident.size() != f.size() || sigma.size() != f.size() || f.size() % w) throw std::length_error("permutation_leaves: the tables differ in length");
+    if (beta.len() != 1 || gamma.len() != 1 || one.len() != 1) throw std::length_error("permutation_leaves: beta, gamma and one are one ring element each");
+    std::vector<uint64_t> coef;
+    for (int row = 0; row < 2; row++)
+        for (const RqNTTVec *c : {&one, &gamma, &gamma, &beta}) coef.insert(coef.end(), c->words().begin(), c->words().end());
+    auto outs = lincomb(cfg, {&f, &ident, &sigma}, coef, {0xBu, 0xDu}, f.size() / w);
+    return {std::move(outs[0]), std::move(outs[1])};
+}
+// One table sum_k coeffs[k] * columns[k] (+ constant) from 1 .. 16 columns of equal length, in one pass
+inline std::vector<uint64_t> fingerprint(const CyclotomicConfig &cfg, const std::vector<const std::vector<uint64_t> *> &columns, const RqNTTVec &coeffs,
+                                         const RqNTTVec *constant = nullptr) {
+    const size_t w = cfg.words_per_elem();
+    if (columns.empty() || coeffs.len() != columns.size() || (constant && constant->len() != 1))
+        throw std::length_error("fingerprint: one coefficient per column, and a constant of one ring element");
+    for (const auto *c : columns)
+        if (c->size() != columns[0]->size()) throw std::length_error("fingerprint: the columns differ in length");
+    std::vector<uint64_t> coef(coeffs.words());
+    if (constant) coef.insert(coef.end(), constant->words().begin(), constant->words().end());
+    else coef.resize(coef.size() + w, 0);
+    const uint32_t mask = (((uint32_t)1 << columns.size()) - 1) | (constant ? (uint32_t)1 << columns.size() : 0);
+    return std::move(lincomb(cfg, columns, coef, {mask}, columns[0]->size() / w)[0]);
+}
+
+// The layer claim of a tree as an object that owns its operands: the halves of the layer below, the polynomial over them and the
+// EqSumCheck of eq(z, .) times it (VirtualPolynomial refers to its MLEs, so they live here).
+class LayerClaim {
+public:
+    LayerClaim(const CyclotomicConfig &cfg, std::vector<DenseMultilinearExtension> halves, const RqNTTVec &z, const RqNTTVec *lam)
+        : halves_(std::move(halves)), g_(cfg, halves_.at(0).num_vars()) {
+        if (halves_.size() == 2) {
+            g_.add_mle_list({&halves_[0], &halves_[1]});
+        } else {  // {p_lo, p_hi, q_lo, q_hi}: p_lo q_hi + p_hi q_lo + lam q_lo q_hi
+            g_.add_mle_list({&halves_[0], &halves_[3]});
+            g_.add_mle_list({&halves_[1], &halves_[2]});
+            g_.add_mle_list({&halves_[2], &halves_[3]}, lam);
+        }
+        check_.emplace(g_, z, SR_MLE_TRAILING);
+    }
+    LayerClaim(const LayerClaim &) = delete;
+    LayerClaim &operator=(const LayerClaim &) = delete;
+    EqSumCheck &sumcheck() { return *check_; }
+
+private:
+    std::vector<DenseMultilinearExtension> halves_;
+    VirtualPolynomial g_;
+    std::optional<EqSumCheck> check_;
+};
+
+// Two ProductTrees in trailing order over the numerator and denominator leaves of a permutation (multiset-equality) argument
+class PermutationCheck {
+public:
+    PermutationCheck(CyclotomicConfig cfg, std::vector<uint64_t> num_leaf_words, std::vector<uint64_t> den_leaf_words, size_t num_vars)
+        : cfg_(cfg), num_(cfg, std::move(num_leaf_words), num_vars, SR_MLE_TRAILING), den_(cfg, std::move(den_leaf_words), num_vars, SR_MLE_TRAILING) {}
+    const ProductTree &num() const { return num_; }
+    const ProductTree &den() const { return den_; }
+    std::pair<RqNTTVec, RqNTTVec> roots() const { return {num_.root(), den_.root()}; }
+    bool holds() const { return num_.root().words() == den_.root().words(); }
+    // side 0: the numerators, 1: the denominators; z: num_vars - k ring elements
+    std::unique_ptr<LayerClaim> layer_claim(int side, size_t k, const RqNTTVec &z) const {
+        const auto h = (side == 0 ? num_ : den_).halves(k);
+        return std::make_unique<LayerClaim>(cfg_, std::vector<DenseMultilinearExtension>{h.first, h.second}, z, nullptr);
+    }
+
+private:
+    CyclotomicConfig cfg_;
+    ProductTree num_, den_;
+};
+
+// Two FractionTrees in trailing order of a logUp lookup: the witness side sums 1 / witness_q[i] (no stored numerators), the table side
+// multiplicities[j] / table_q[j]; the multiplicities are ring elements supplied by the caller.  holds(): P_w Q_t == P_t Q_w, a
+// polynomial identity in the challenge that needs no inverse and excludes no challenge.
+class LookupCheck {
+public:
+    LookupCheck(CyclotomicConfig cfg, std::vector<uint64_t> witness_q, std::vector<uint64_t> table_q, std::vector<uint64_t> multiplicities,
+                size_t num_vars_w, size_t num_vars_t)
+        : cfg_(cfg), witness_(cfg, std::move(witness_q), num_vars_w, SR_MLE_TRAILING),
+          table_(cfg, std::move(multiplicities), std::move(table_q), num_vars_t, SR_MLE_TRAILING) {}
+    const FractionTree &witness() const { return witness_; }
+    const FractionTree &table() const { return table_; }
+    bool holds() const {
+        const auto rw = witness_.root(), rt = table_.root();
+        return (rw.first * rt.second).words() == (rt.first * rw.second).words();
+    }
+    // side 0: the witness, 1: the table; z: num_vars - k ring elements; lam: one ring element
+    std::unique_ptr<LayerClaim> layer_claim(int side, size_t k, const RqNTTVec &z, const RqNTTVec &lam) const {
+        return std::make_unique<LayerClaim>(cfg_, (side == 0 ? witness_ : table_).halves(k), z, &lam);
+    }
+
+private:
+    CyclotomicConfig cfg_;
+    FractionTree witness_, table_;
 };
 
 // SparseMultilinearExtension<RqNTT> of crates/poly (src/mle/sparse.rs): the stored evaluations as ascending indices and their values

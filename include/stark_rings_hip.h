@@ -543,6 +543,37 @@ int sr_frac_tree_dev(sr_ctx *ctx, uint64_t *d_p_layers, uint64_t *d_q_layers, co
                      size_t n_leaves, size_t num_vars, int order, void *stream);
 int sr_frac_tree(sr_ctx *ctx, uint64_t *p_layers, uint64_t *q_layers, const uint64_t *p_leaves, const uint64_t *q_leaves, size_t n_leaves,
                  size_t num_vars, int order);
+/* Linear combinations (csrc/lincomb.hpp): up to SR_LINCOMB_MAX_OUTPUTS tables from up to SR_LINCOMB_MAX_TABLES in one pass, with
+ * ring-element coefficients -- the leaves of a permutation argument (beta + f + gamma id, beta + f + gamma sigma) or a logUp lookup
+ * (beta - sum_k gamma^k col_k), the fold sum_i rho_i f_i of many instances into one, many MLEs batched into one.  For every ring id,
+ * with elements in CRT/NTT form, `*` the slot product of sr_mul_elem_add_batch and `+` the slot sum:
+ *   out_m[e] = [bit n_tables of uses[m]] coef[m][n_tables]  +  sum_{k < n_tables, bit k of uses[m]} coef[m][k] * T_k[e]      e < n
+ * It is the composition of three operators of crates/poly's DenseMultilinearExtension: AddAssign<(R, &Self)> (mle/dense.rs:288-317),
+ * MulAssign<R> (:370-374) and Add<R> (:386-395).  The constant goes to every one of the n output elements: that is the mathematical
+ * definition, whereas the reference's Add<R> touches only the stored evaluations of a truncated MLE.
+ * d_outs, d_tables: HOST arrays of n_outputs / n_tables device pointers; they reach the kernel by value, so a captured graph holds no
+ * host pointer.  d_coef: n_outputs x (n_tables + 1) ring elements on the device, row-major, entry n_tables of a row the additive
+ * constant.  uses: a HOST array of one bit mask per output; an entry of d_coef whose bit is clear is never read and may hold anything.
+ * n_evals[k] <= n: the stored part of table k; the rest of it is zero and is never loaded.  n_evals == NULL: every table is full.
+ * All n elements of every output are written.  Canonical inputs give canonical outputs.  n = 0 succeeds and launches nothing; n < 2^48.
+ * Nothing is allocated and no context scratch is touched: no warm-up and no sr_ctx_reserve_scratch before a capture.
+ * Tables may coincide or overlap each other.  Outputs are mutually disjoint and disjoint from d_coef.  An output may be the same
+ * buffer as a table (the same base pointer: in place) only when n_outputs == 1 -- several outputs may go in several launches, and a
+ * later launch would read what an earlier one wrote.  Every other overlap is SR_E_INVALID.  Also SR_E_INVALID, each with its own
+ * message and before any device work: a null context (first), n_tables outside 1 .. 16, n_outputs outside 1 .. 4, a null pointer, a
+ * mask of zero, a mask bit above n_tables, a table that no output uses, n_evals[k] > n.
+ * sr_lincomb_plan: pure host arithmetic -- the kernel launches of a call and the outputs one launch produces.  A call of at most
+ * four tables whose outputs fit one launch keeps its coefficients in registers (two outputs on Goldilocks and BabyBear, one on Stark
+ * and goldilocks24, none on babybear72 and frog16); otherwise a launch produces four outputs on BabyBear, three on Goldilocks, one on
+ * the other rings, and reads every table once per launch.
+ * The host-pointer form stages whole tables like sr_mle_fix_variables (the chunked pipeline takes two operands, not seventeen): the
+ * stored parts of the tables, the outputs and the coefficients live in context-owned device temporaries for the call. */
+enum { SR_LINCOMB_MAX_TABLES = 16, SR_LINCOMB_MAX_OUTPUTS = 4 };
+int sr_lincomb_plan(int ring, int log2_degree, int n_tables, int n_outputs, int *launches, int *outputs_per_launch);
+int sr_lincomb_dev(sr_ctx *ctx, uint64_t *const *d_outs, int n_outputs, const uint64_t *const *d_tables, const size_t *n_evals,
+                   int n_tables, const uint64_t *d_coef, const uint32_t *uses, size_t n, void *stream);
+int sr_lincomb(sr_ctx *ctx, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+               const uint64_t *coef, const uint32_t *uses, size_t n);
 /* Norms of a coefficient slice on the device: WithLinfNorm::linf_norm / WithL2Norm::l2_norm_squared over [Fq]
  * (crates/ring/src/traits.rs:6-36; per element balanced_decomposition/convertible_ring.rs:49-66; the signed representative of
  * fq_convertible.rs:20-34 and stark_prime/decomposition.rs:40-52).

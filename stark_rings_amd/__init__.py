@@ -12,6 +12,8 @@ Layout:
   wsumcheck.py          the device-pointer forms of the weighted sum-check rounds (sr_vpoly_wround_evals_dev, sr_vpoly_wround_fold_evals_dev)
   grand_product.py      ProductTree: every layer of a table's binary product tree, the circuit of the layered grand-product argument
   frac_tree.py          FractionTree: every layer of a sum of fractions p/q, the circuit of the layered logUp (lookup, range) argument
+  lincomb.py            linear combinations of up to 16 tables with ring-element coefficients, up to 4 outputs from one pass
+  lookup.py             PermutationCheck and LookupCheck: leaves (lincomb), trees and layer claims end to end on the device
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
   sparse.py             SparseMatrix of crates/linear_algebra with device-resident values: transpose, sparse x sparse product
   monomial.py           the reference's monomial helpers (monomial.rs) over the ring product
@@ -33,5 +35,7 @@ from .mle import DenseMultilinearExtension, EqSumCheck, SparseMultilinearExtensi
 from .grand_product import ProductTree  # noqa: F401
 from .wsumcheck import vpoly_wround_evals_dev, vpoly_wround_fold_evals_dev  # noqa: F401
 from .frac_tree import FractionTree, frac_tree_dev, frac_tree_plan  # noqa: F401  (the host-pointer form: frac_tree.frac_tree)
+from .lincomb import lincomb_dev, lincomb_plan  # noqa: F401  (the host-pointer form: lincomb.lincomb)
+from .lookup import LookupCheck, PermutationCheck, fingerprint, permutation_leaves  # noqa: F401
 from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401
 from .sparse import SparseMatrixNTT  # noqa: F401

@@ -51,6 +51,10 @@ SYMBOLS = {
     "sr_frac_tree_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_int,
                                     _c.c_void_p]),
     "sr_frac_tree": (_c.c_int, [_c.c_void_p, u64p, u64p, u64p, u64p, _c.c_size_t, _c.c_size_t, _c.c_int]),
+    "sr_lincomb_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sr_lincomb_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                  _c.c_void_p]),
+    "sr_lincomb": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, u64p, _c.c_void_p, _c.c_size_t]),
     "sr_mle_round_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
     "sr_mle_round_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_void_p,
                                           _c.c_size_t, _c.c_void_p]),

@@ -40,6 +40,7 @@
 #include "sumcheck_weighted.hpp"
 #include "prod_tree.hpp"
 #include "frac_tree.hpp"
+#include "lincomb.hpp"
 
 namespace {
 
@@ -2214,6 +2215,82 @@ int check_frac_tree(sr_ctx *c, const void *p_layers, const void *q_layers, const
     if (p_leaves && ranges_overlap(q_layers, out, p_leaves, in)) return fail(SR_E_INVALID, "frac_tree: d_q_layers overlaps d_p_leaves");
     return SR_OK;
 }
+// ---- linear combinations (csrc/lincomb.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch -------------------
+// The launches of sr::lincomb::plan: outputs m0 .. m0 + outputs_per_launch - 1 each, every launch over all the tables.
+int dev_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                const uint64_t *coef, const uint32_t *uses, size_t n, hipStream_t st) {
+    if (n == 0) return SR_OK;
+    sr::lincomb::Plan p;
+    if (!sr::lincomb::plan(c->ring, n_tables, n_outputs, &p)) return fail(SR_E_INVALID, "lincomb: no plan for these arguments");
+    const size_t w = (size_t)c->degree * c->limbs;
+    uintptr_t all = (uintptr_t)coef;
+    for (int k = 0; k < n_tables; k++) all |= (uintptr_t)tables[k];
+    for (int m = 0; m < n_outputs; m++) all |= (uintptr_t)outs[m];
+    const bool aligned = (all & 15u) == 0;
+    for (int m0 = 0; m0 < n_outputs; m0 += p.outputs_per_launch) {
+        const int mm = n_outputs - m0 < p.outputs_per_launch ? n_outputs - m0 : p.outputs_per_launch;
+        const bool reg = p.launches == 1 && n_tables <= sr::lincomb::kRegTables;
+        sr::lincomb::Args a{};
+        for (int k = 0; k < n_tables; k++) {
+            a.t[k] = tables[k];
+            a.ne[k] = n_evals ? n_evals[k] : n;
+        }
+        for (int m = 0; m < mm; m++) {
+            a.out[m] = outs[m0 + m];
+            a.uses[m] = uses[m0 + m];
+        }
+        a.coef = coef + (size_t)m0 * (n_tables + 1) * w;
+        ProfScope prof(c, st, K_POINTWISE);
+        hipError_t e;
+        switch (c->ring) {
+            case SR_RING_GOLDILOCKS_POW2: e = sr::lincomb::launch<sr::Goldilocks>({}, reg && mm <= sr::lincomb::kRegOutputs<sr::Goldilocks>, mm, a, n_tables, n, c->k, aligned, st); break;
+            case SR_RING_BABYBEAR_POW2: e = sr::lincomb::launch<sr::BabyBear>({}, reg && mm <= sr::lincomb::kRegOutputs<sr::BabyBear>, mm, a, n_tables, n, c->k, aligned, st); break;
+            case SR_RING_STARK_POW2: e = sr::lincomb::launch<sr::Stark>({}, reg && mm <= sr::lincomb::kRegOutputs<sr::Stark>, mm, a, n_tables, n, c->k, aligned, st); break;
+            case SR_RING_GOLDILOCKS_24: e = sr::lincomb::launch<sr::SlotG24>(c->small, reg && mm <= sr::lincomb::kRegOutputs<sr::SlotG24>, mm, a, n_tables, n, 0, aligned, st); break;
+            case SR_RING_BABYBEAR_72: e = sr::lincomb::launch<sr::SlotB72>(c->small, false, mm, a, n_tables, n, 0, aligned, st); break;
+            default: e = sr::lincomb::launch<sr::SlotFrog>(c->frog, false, mm, a, n_tables, n, 0, aligned, st); break;
+        }
+        if (e != hipSuccess) return fail(SR_E_HIP, std::string("lincomb launch: ") + hipGetErrorString(e));
+    }
+    return SR_OK;
+}
+// the argument checks the two forms of sr_lincomb share; everything here is host arithmetic on the arguments
+int check_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                  const uint64_t *coef, const uint32_t *uses, size_t n) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (n_tables < 1 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb: n_tables outside 1 .. 16");
+    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb: n_outputs outside 1 .. 4");
+    if (!outs || !tables || !coef || !uses) return fail(SR_E_INVALID, "lincomb: null argument");
+    uint32_t any = 0;
+    for (int m = 0; m < n_outputs; m++) {
+        if (uses[m] == 0) return fail(SR_E_INVALID, "lincomb: an output with an empty mask");
+        if (uses[m] >> (n_tables + 1)) return fail(SR_E_INVALID, "lincomb: a mask bit above n_tables");
+        any |= uses[m];
+    }
+    for (int k = 0; k < n_tables; k++)
+        if (!((any >> k) & 1u)) return fail(SR_E_INVALID, "lincomb: a table that no output uses");
+    if (n >= (size_t)1 << 48) return fail(SR_E_INVALID, "lincomb: n must be below 2^48");
+    for (int k = 0; k < n_tables; k++)
+        if (n_evals && n_evals[k] > n) return fail(SR_E_INVALID, "lincomb: n_evals exceeds n");
+    for (int k = 0; k < n_tables; k++)
+        if (!tables[k]) return fail(SR_E_INVALID, "lincomb: null table");
+    for (int m = 0; m < n_outputs; m++)
+        if (!outs[m]) return fail(SR_E_INVALID, "lincomb: null output");
+    if (int rc = check_count(c, n)) return rc;  // everything above is decided without reading the context
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    for (int m = 0; m < n_outputs; m++) {
+        for (int j = 0; j < m; j++)
+            if (ranges_overlap(outs[m], n * w, outs[j], n * w)) return fail(SR_E_INVALID, "lincomb: two outputs overlap");
+        if (ranges_overlap(outs[m], n * w, coef, (size_t)n_outputs * (n_tables + 1) * w))
+            return fail(SR_E_INVALID, "lincomb: an output overlaps the coefficients");
+        for (int k = 0; k < n_tables; k++) {
+            if (!ranges_overlap(outs[m], n * w, tables[k], (n_evals ? n_evals[k] : n) * w)) continue;
+            if (outs[m] != tables[k]) return fail(SR_E_INVALID, "lincomb: an output overlaps a table");
+            if (n_outputs != 1) return fail(SR_E_INVALID, "lincomb: in place needs n_outputs == 1");
+        }
+    }
+    return SR_OK;
+}
 // d_counter[i] (sr_ctx_create_ex) to the host, then cleared
 int read_counter(sr_ctx *c, int i, unsigned long long *out, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(out, c->d_counter + i, sizeof *out, hipMemcpyDeviceToHost, st));
@@ -2834,6 +2911,52 @@ int sr_frac_tree(sr_ctx *c, uint64_t *p_layers, uint64_t *q_layers, const uint64
                       return dev_frac_tree(c, (uint64_t *)d[2], (uint64_t *)d[3], p_leaves ? (const uint64_t *)d[1] : nullptr, (const uint64_t *)d[0],
                                            n_leaves, num_vars, order, c->stream);
                   });
+}
+int sr_lincomb_plan(int ring, int log2_degree, int n_tables, int n_outputs, int *launches, int *outputs_per_launch) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!launches || !outputs_per_launch) return fail(SR_E_INVALID, "lincomb_plan: null result pointer");
+    if (n_tables < 1 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_plan: n_tables outside 1 .. 16");
+    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb_plan: n_outputs outside 1 .. 4");
+    sr::lincomb::Plan p;
+    if (!sr::lincomb::plan(ring, n_tables, n_outputs, &p)) return fail(SR_E_INVALID, "lincomb_plan: no plan for these arguments");
+    *launches = p.launches;
+    *outputs_per_launch = p.outputs_per_launch;
+    return SR_OK;
+}
+int sr_lincomb_dev(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                   const uint64_t *coef, const uint32_t *uses, size_t n, void *stream) {
+    if (int rc = check_lincomb(c, outs, n_outputs, tables, n_evals, n_tables, coef, uses, n)) return rc;
+    const Call call(c, stream);
+    return dev_lincomb(c, outs, n_outputs, tables, n_evals, n_tables, coef, uses, n, call.st);
+}
+int sr_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+               const uint64_t *coef, const uint32_t *uses, size_t n) {
+    if (int rc = check_lincomb(c, outs, n_outputs, tables, n_evals, n_tables, coef, uses, n)) return rc;
+    if (n == 0) return SR_OK;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8, ob = (n * w + 15) & ~(size_t)15;
+    // HOST_0: the stored parts of the tables, one behind the other on 16-byte boundaries; HOST_1: the outputs; HOST_2: the coefficients
+    size_t off[SR_LINCOMB_MAX_TABLES], total = 0;
+    for (int k = 0; k < n_tables; k++) {
+        off[k] = total;
+        total += ((n_evals ? n_evals[k] : n) * w + 15) & ~(size_t)15;
+    }
+    const int rc = staged(c, {{nullptr, nullptr, total}, {nullptr, nullptr, ob * n_outputs}, {coef, nullptr, (size_t)n_outputs * (n_tables + 1) * w}},
+                          [&](void *const *d) -> int {
+                              const uint64_t *dt[SR_LINCOMB_MAX_TABLES];
+                              uint64_t *dout[SR_LINCOMB_MAX_OUTPUTS];
+                              for (int k = 0; k < n_tables; k++) {
+                                  dt[k] = (const uint64_t *)((char *)d[0] + off[k]);
+                                  const size_t b = (n_evals ? n_evals[k] : n) * w;
+                                  if (b) HIP_TRY(hipMemcpyAsync((void *)dt[k], tables[k], b, hipMemcpyHostToDevice, c->stream));
+                              }
+                              for (int m = 0; m < n_outputs; m++) dout[m] = (uint64_t *)((char *)d[1] + ob * m);
+                              if (int r = dev_lincomb(c, dout, n_outputs, dt, n_evals, n_tables, (const uint64_t *)d[2], uses, n, c->stream)) return r;
+                              for (int m = 0; m < n_outputs; m++) HIP_TRY(hipMemcpyAsync(outs[m], dout[m], n * w, hipMemcpyDeviceToHost, c->stream));
+                              return SR_OK;
+                          });
+    return rc;
 }
 int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches) {
     return round_plan_entry(kMleRound, ring, log2_degree, num_vars, n_tables, 0, 0, mode, work_elems, launches);

@@ -99,6 +99,51 @@ class DenseMultilinearExtension:
         return self
 
     @staticmethod
+    def linear_combination(mles, coeffs, const=None, out=None, stream=None):
+        """sum_k coeffs[k] * mles[k] (+ const) as one MLE from 1 .. 16 in one pass over their tables (sr_lincomb_dev): the composition
+        of `MulAssign<R>`, `AddAssign<(R, &Self)>` and `Add<R>` (dense.rs:370-374, 288-317, 386-395).  coeffs: one ring element (a
+        tensor) per MLE, or one tensor of len(mles) elements; const: one ring element or None.  The inputs may be truncated and need
+        not store the same number of evaluations.  The result stores the longest input's evaluations, or all 2^num_vars with a
+        constant: the constant goes to every evaluation, whereas the reference's Add<R> touches only the stored ones.  out: an MLE
+        that stores exactly that many (it may be one of the inputs: in place), default a new one."""
+        import torch
+
+        from .lincomb import lincomb_dev
+
+        if not 1 <= len(mles) <= 16:
+            raise RingError("linear_combination: 1 .. 16 MLEs")
+        ring, nv = mles[0].ring, mles[0].num_vars
+        if any(m.ring is not ring or m.num_vars != nv for m in mles):
+            raise RingError("linear_combination: the MLEs differ in ring or num_vars")
+        w, K = ring.words_per_elem, len(mles)
+        parts = [coeffs] if hasattr(coeffs, "numel") else list(coeffs)
+        if sum(c.numel() for c in parts) != K * w:
+            raise RingError("linear_combination: one coefficient (one ring element) per MLE")
+        if const is not None and const.numel() != w:
+            raise RingError("linear_combination: the constant is not one ring element")
+        first = mles[0].evaluations
+        coef = torch.cat([c.reshape(-1) for c in parts] + [const.reshape(-1) if const is not None else torch.zeros(w, dtype=first.dtype, device=first.device)])
+        n = 1 << nv if const is not None else max(len(m) for m in mles)
+        if out is None:
+            out = DenseMultilinearExtension(ring, nv, torch.empty(n * w, dtype=first.dtype, device=first.device))
+        elif out.ring is not ring or out.num_vars != nv or len(out) != n:
+            raise RingError("linear_combination: out must store %d evaluations of the same ring and num_vars" % n)
+        if stream is not None:
+            coef.record_stream(stream)
+            out.evaluations.record_stream(stream)
+        # a table that stores nothing is all zero: it takes no part (and has no buffer to point at)
+        live = [k for k in range(K) if len(mles[k])]
+        if not live:
+            live = [0]
+        rows = torch.cat([coef[k * w:(k + 1) * w] for k in live] + [coef[K * w:]]) if len(live) != K else coef
+        tables = [mles[k].evaluations if len(mles[k]) else out.evaluations for k in live]
+        n_evals = [len(mles[k]) for k in live]
+        mask = (1 << len(live)) - 1 | (1 << len(live) if const is not None else 0)
+        if n:
+            lincomb_dev(ring, [out.evaluations], tables, rows, [mask], n, n_evals, stream)
+        return out
+
+    @staticmethod
     def _round(tables, mode, stream):
         import torch
 
