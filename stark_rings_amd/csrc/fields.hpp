@@ -278,6 +278,25 @@ struct Goldilocks {
             : "scc");
         return t;
     }
+    // canonical (l2 + hl * eps - eps) for ANY l2, hl: 4 VALU.  What the shift products 2^E, 32 <= E < 64, fold with (mul_pow2:
+    // y0 2^32 + y1 eps - y2 as y1 eps + {y0 : ~y2}, the "- y2" being the "+ ~y2" of the low word less eps) -- no borrow chain.
+    // S = l2 + hl eps <= 2^65 - 2^33.  On the mad's carry-out the low 64 bits are S - 2^64 = S - eps (mod p), <= 2^64 - 2^33 < p:
+    // done.  The other lanes take + p (mod 2^64): S - eps, < p, unless S < eps, where the sum wraps to 2^64 + S - eps >= p and a
+    // second + p (the only lanes the compare against p ever selects) leaves S - eps + p.
+    SR_HD static elem mad_eps_less_eps(uint64_t l2, uint32_t hl) {
+        uint64_t t = l2, cy, sv;                   // the sum takes the addend's register pair
+        asm("v_mad_u64_u32 %0, %1, %3, -1, %0\n\t"
+            "s_andn1_saveexec_b64 %2, %1\n\t"      // lanes WITHOUT the carry-out
+            "v_lshl_add_u64 %0, %0, 0, %4\n\t"
+            "v_cmp_le_u64_e64 %1, %4, %0\n\t"      // inactive lanes read as 0
+            "s_mov_b64 exec, %1\n\t"
+            "v_lshl_add_u64 %0, %0, 0, %4\n\t"
+            "s_mov_b64 exec, %2"
+            : "+v"(t), "=&s"(cy), "=&s"(sv)
+            : "v"(hl), "s"((uint64_t)P)
+            : "scc");
+        return t;
+    }
     // the "+ p on the lanes that borrowed" of a subtraction and the fold behind it as ONE statement: canonical ((r + [bo] p) + hl eps)
     SR_HD static elem fix_fold(uint64_t r, uint64_t bo, uint32_t hl) {
         uint64_t t, cy, c2;
@@ -365,6 +384,15 @@ struct Goldilocks {
         const unsigned __int128 w = (unsigned __int128)l2 + (uint64_t)hl * EPS;
         uint64_t t = (uint64_t)w;
         if ((uint64_t)(w >> 64) != 0 || t >= P) t += EPS;   // on overflow t <= 2^64 - 2^33 and t + eps < p
+        return t;
+    }
+    SR_HD static elem mad_eps_less_eps(uint64_t l2, uint32_t hl) {
+        const unsigned __int128 w = (unsigned __int128)l2 + (uint64_t)hl * EPS;
+        uint64_t t = (uint64_t)w;
+        if ((uint64_t)(w >> 64) == 0) {
+            t += P;              // S - eps, or 2^64 + S - eps >= p where S < eps
+            if (t >= P) t += P;
+        }
         return t;
     }
     SR_HD static elem fix_fold(uint64_t r, uint64_t bo, uint32_t hl) { return mad_eps_fix(bo ? r + P : r, hl); }

@@ -59,7 +59,9 @@ constexpr int kLdsElems = kTile + kTile / 16;  // padded: pos + (pos >> 4)
 
 // x * 2^E mod p for a compile-time 0 < E < 96.  ANY 64-bit representative in (nothing below assumes x < p: the three branches
 // only need l2 + hl eps < 2^64 + p, which holds for every x -- tools/ubench/field_check.hip runs all 95 exponents on
-// non-canonical operands), canonical out: 5 / 7 / 7 VALU for E < 32 / < 64 / < 96.
+// non-canonical operands), canonical out: 5 / 8 / 7 VALU for E < 32 / < 64 / < 96 (three shifts, v_not_b32 and the four of
+// mad_eps_less_eps in the middle class; 7 at E = 48, where the v_not takes its half-word through SDWA.  E = 12, 48, 72 alone in a
+// kernel: profiles/r08/isa_shift_q1.txt; the middle class was 10 through reduce128, its borrow chain and its operand's zero word).
 template <int E>
 SR_HD u64 mul_pow2(u64 x) {
     static_assert(E > 0 && E < 96, "shift out of range");
@@ -69,8 +71,9 @@ SR_HD u64 mul_pow2(u64 x) {
     u64 res;
     if constexpr (q == 0) {
         res = G::mad_eps_fix(xs, y2);                       // xs + y2 * eps: nothing to subtract (reduce128 with a zero top word)
-    } else if constexpr (q == 1) {
-        res = G::reduce128(xs << 32, (xs >> 32) | ((u64)y2 << 32));
+    } else if constexpr (q == 1) {                          // (y0 + y1 2^32 + y2 2^64) * 2^32 = y0 2^32 + y1 eps - y2
+        const u64 l2 = (xs << 32) | (u32)~y2;               // {y0 : ~y2} = y0 2^32 + eps - y2: the mad's addend, one v_not_b32
+        res = G::mad_eps_less_eps(l2, (u32)(xs >> 32));
     } else {                                                // (y0 + y1 2^32 + y2 2^64) * 2^64 = y0 * eps - (y1 + y2 2^32)
         const u32 y0 = (u32)xs;
         const u64 B = ((u64)y0 << 32) - y0;                 // y0 * (2^32 - 1) < p
@@ -112,7 +115,8 @@ SR_HD void bf_dif(u64 &a, u64 &b) {
 // the CANONICAL v 2^E to ANY 64-bit representative u with six VALU instead of seven (Goldilocks::addsub_lazy) and leaves arbitrary
 // representatives; butterflies with twiddle 1 keep the canonical form and need canonical inputs -- in the DFT_16 networks below
 // their inputs always come out of twiddle-1 butterflies, all the way back to the network's inputs (tools/model_fast_goldilocks.py
-// asserts it; the SR_GL_CHECK_REPS build counts violations on the device).
+// asserts it; the SR_GL_CHECK_REPS build counts violations on the device).  The phased form (dit_phased) can run the twiddle-1
+// butterfly of slot 0 lazily as well (ANY0); this butterfly-by-butterfly form does not.
 template <int E, bool FUSED = true, bool LAZY = false>
 SR_HD void bf_dit(u64 &u, u64 &v) {
     if constexpr (LAZY && E % 96 != 0) {
@@ -223,17 +227,23 @@ SR_HD void dit_fix(u64 &s, u64 &d, u64 c1, u64 c2) {
     if constexpr (LZ) G::addsub_lazy_fix(s, d, c1, c2);
     else G::addsub_fix(s, d, c1, c2);
 }
-template <template <int> class BF, bool LAZY = false, int... Is>
+// ANY0 (with LAZY): the twiddle-1 butterfly that touches slot 0 takes the lazy form too -- any u, CANONICAL v, as a shifted one.  In
+// the DFT_16 networks below its v always comes out of a canonical butterfly (or is a network input, canonical by the networks'
+// contract), its sum stays in slot 0, the u of the next stage's slot-0 butterfly, and its difference is the u of a shifted lazy
+// butterfly or leaves the network: slot 0 then ACCEPTS any representative and LEAVES as one, and the network is four VALU shorter.
+template <template <int> class BF, bool LAZY, bool ANY0, int I>
+constexpr bool dit_lazy_bf() { return LAZY && (BF<I>::E % 96 != 0 || (ANY0 && BF<I>::lo == 0)); }
+template <template <int> class BF, bool LAZY = false, bool ANY0 = false, int... Is>
 SR_HD void dit_phased(u64 *x, std::integer_sequence<int, Is...>) {  // (u, v) -> (u + v 2^E, u - v 2^E)
     constexpr int n = 8;
     u64 t[n], c1[n], c2[n], sv[n], dv[n];
     u32 s0[n], s1[n], d0[n], d1[n];
     // v 2^E first (E >= 96: v 2^(E - 96), and the legs swap: u - t is the sum leg)
     ((x[BF<Is>::hi] = shift96<BF<Is>::E % 96>(x[BF<Is>::hi])), ...);
-    ((t[Is] = dit_pre_add<(LAZY && BF<Is>::E % 96 != 0)>(x[BF<Is>::lo], x[BF<Is>::hi])), ...);
+    ((t[Is] = dit_pre_add<dit_lazy_bf<BF, LAZY, ANY0, Is>()>(x[BF<Is>::lo], x[BF<Is>::hi])), ...);
     (G::addsub_chains<false>(t[Is], x[BF<Is>::lo], x[BF<Is>::hi], s0[Is], s1[Is], d0[Is], d1[Is], c1[Is], c2[Is]), ...);
     ((sv[Is] = (u64)s0[Is] | ((u64)s1[Is] << 32), dv[Is] = (u64)d0[Is] | ((u64)d1[Is] << 32)), ...);
-    (dit_fix<(LAZY && BF<Is>::E % 96 != 0)>(sv[Is], dv[Is], c1[Is], c2[Is]), ...);
+    (dit_fix<dit_lazy_bf<BF, LAZY, ANY0, Is>()>(sv[Is], dv[Is], c1[Is], c2[Is]), ...);
     ((x[BF<Is>::lo] = BF<Is>::E >= 96 ? dv[Is] : sv[Is], x[BF<Is>::hi] = BF<Is>::E >= 96 ? sv[Is] : dv[Is]), ...);
 }
 // the stages of the cyclic DFT_16 networks: butterfly I = block I / HALF, position I % HALF
@@ -252,12 +262,12 @@ struct StageOf {
 constexpr int kPhased = 8;
 template <int OFF, int... Is>
 constexpr std::integer_sequence<int, (OFF + Is)...> seq_from(std::integer_sequence<int, Is...>) { return {}; }
-template <template <int> class BF, bool DIT, int N, int P, bool LAZY = false>
+template <template <int> class BF, bool DIT, int N, int P, bool LAZY = false, bool ANY0 = false>
 SR_HD void stage_in_groups(u64 *x) {
     constexpr int G = P < N ? P : N;
     if constexpr (DIT) {
-        dit_phased<BF, LAZY>(x, std::make_integer_sequence<int, G>{});
-        if constexpr (G < N) dit_phased<BF, LAZY>(x, seq_from<G>(std::make_integer_sequence<int, N - G>{}));
+        dit_phased<BF, LAZY, ANY0>(x, std::make_integer_sequence<int, G>{});
+        if constexpr (G < N) dit_phased<BF, LAZY, ANY0>(x, seq_from<G>(std::make_integer_sequence<int, N - G>{}));
     } else {
         dif_phased<BF>(x, std::make_integer_sequence<int, G>{});
         if constexpr (G < N) dif_phased<BF>(x, seq_from<G>(std::make_integer_sequence<int, N - G>{}));
@@ -268,19 +278,21 @@ SR_HD void dif_stage(u64 *x, std::integer_sequence<int, Bs...>) {
     if constexpr (P <= 0) (dif_group<HALF, STEP, Bs * 2 * HALF, P == 0>(x, std::make_integer_sequence<int, HALF>{}), ...);
     else stage_in_groups<StageOf<HALF, STEP, false>::template Bf, false, HALF * (int)sizeof...(Bs), P>(x);
 }
-template <int HALF, int STEP, int P = kPhased, bool LAZY = false, int... Bs>
+template <int HALF, int STEP, int P = kPhased, bool LAZY = false, bool ANY0 = false, int... Bs>
 SR_HD void dit_stage(u64 *x, std::integer_sequence<int, Bs...>) {
+    static_assert(!ANY0 || P > 0, "the lazy slot-0 chain exists in the phased form only");
     if constexpr (P <= 0) (dit_group<HALF, STEP, Bs * 2 * HALF, P == 0, LAZY>(x, std::make_integer_sequence<int, HALF>{}), ...);
-    else stage_in_groups<StageOf<HALF, STEP, true>::template Bf, true, HALF * (int)sizeof...(Bs), P, LAZY>(x);
+    else stage_in_groups<StageOf<HALF, STEP, true>::template Bf, true, HALF * (int)sizeof...(Bs), P, LAZY, ANY0>(x);
 }
 template <int U, int P, bool LAZY, int... Is>
 SR_HD void dit_nat_bfs(u64 *x, std::integer_sequence<int, Is...>) {
     (bf_dit<StageNat<U>::template Bf<Is>::E, P == 0, LAZY>(x[StageNat<U>::template Bf<Is>::lo], x[StageNat<U>::template Bf<Is>::hi]), ...);
 }
-template <int U, int P = kPhased, bool LAZY = false>
+template <int U, int P = kPhased, bool LAZY = false, bool ANY0 = false>
 SR_HD void dit_nat_stage(u64 *x) {
+    static_assert(!ANY0 || P > 0, "the lazy slot-0 chain exists in the phased form only");
     if constexpr (P <= 0) dit_nat_bfs<U, P, LAZY>(x, std::make_integer_sequence<int, 8>{});
-    else stage_in_groups<StageNat<U>::template Bf, true, 8, P, LAZY>(x);
+    else stage_in_groups<StageNat<U>::template Bf, true, 8, P, LAZY, ANY0>(x);
 }
 // 16-point cyclic DFT with omega_16 = 2^156: natural order in, bit-reversed order out (unnormalised)
 template <int P = kPhased>
@@ -291,29 +303,35 @@ SR_HD void dft16_fwd(u64 *x) {
     dif_stage<1, (kW16Exp * 8) % 192, P>(x, std::make_integer_sequence<int, 8>{});
 }
 // inverse network: bit-reversed order in, natural order out, result = 16 * original.  LAZY: canonical in, arbitrary 64-bit
-// representatives out (slot 0, which only twiddle-1 butterflies touch, stays canonical)
-template <int P = kPhased, bool LAZY = false>
+// representatives out (slot 0, which only twiddle-1 butterflies touch, stays canonical).  LAZY and ANY0: slot 0 may come in and
+// leaves as any representative (dit_phased); slots 1 .. 15 canonical in as ever.
+template <int P = kPhased, bool LAZY = false, bool ANY0 = false>
 SR_HD void dft16_inv(u64 *x) {
-    dit_stage<1, (kW16Exp * 8) % 192, P, LAZY>(x, std::make_integer_sequence<int, 8>{});
-    dit_stage<2, (kW16Exp * 4) % 192, P, LAZY>(x, std::make_integer_sequence<int, 4>{});
-    dit_stage<4, (kW16Exp * 2) % 192, P, LAZY>(x, std::make_integer_sequence<int, 2>{});
-    dit_stage<8, kW16Exp, P, LAZY>(x, std::make_integer_sequence<int, 1>{});
+    dit_stage<1, (kW16Exp * 8) % 192, P, LAZY, ANY0>(x, std::make_integer_sequence<int, 8>{});
+    dit_stage<2, (kW16Exp * 4) % 192, P, LAZY, ANY0>(x, std::make_integer_sequence<int, 4>{});
+    dit_stage<4, (kW16Exp * 2) % 192, P, LAZY, ANY0>(x, std::make_integer_sequence<int, 2>{});
+    dit_stage<8, kW16Exp, P, LAZY, ANY0>(x, std::make_integer_sequence<int, 1>{});
 }
 // dft16_fwd as a decimation-in-time network (StageNat): same order in, same order out, same values (mod p)
-template <int P = kPhased, bool LAZY = false>
+template <int P = kPhased, bool LAZY = false, bool ANY0 = false>
 SR_HD void dft16_fwd_dit(u64 *x) {
-    dit_nat_stage<0, P, LAZY>(x);
-    dit_nat_stage<1, P, LAZY>(x);
-    dit_nat_stage<2, P, LAZY>(x);
-    dit_nat_stage<3, P, LAZY>(x);
+    dit_nat_stage<0, P, LAZY, ANY0>(x);
+    dit_nat_stage<1, P, LAZY, ANY0>(x);
+    dit_nat_stage<2, P, LAZY, ANY0>(x);
+    dit_nat_stage<3, P, LAZY, ANY0>(x);
 }
-// what the D = 2^16 .. 2^20 kernels call: CANON = the results leave the library as they are (plain forward transform)
-template <bool CANON = false, int P = kPhased>
+// what the D = 2^16 .. 2^20 kernels call: CANON = the results leave the library as they are (plain forward transform).
+// ANY0 is a property of the CALL SITE: slot 0 of the result goes into a general product (or a scratch that one multiplies next), so
+// any representative will do there -- and then slot 0 of the operand may be any representative as well.  It stays false where the
+// unmultiplied slot 0 goes on to canonical consumers: the CANON networks, the inverse column pass (Gentleman-Sande stages behind
+// it) and the first network of tile256_fwd_regs (its slot 0 crosses the exchange into arbitrary slots of other lanes).
+template <bool CANON = false, int P = kPhased, bool ANY0 = false>
 SR_HD void dft16_fwd_hot(u64 *x) {
-    dft16_fwd_dit<P, !CANON>(x);
+    static_assert(!(CANON && ANY0), "a canonical network keeps slot 0 canonical");
+    dft16_fwd_dit<P, !CANON, ANY0>(x);
 }
-template <int P = kPhased>
-SR_HD void dft16_inv_hot(u64 *x) { dft16_inv<P, true>(x); }
+template <int P = kPhased, bool ANY0 = false>
+SR_HD void dft16_inv_hot(u64 *x) { dft16_inv<P, true, ANY0>(x); }
 
 // Q leading stages skipped: 2^Q independent cyclic DFTs of size 16 >> Q on consecutive register groups (used when
 // D < 4096 and a tile holds 2^Q ring elements: the stride-256 pass must not mix them); same twiddles as the tail
@@ -620,16 +638,18 @@ __device__ __forceinline__ void cols256_tile(const unsigned tile, u64 *data, con
         cols_stage_fwd<2>(x);
         cols_stage_fwd<3>(x);
 #pragma unroll
-        for (int h = 0; h < 16; h++) x[h] = G::mul(x[h], wc[h * 16 + rg]);
-#pragma unroll
-        for (int h = 0; h < 16; h++) lds[CT::idx(16 * h + rg, col)] = x[h];  // leg 16 h + rg, column col
+        for (int h = 0; h < 16; h++) lds[CT::idx(16 * h + rg, col)] = x[h];  // leg 16 h + rg, column col (lazy representatives)
         __syncthreads();
         u64 tw[16];
 #pragma unroll
         for (int sg = 0; sg < 16; sg++) tw[sg] = *reinterpret_cast<const u64 *>(tb + (offB + (unsigned)sg * leg));
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = lds[CT::idx(16 * rg + j, col)];  // block rg, leg j
-        dft16_fwd_hot(x);
+        // the W layer on THIS side of the exchange: block rg, leg j takes wc[rg * 16 + j], which is 1 for leg 0 -- 15 products, and
+        // slot 0 of the network behind them takes the lazy representative as it is
+#pragma unroll
+        for (int j = 1; j < 16; j++) x[j] = G::mul(x[j], wc[rg * 16 + j]);
+        dft16_fwd_hot<false, kPhased, true>(x);
 #pragma unroll
         for (int sg = 0; sg < 16; sg++)
             st_scratch(reinterpret_cast<u64 *>(pb + (offB + (unsigned)sg * leg)), G::mul(x[sg], tw[sg]));
@@ -642,14 +662,14 @@ __device__ __forceinline__ void cols256_tile(const unsigned tile, u64 *data, con
         }
 #pragma unroll
         for (int sg = 0; sg < 16; sg++) x[sg] = G::mul(x[sg], tw[sg]);
-        dft16_inv_hot(x);
+        dft16_inv_hot(x);  // slot 0 stays canonical: it takes no product and the stages behind the exchange are canonical
+#pragma unroll
+        for (int j = 1; j < 16; j++) x[j] = G::mul(x[j], wc[rg * 16 + j]);  // the W layer, block rg, leg j (leg 0: factor 1)
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[CT::idx(16 * rg + j, col)] = x[j];
         __syncthreads();
 #pragma unroll
         for (int h = 0; h < 16; h++) x[h] = lds[CT::idx(16 * h + rg, col)];
-#pragma unroll
-        for (int h = 0; h < 16; h++) x[h] = G::mul(x[h], wc[h * 16 + rg]);
         cols_stage_inv<3>(x);
         cols_stage_inv<2>(x);
         cols_stage_inv<1>(x);
@@ -777,22 +797,20 @@ __global__ __launch_bounds__(256, 3) void cols256_keep_kernel(u64 *data, const u
             cols_stage_fwd<1>(x);
             cols_stage_fwd<2>(x);
             cols_stage_fwd<3>(x);
-            if (first) {
-                wl[t] = wv;
-                __syncthreads();
-            }
+            if (first) wl[t] = wv;   // read behind the "tile full" barrier below
+            else __syncthreads();    // every lane has read the previous ring element's exchange before these writes land
 #pragma unroll
-            for (int h = 0; h < 16; h++) {
-                x[h] = G::mul(x[h], wl[h * 16 + rg]);
-                if ((h & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // keeps the 16 table reads from all being hoisted in front
-            }
-            if (!first) __syncthreads();  // every lane has read the previous ring element's exchange before these writes land
-#pragma unroll
-            for (int h = 0; h < 16; h++) lh[272 * h] = x[h];
+            for (int h = 0; h < 16; h++) lh[272 * h] = x[h];  // lazy representatives
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < 16; j++) x[j] = lj[17 * j];
-            dft16_fwd_hot(x);
+            // the W layer behind the exchange (cols256_tile): block rg, leg j; leg 0 takes no product
+#pragma unroll
+            for (int j = 1; j < 16; j++) {
+                x[j] = G::mul(x[j], wl[rg * 16 + j]);
+                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // keeps the 15 table reads from all being hoisted in front
+            }
+            dft16_fwd_hot<false, kPhased, true>(x);
 #pragma unroll
             for (int sg = 0; sg < 16; sg++) *keep_ptr_b(pb, offB, sg) = G::mul(x[sg], tw[sg]);  // as st_scratch
         } else {
@@ -808,19 +826,22 @@ __global__ __launch_bounds__(256, 3) void cols256_keep_kernel(u64 *data, const u
                 x[sg] = G::mul(x[sg], tw[sg]);
                 if ((sg & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             }
-            dft16_inv_hot(x);
-            if (first) wl[t] = wv;   // read behind the "tile full" barrier below
-            else __syncthreads();    // every lane has read the previous ring element's exchange before these writes land
+            dft16_inv_hot(x);  // slot 0 canonical: no product in front of the canonical stages behind the exchange
+            if (first) {
+                wl[t] = wv;
+                __syncthreads();
+            }
+#pragma unroll
+            for (int j = 1; j < 16; j++) {  // the W layer in front of the exchange: block rg, leg j
+                x[j] = G::mul(x[j], wl[rg * 16 + j]);
+                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+            if (!first) __syncthreads();  // every lane has read the previous ring element's exchange before these writes land
 #pragma unroll
             for (int j = 0; j < 16; j++) lj[17 * j] = x[j];
             __syncthreads();
 #pragma unroll
             for (int h = 0; h < 16; h++) x[h] = lh[272 * h];
-#pragma unroll
-            for (int h = 0; h < 16; h++) {
-                x[h] = G::mul(x[h], wl[h * 16 + rg]);
-                if ((h & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-            }
             cols_stage_inv<3>(x);
             cols_stage_inv<2>(x);
             cols_stage_inv<1>(x);
@@ -896,7 +917,10 @@ __device__ __forceinline__ void tile_inv(u64 *x, u64 *lds, const int t, const Ta
     for (int s = 0; s < 16; s++) x[s] = lds[pad(base2 + s * 16)];
 #pragma unroll
     for (int s = 1; s < 16; s++) x[s] = G::mul(x[s], T.w2i[s * 16 + i0]);
-    if (LZ) x[0] = G::canon(x[0]);  // see tile256_inv
+    // x[0] skips the table product (its factor is 1) but is an arbitrary slot of ANOTHER lane's lazy network.  The 4096-point networks
+    // keep the canonical slot-0 chain (no ANY0: its twiddle-1 butterflies want canonical inputs), so the skipped value is made
+    // canonical here and in front of the third network below.  tile256_inv takes ANY0 instead and needs no canon.
+    if (LZ) x[0] = G::canon(x[0]);
     dft16_inv<P, LZ>(x);
 #pragma unroll
     for (int j = 0; j < 16; j++) lds[pad(base2 + j * 16)] = x[j];
@@ -1054,10 +1078,13 @@ __device__ __forceinline__ void wave256_exchange(unsigned *wr, const unsigned *r
 template <bool CANON = false>
 __device__ __forceinline__ void tile256_fwd_regs(const Wave256 &W, const int t, const Tables &T, u64 *x) {
     const int i0 = t & 15;
-    dft16_fwd_hot(x);
+    dft16_fwd_hot(x);  // slot 0 skips w2f and crosses the exchange into arbitrary slots of the lanes i0 = 0: canonical out
 #pragma unroll
     for (int s = 1; s < 16; s++) x[s] = G::mul(x[s], T.w2f[s * 16 + i0]);
     wave256_exchange<17, 1>(W.strided, W.own, x);
+    // Without CANON the slots go into the slot product and ANY0 would be legal here, four VALU less per transform -- but the fused
+    // product then needs 96 VGPRs and 8 bytes of scratch where it has 92 and none (five workgroups per CU: 96 is the ceiling), so
+    // this network keeps the canonical slot-0 chain (the variant's listing line: profiles/r08/isa_shift_w_slot0.txt).
     dft16_fwd_hot<CANON>(x);
 }
 template <bool CANON = false>
@@ -1067,14 +1094,13 @@ __device__ __forceinline__ void tile256_fwd(const u64 *__restrict__ src, const W
 }
 __device__ __forceinline__ void tile256_inv(u64 *x, const Wave256 &W, const int t, const Tables &T, u64 *__restrict__ dst) {
     const int i0 = t & 15, base2 = (t >> 4) * 256 + i0;
-    dft16_inv_hot(x);
+    dft16_inv_hot<kPhased, true>(x);
     wave256_exchange<1, 17>(W.own, W.strided, x);
 #pragma unroll
     for (int s = 1; s < 16; s++) x[s] = G::mul(x[s], T.w2i[s * 16 + i0]);
-    // x[0] skips the table product (its factor is 1) but is slot i0 of ANOTHER lane's network, a lazy representative: the twiddle-1
-    // butterflies of the next network want it canonical
-    x[0] = G::canon(x[0]);
-    dft16_inv_hot(x);
+    // x[0] skips the table product (its factor is 1) and is slot i0 of ANOTHER lane's network, a lazy representative: the next
+    // network takes any representative in slot 0 (only there), and what it leaves is multiplied first by the inverse column pass
+    dft16_inv_hot<kPhased, true>(x);
 #pragma unroll
     for (int j = 0; j < 16; j++) st_scratch(dst + base2 + j * 16, x[j]);
 }

@@ -70,10 +70,56 @@ M64 = 1 << 64
 EPS = (1 << 32) - 1
 
 
+def mul_pow2(x, e):
+    """gl::mul_pow2<e> word for word: x 2^e for ANY u64 x, 0 < e < 96, canonical out.  (y0, y1, y2) = the three 32-bit words of
+    x 2^(e % 32).  The class 32 <= e < 64 (Goldilocks::mad_eps_less_eps) is y0 2^32 + y1 eps - y2 as S = y1 eps + {y0 : ~y2}, which
+    is the target + eps: on the carry-out of S the low 64 bits are the answer; the other lanes take + p modulo 2^64, and once more
+    where that wrapped (S < eps, which needs y0 = y1 = 0: x = m 2^(64 - r)).  Asserts that nothing wraps a further time."""
+    assert 0 <= x < M64 and 0 < e < 96
+    q, r = divmod(e, 32)
+    xs = (x << r) % M64
+    y0, y1, y2 = xs & EPS, xs >> 32, x >> (64 - r) if r else 0
+    if q == 0:                                        # mad_eps_fix: xs + y2 eps, + eps on carry or >= p
+        w = xs + y2 * EPS
+        t = w % M64
+        if w >= M64 or t >= p:
+            t = (t + EPS) % M64                       # w >= 2^64: t <= 2^64 - 2^33 before; t >= p: + eps = - p modulo 2^64
+    elif q == 1:
+        S = y1 * EPS + ((y0 << 32) | (EPS - y2))      # {y0 : ~y2}
+        assert S <= 2 * M64 - (1 << 33)
+        if S >= M64:
+            t = S - M64
+            assert t < p, "carry lanes are canonical as they are"
+        else:
+            t = (S + p) % M64
+            if S < EPS:
+                assert y0 == 0 and y1 == 0 and t >= p, "the wrapped lanes are exactly those the compare selects"
+                t = (t + p) % M64
+            else:
+                assert t == S - EPS and t < p, "no compare hit outside the wrapped lanes"
+    else:                                             # y0 eps - (y1 + y2 2^32), canonical sub
+        B, C = (y0 << 32) - y0, y1 | (y2 << 32)
+        assert B < p and C < p
+        t = (B - C) % p
+    assert t == x * pow(2, e, p) % p and t < p
+    return t
+
+
 def lazy_bf(a, v, e):
     """(a, v) -> (a + v 2^e, a - v 2^e) on u64 representatives; e in [0, 192), e % 96 != 0"""
     assert 0 <= a < M64 and 0 <= v < M64 and e % 96 != 0
-    t = v * pow(2, e % 96, p) % p                     # mul_pow2: any u64 in, canonical out
+    t = mul_pow2(v, e % 96)                           # any u64 in, canonical out
+    return _lazy_legs(a, t, e)
+
+
+def lazy_bf_one(a, v):
+    """the twiddle-1 butterfly of the slot-0 chain in the lazy form (dit_phased, ANY0): any u64 a, CANONICAL v"""
+    assert 0 <= a < M64
+    assert v < p, "lazy twiddle-1 butterfly on a non-canonical v"
+    return _lazy_legs(a, v, 0)
+
+
+def _lazy_legs(a, t, e):
     s = a + t
     if s >= M64:
         s = s - M64 + EPS
@@ -94,9 +140,10 @@ def brv_bits(x, bits):
     return brv(x, bits) if bits else 0
 
 
-def dft16_fwd_dit(x, lazy=False):
+def dft16_fwd_dit(x, lazy=False, any0=False):
     """DIT, natural in, bit-reversed out: the same function as dft16_fwd.  Stage u pairs (lo, lo + (8 >> u)); every butterfly of
-    block blk = lo // (16 >> u) carries omega_16^((8 >> u) brv_u(blk))."""
+    block blk = lo // (16 >> u) carries omega_16^((8 >> u) brv_u(blk)).  any0 (with lazy): the butterfly that touches slot 0 is lazy
+    in every stage -- slot 0 may come in and leaves as any representative."""
     x = list(x)
     for u in range(4):
         half = 8 >> u
@@ -107,6 +154,9 @@ def dft16_fwd_dit(x, lazy=False):
             e = (W16_EXP * half * brv_bits(blk, u)) % 192
             if lazy and e % 96:
                 x[lo], x[hi] = lazy_bf(x[lo], x[hi], e)
+            elif lazy and any0 and lo == 0:
+                assert e == 0
+                x[lo], x[hi] = lazy_bf_one(x[lo], x[hi])
             elif lazy:
                 assert e == 0
                 x[lo], x[hi] = canon_bf(x[lo], x[hi])
@@ -116,8 +166,8 @@ def dft16_fwd_dit(x, lazy=False):
     return x
 
 
-def dft16_inv_lazy(x):
-    """dft16_inv on representatives: bit-reversed in, natural out"""
+def dft16_inv_lazy(x, any0=False):
+    """dft16_inv on representatives: bit-reversed in, natural out; any0 as in dft16_fwd_dit"""
     x = list(x)
     half = 1
     steps = {1: (W16_EXP * 8) % 192, 2: (W16_EXP * 4) % 192, 4: (W16_EXP * 2) % 192, 8: W16_EXP}
@@ -128,6 +178,8 @@ def dft16_inv_lazy(x):
                 lo, hi = base + j, base + j + half
                 if e % 96:
                     x[lo], x[hi] = lazy_bf(x[lo], x[hi], e)
+                elif any0 and lo == 0:
+                    x[lo], x[hi] = lazy_bf_one(x[lo], x[hi])
                 else:
                     assert e == 0
                     x[lo], x[hi] = canon_bf(x[lo], x[hi])
@@ -600,15 +652,16 @@ def rows256_fwd_lazy(row, T, last_canonical=False):
     return y
 
 
-def rows256_inv_lazy(row, T, canon=True):
+def rows256_inv_lazy(row, T, canon=True, any0=False):
+    """any0: what tile256_inv runs -- both networks with the lazy slot-0 chain, no G::canon (canon is then ignored)"""
     y = list(row)
     for t in range(16):
-        y[16 * t:16 * t + 16] = dft16_inv_lazy(y[16 * t:16 * t + 16])
+        y[16 * t:16 * t + 16] = dft16_inv_lazy(y[16 * t:16 * t + 16], any0)
     for i0 in range(16):
         xs = [y[i0]] + [y[s_ * 16 + i0] * T["W2i"][s_][i0] % p for s_ in range(1, 16)]
-        if canon:
+        if canon and not any0:
             xs[0] %= p                                                  # G::canon
-        x = dft16_inv_lazy(xs)
+        x = dft16_inv_lazy(xs, any0)
         for j in range(16):
             y[j * 16 + i0] = x[j]
     return y
@@ -727,6 +780,123 @@ def check_lazy_tiles(seed=21):
     return True
 
 
+# ------------------------------------------------------------------------------------------------
+# The column pass on representatives, as cols256_tile / cols256_keep_kernel run it: the W layer on the REGISTER side of the exchange
+# (block h, leg j takes Wc[h][j]; leg 0, whose factor is 1, takes no product).  Forward: the lazy pass-A words cross the exchange
+# as they are and the unmultiplied leg 0 enters slot 0 of a network with the lazy slot-0 chain (any0), whose results all go into the
+# block-twist product.  Inverse: the network keeps slot 0 canonical (any0 = False) because it reaches the canonical Gentleman-Sande
+# stages without a product in between (canon_bf asserts it).
+# ------------------------------------------------------------------------------------------------
+def cols256_column_fwd_lazy(col, T, i2):
+    """one column (256 legs, canonical or not on the `a` legs) -> its 256 words of the forward column pass"""
+    lds = [None] * 256
+    for rg in range(16):
+        x = cols_passA_fwd_lazy([col[rg + 16 * jj] for jj in range(16)], T["tw_exp"])
+        for h in range(16):
+            lds[16 * h + rg] = x[h]                                       # lazy representatives through the exchange
+    out = [None] * 256
+    for h in range(16):
+        x = [lds[16 * h]] + [lds[16 * h + j] * T["Wcf"][h][j] % p for j in range(1, 16)]
+        x = dft16_fwd_dit(x, lazy=True, any0=True)
+        for sg in range(16):
+            out[16 * h + sg] = x[sg] * T["twist_f"][16 * h + sg][i2] % p
+    return out
+
+
+def cols256_column_inv_lazy(col, T, i2):
+    lds = [None] * 256
+    for h in range(16):
+        x = dft16_inv_lazy([col[16 * h + sg] * T["twist_i"][16 * h + sg][i2] % p for sg in range(16)])
+        assert x[0] < p
+        for j in range(16):
+            lds[16 * h + j] = x[j] * T["Wci"][h][j] % p if j else x[0]
+    out = [None] * 256
+    for rg in range(16):
+        x = [lds[rg + 16 * h] for h in range(16)]
+        for u in range(3, -1, -1):
+            half = 8 >> u
+            for jj in range(16):
+                if jj & half:
+                    continue
+                e = (192 - T["tw_exp"][(1 << u) + (jj >> (4 - u))]) % 192
+                s_, d = canon_bf(x[jj], x[jj + half])
+                if e >= 96:                                               # 2^96 = -1: the difference the other way round
+                    d = (p - d) % p
+                x[jj], x[jj + half] = s_, mul_pow2(d, e % 96) if e % 96 else d
+        for jj in range(16):
+            out[rg + 16 * jj] = x[jj]
+    return out
+
+
+def check_shift_q1(seed=31, rounds=2000):
+    """mul_pow2 (which asserts its own no-further-wrap conditions) on the edge words of the 2^32 .. 2^63 class and on random words"""
+    rng = random.Random(seed)
+    repairs = 0
+    for e in range(33, 64):
+        r = e - 32
+        words = [0, 1, p - 1, p, p + 1, M64 - 1]
+        for m in (1, 2, (1 << r) - 1):
+            words += [((m << (64 - r)) + d) % M64 for d in (-1, 0, 1)]
+        words += [rng.randrange(M64) for _ in range(rounds)]
+        for x in words:
+            mul_pow2(x, e)
+            repairs += (x << r) % M64 == 0 and x != 0
+    assert repairs >= 31 * 2
+    for e in range(1, 96):
+        for x in [0, 1, p - 1, p, p + 1, M64 - 1, 1 << 63, EPS, EPS + 1] + [rng.randrange(M64) for _ in range(50)]:
+            mul_pow2(x, e)
+    return True
+
+
+def check_slot0_chain_and_w_layer(seed=33, rounds=120):
+    rng = random.Random(seed)
+    T = cols_tables(16)
+    edge = [0, 1, p - 1, p - 2, EPS, EPS + 1, (1 << 63), p - EPS, (1 << 32), p >> 1]
+    raw0 = [0, p, p + 1, M64 - 1, M64 - EPS, p - 1, EPS]                 # representatives slot 0 may come in as
+    for r in range(rounds):
+        x = [rng.choice(edge) for _ in range(16)] if r < 40 else [rng.randrange(p) for _ in range(16)]
+        x0 = rng.choice(raw0) if r % 2 else rng.randrange(M64)
+        xs = [x0] + x[1:]
+        want = dft16_fwd([x0 % p] + x[1:])
+        assert [v % p for v in dft16_fwd_dit(xs, lazy=True, any0=True)] == want
+        want_i = dft16_inv([x0 % p] + x[1:])
+        assert [v % p for v in dft16_inv_lazy(xs, any0=True)] == want_i
+    # a non-canonical word anywhere else must trip an assertion: slots 1 .. 15 stay canonical-in
+    for slot in (1, 4, 8, 15):
+        xs = [rng.randrange(p) for _ in range(16)]
+        xs[slot] = p + 1
+        for net in (lambda v: dft16_fwd_dit(v, lazy=True, any0=True), lambda v: dft16_inv_lazy(v, any0=True)):
+            try:
+                net(xs)
+                raise SystemExit("a non-canonical word in slot %d went through" % slot)
+            except AssertionError:
+                pass
+    # rows256 inverse as the kernel runs it: no canon, crafted blocks included (the representative p in the skipped value)
+    for slot in range(1, 16):
+        row = [rng.randrange(p) for _ in range(256)]
+        row[0:16] = crafted_inverse_block(rng, slot)
+        assert [v % p for v in rows256_inv_lazy(row, T, any0=True)] == rows256_inv(row, T)
+    # column pass, one column at a time, against the canonical model
+    for trial in range(3):
+        if trial == 0:
+            a = [p - 1] * 256
+        elif trial == 1:
+            a = [rng.choice(edge) for _ in range(256)]
+        else:
+            a = [rng.randrange(p) for _ in range(256)]
+        i2 = (5, 0, 255)[trial]
+        T1 = dict(T)
+        T1["N2"] = 1
+        T1["twist_f"] = [[row[i2]] for row in T["twist_f"]]
+        T1["twist_i"] = [[row[i2]] for row in T["twist_i"]]
+        want = cols256_fwd(a, T1)
+        got = cols256_column_fwd_lazy(a, T, i2)
+        assert got == want, "column pass forward on representatives"
+        back = cols256_column_inv_lazy(got, T, i2)
+        assert back == cols256_inv(got, T1), "column pass inverse on representatives"
+    return True
+
+
 def check_cols256(k=16, seed=5):
     rng = random.Random(seed)
     T = cols_tables(k)
@@ -789,4 +959,8 @@ if __name__ == "__main__":
     print("lazy DIT networks ok")
     check_lazy_tiles()
     print("lazy tiles ok")
+    check_shift_q1()
+    print("shift products 2^32 .. 2^63 ok")
+    check_slot0_chain_and_w_layer()
+    print("lazy slot-0 chain and register-side W layer ok")
     print("model OK")

@@ -1,5 +1,6 @@
 // Device-vs-host check of fields.hpp (same source compiled twice): catches device-only codegen problems.
 #include <cstdio>
+#include <string>
 #include <vector>
 #include "../../stark_rings_amd/csrc/fields.hpp"
 #include "../../stark_rings_amd/csrc/ntt_goldilocks.hpp"
@@ -75,9 +76,83 @@ template <int... Es>
 static void host_pow2(uint64_t x, uint64_t *o, std::integer_sequence<int, Es...>) {
     ((o[Es] = sr::gl::mul_pow2<Es + 1>(x)), ...);
 }
+// the shift products 2^E, 32 < E < 64 (Goldilocks::mad_eps_less_eps), with an exponent per word: word i takes 2^e[i]
+template <int... Es>
+__global__ void kpow2_mid(const uint64_t *a, const uint64_t *e, uint64_t *o, int n, std::integer_sequence<int, Es...>) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t x = a[i];
+    const int ee = (int)e[i];
+    uint64_t r = ~0ull;
+    ((ee == Es + 33 ? (r = sr::gl::mul_pow2<Es + 33>(x), 0) : 0), ...);
+    o[i] = r;
+}
+template <int... Es>
+static uint64_t host_pow2_mid(uint64_t x, int ee, std::integer_sequence<int, Es...>) {
+    uint64_t r = ~0ull;
+    ((ee == Es + 33 ? (r = sr::gl::mul_pow2<Es + 33>(x), 0) : 0), ...);
+    return r;
+}
 static uint64_t mulmod(uint64_t x, uint64_t y) { return (uint64_t)(((unsigned __int128)(x % G::P) * (y % G::P)) % G::P); }
 static uint64_t mix(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31); }
-int main() {
+// The words on which the second + p of Goldilocks::mad_eps_less_eps is taken: x 2^r (r = E - 32) has no bits in its two low words,
+// x = m 2^(64 - r).  With their neighbours m 2^(64 - r) +- 1, for m = 1, 2, 2^r - 1 and every E in 33 .. 63.
+static std::vector<uint64_t> repair_words() {
+    std::vector<uint64_t> w;
+    for (int e = 33; e < 64; e++) {
+        const int r = e - 32;
+        const uint64_t ms[3] = {1, 2, (1ull << r) - 1};
+        for (uint64_t m : ms)
+            for (int d = -1; d <= 1; d++) w.push_back((m << (64 - r)) + (uint64_t)(int64_t)d);   // m 2^(64-r) wraps to 0 for r = 1, m = 2
+    }
+    return w;
+}
+// field_check --mid in out: `in` holds pairs of 64-bit words (x, E), 33 <= E <= 63; the device form of mul_pow2<E>(x) for every pair
+// goes to `out` (one word per pair) and is compared with the host form here.  tests/test_shift_q1_gpu.py
+static int run_mid(const char *in, const char *out) {
+    FILE *f = fopen(in, "rb");
+    if (!f) return 2;
+    std::vector<uint64_t> buf;
+    uint64_t pair[2];
+    bool ok = true;
+    while (ok && fread(pair, 8, 2, f) == 2) {
+        ok = pair[1] >= 33 && pair[1] <= 63;
+        buf.push_back(pair[0]);
+        buf.push_back(pair[1]);
+    }
+    fclose(f);
+    if (!ok || buf.empty()) return 2;
+    const int n = (int)(buf.size() / 2);
+    std::vector<uint64_t> x(n), e(n), o(n);
+    for (int i = 0; i < n; i++) x[i] = buf[2 * i], e[i] = buf[2 * i + 1];
+    uint64_t *dx = nullptr, *de = nullptr, *dout = nullptr;
+    bool dev = hipMalloc(&dx, n * 8) == hipSuccess && hipMalloc(&de, n * 8) == hipSuccess && hipMalloc(&dout, n * 8) == hipSuccess;
+    if (dev) {
+        hipMemcpy(dx, x.data(), n * 8, hipMemcpyHostToDevice);
+        hipMemcpy(de, e.data(), n * 8, hipMemcpyHostToDevice);
+        hipLaunchKernelGGL(kpow2_mid, dim3((n + 255) / 256), dim3(256), 0, 0, dx, de, dout, n, std::make_integer_sequence<int, 31>{});
+        dev = hipMemcpy(o.data(), dout, n * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    hipFree(dx);
+    hipFree(de);
+    hipFree(dout);
+    if (!dev) return 2;
+    int bad = 0;
+    for (int i = 0; i < n; i++) {
+        const uint64_t h = host_pow2_mid(x[i], (int)e[i], std::make_integer_sequence<int, 31>{});
+        if (o[i] != h && bad++ < 12)
+            printf("MISMATCH mul_pow2<%d> x=%016llx dev=%016llx host=%016llx\n", (int)e[i], (unsigned long long)x[i], (unsigned long long)o[i], (unsigned long long)h);
+    }
+    f = fopen(out, "wb");
+    if (!f) return 2;
+    const bool written = fwrite(o.data(), 8, n, f) == (size_t)n;
+    fclose(f);
+    if (!written) return 2;
+    printf("field_check --mid: %d words, %d mismatches\n", n, bad);
+    return bad != 0;
+}
+int main(int argc, char **argv) {
+    if (argc == 4 && std::string(argv[1]) == "--mid") return run_mid(argv[2], argv[3]);
     const int n = 1 << 16;
     std::vector<uint64_t> a(n), b(n), o(n * 6);
     const uint64_t sp[] = {0, 1, 2, G::P - 1, G::P - 2, 0xFFFFFFFFull, 0x100000000ull, 0xFFFFFFFF00000000ull, 1ull << 40, 1ull << 63, 0xFFFFFFFEFFFFFFFFull};
@@ -158,8 +233,9 @@ int main() {
                                0xFFFFFFFFull, 0x100000000ull, 1ull << 63, (1ull << 63) - 1, 0x8000000080000000ull, 0xFFFFFFFF80000000ull};
         const int nr = 16, m = 1 << 14;
         std::vector<uint64_t> ra(m), rb(m), ro(4 * (size_t)m), po(95 * (size_t)m);
+        const std::vector<uint64_t> rw = repair_words();   // behind the edge pairs: the words that take the second + p of the 2^32..2^63 class
         for (int i = 0; i < m; i++) {
-            ra[i] = i < nr * nr ? rv[i / nr] : mix(i + 0xABC);   // any u64
+            ra[i] = i < nr * nr ? rv[i / nr] : i < nr * nr + (int)rw.size() ? rw[i - nr * nr] : mix(i + 0xABC);   // any u64
             rb[i] = i < nr * nr ? rv[i % nr] : mix(i + 0xDEF);
         }
         uint64_t *dp;
@@ -194,7 +270,7 @@ int main() {
                            (unsigned long long)po[95 * (size_t)i + e - 1], (unsigned long long)hp[e - 1], (unsigned long long)w);
             }
         }
-        printf("non-canonical operands: %d x (mul, mad_eps_fix, fix_fold, reduce128, 95 shift products) checked\n", m);
+        printf("non-canonical operands: %d x (mul, mad_eps_fix, fix_fold, reduce128, 95 shift products) checked, %d of them m 2^(64-r) and neighbours\n", m, (int)rw.size());
     }
     printf("field_check: %d mismatches\n", bad);
     return bad != 0;
