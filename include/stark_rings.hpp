@@ -40,6 +40,9 @@
 //                                                                      round_evals_weighted / fold_round_evals_weighted (sr_vpoly_wround_*:
 //                                                                      a per-pair weight, the eq factor without a table); class EqSumCheck:
 //                                                                      a whole sum-check of eq(z, .) g, message / next / final
+//   the range (norm) check of a lattice  (LatticeFold's norm check)     class RangePolynomial: sum_i mu_i prod_{|j| < B} (f_i - j) over 1 .. 8
+//     folding scheme                                                   MLEs, each read once (sr_range_wround_evals); RangeSumCheck: the
+//                                                                      whole check; CyclotomicConfig::range_wround_plan / _evals_dev / _evals
 //   SparseMultilinearExtension<RqNTT>    crates/poly mle/sparse.rs   class SparseMultilinearExtension: from_slice, from_matrix, fix_variables,
 //     precompute_eq                      sparse.rs:381-394             fixed_variables, evaluate, to_evaluations; eq_table(point); device
 //                                                                      pointers: CyclotomicConfig::eq_table_dev / smle_plan / smle_fix_variables_dev
@@ -242,6 +245,25 @@ public:
         check(sr_vpoly_wround_fold_evals_dev(raw(), d_out, d_out_tables, n_evals_out, d_weights, d_tables, n_evals, n_tables, terms, n_terms,
                                              d_coeffs, num_vars, d_r, order, d_work, work_elems, stream),
               "vpoly_wround_fold_evals_dev");
+    }
+    // range-check (norm-check) rounds (include/stark_rings_hip.h: sr_range_wround_plan, sr_range_wround_evals_dev, sr_range_wround_evals):
+    // {work_elems, launches} of the plan, the device call and the host-pointer form (2 bound elements into `out`)
+    std::pair<size_t, int> range_wround_plan(int log2_degree, size_t num_vars, int n_tables, int bound, int order) const {
+        size_t work = 0;
+        int launches = 0;
+        check(sr_range_wround_plan((int)ring_, log2_degree, num_vars, n_tables, bound, order, &work, &launches), "range_wround_plan");
+        return {work, launches};
+    }
+    void range_wround_evals_dev(uint64_t *d_out, const uint64_t *d_weights, const uint64_t *const *d_tables, const size_t *n_evals, int n_tables,
+                                int bound, const uint64_t *d_coeffs, size_t num_vars, int order, uint64_t *d_work, size_t work_elems,
+                                void *stream) const {
+        check(sr_range_wround_evals_dev(raw(), d_out, d_weights, d_tables, n_evals, n_tables, bound, d_coeffs, num_vars, order, d_work, work_elems,
+                                        stream),
+              "range_wround_evals_dev");
+    }
+    void range_wround_evals(uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables, int bound,
+                            const uint64_t *coeffs, size_t num_vars, int order) const {
+        check(sr_range_wround_evals(raw(), out, weights, tables, n_evals, n_tables, bound, coeffs, num_vars, order), "range_wround_evals");
     }
     std::pair<size_t, int> smle_plan(int log2_degree, size_t nnz, size_t n_out, size_t n_fixed) const {
         size_t work = 0;
@@ -1022,6 +1044,73 @@ private:
     std::shared_ptr<std::vector<DenseMultilinearExtension>> owned_;  // the tables of a polynomial that fold_round_evals / fixed_variables made
 };
 
+// The range-check (norm-check) claim without eq, g(x) = sum_i mu_i P_B(f_i(x)) with P_B(x) = prod_{j = -(B-1)}^{B-1} (x - R::from(j)), over
+// 1 .. 8 dense MLEs (sr_range_wround_evals): every entry of every f_i lies in (-B, B) exactly when sum_b eq(beta, b) g(b) = 0.  It has the
+// members EqSumCheckOver uses of its g, so RangeSumCheck(RangePolynomial(cfg, tables, bound), z, order) is the prover of the whole norm
+// check.  The tables are referred to, not copied; coeffs: one ring element per table, or nullptr for one().  degree() = 2 bound - 1.
+class RangePolynomial {
+public:
+    RangePolynomial(CyclotomicConfig cfg, const std::vector<const DenseMultilinearExtension *> &tables, int bound, const RqNTTVec *coeffs = nullptr)
+        : cfg_(std::move(cfg)), nv_(tables.empty() ? 0 : tables[0]->num_vars()), bound_(bound), tables_(tables) {
+        if (tables.empty() || tables.size() > SR_RANGE_MAX_TABLES) throw std::length_error("RangePolynomial: 1 .. 8 tables");
+        if (bound < 2 || bound > SR_RANGE_MAX_BOUND) throw std::length_error("RangePolynomial: bound must be 2 .. 8");
+        for (const DenseMultilinearExtension *t : tables)
+            if (t->config().raw() != cfg_.raw() || t->num_vars() != nv_) throw std::length_error("RangePolynomial: the MLEs differ in ring or num_vars");
+        if (coeffs && coeffs->len() != tables.size()) throw std::length_error("RangePolynomial: one coefficient per table");
+        if (coeffs) coeffs_ = coeffs->words();
+    }
+    size_t num_vars() const { return nv_; }
+    size_t degree() const { return (size_t)(2 * bound_ - 1); }  // a round message has degree() + 1 elements
+    int bound() const { return bound_; }
+    const std::vector<const DenseMultilinearExtension *> &tables() const { return tables_; }
+    const CyclotomicConfig &config() const { return cfg_; }
+    // h(t) = sum_b weights[b] g(t, b), t = 0 .. degree(), b over the 2^(num_vars() - 1) pairs of the round
+    RqNTTVec round_evals_weighted(const RqNTTVec &weights, int order = SR_MLE_LEADING) const {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("round_evals_weighted: unknown order");
+        if (nv_ < 1 || weights.len() != (size_t)1 << (nv_ - 1)) throw std::length_error("round_evals_weighted: one weight per pair");
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        for (const DenseMultilinearExtension *t : tables_) {
+            ptrs.push_back(t->words().empty() ? nullptr : t->words().data());
+            sizes.push_back(t->len());
+        }
+        std::vector<uint64_t> out(cfg_.words_per_elem() * 2 * (size_t)bound_);
+        cfg_.range_wround_evals(out.data(), weights.words().data(), ptrs.data(), sizes.data(), (int)tables_.size(), bound_,
+                                coeffs_.empty() ? nullptr : coeffs_.data(), nv_, order);
+        return RqNTTVec(cfg_, std::move(out));
+    }
+    // the same claim with the variables of `point` fixed in every table; the result owns its tables
+    RangePolynomial fixed_variables(const RqNTTVec &point, int order = SR_MLE_LEADING) const {
+        if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("fixed_variables: unknown order");
+        if (point.len() > nv_) throw std::length_error("too many partial points");
+        auto owned = std::make_shared<std::vector<DenseMultilinearExtension>>();
+        for (const DenseMultilinearExtension *t : tables_)
+            owned->push_back(order == SR_MLE_LEADING ? t->fixed_variables(point) : t->fix_last_variables(point));
+        RangePolynomial g(*this);
+        g.nv_ = nv_ - point.len();
+        g.tables_.clear();
+        for (const DenseMultilinearExtension &t : *owned) g.tables_.push_back(&t);
+        g.owned_ = std::move(owned);
+        return g;
+    }
+    // every table folded at r (one variable, sr_mle_fix_variables) and round_evals_weighted(next_weights) of the folded claim
+    std::pair<RqNTTVec, RangePolynomial> fold_round_evals_weighted(const RqNTTVec &r, const RqNTTVec &next_weights, int order = SR_MLE_LEADING) const {
+        if (r.len() != 1) throw std::length_error("fold_round_evals_weighted: r is not one ring element");
+        if (nv_ < 2) throw std::length_error("fold_round_evals_weighted: num_vars >= 2");
+        RangePolynomial g = fixed_variables(r, order);
+        RqNTTVec msg = g.round_evals_weighted(next_weights, order);
+        return {std::move(msg), std::move(g)};
+    }
+
+private:
+    CyclotomicConfig cfg_;
+    size_t nv_;
+    int bound_;
+    std::vector<const DenseMultilinearExtension *> tables_;
+    std::vector<uint64_t> coeffs_;
+    std::shared_ptr<std::vector<DenseMultilinearExtension>> owned_;  // the tables of a claim that fixed_variables made
+};
+
 // The prover of a whole sum-check of  sum_b eq(z, b) g(b)  -- a zero-check, R1CS, the layer claim of a product or fraction tree -- WITHOUT
 // an eq table.  In the round that binds variable v, with the challenges r of the earlier rounds bound,
 //     s(t) = [prod_{i bound} eq(z_i, r_i)] * eq(z_v, t) * h(t),   h(t) = sum_b w[b] g(t, b),   w = eq(z_rest, .)
@@ -1029,9 +1118,11 @@ private:
 // (VirtualPolynomial::round_evals_weighted / fold_round_evals_weighted).  message() is s(0 .. degree + 1), bit-identical to what the
 // prover that holds eq(z, .) as one more table sends.  g is referred to, not copied, until the first next(); z: num_vars ring elements;
 // SR_MLE_LEADING binds variable 0 first, SR_MLE_TRAILING variable n - 1.
-class EqSumCheck {
+// G: VirtualPolynomial (EqSumCheck) or RangePolynomial (RangeSumCheck).
+template <class G>
+class EqSumCheckOver {
 public:
-    EqSumCheck(const VirtualPolynomial &g, const RqNTTVec &z, int order = SR_MLE_LEADING)
+    EqSumCheckOver(const G &g, const RqNTTVec &z, int order = SR_MLE_LEADING)
         : cfg_(g.config()), g_(g), z_(z), order_(order), n_(g.num_vars()), d_(g.degree()), round_(1), prefix_(one()), h_(one()) {
         if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("EqSumCheck: unknown order");
         if (n_ < 1 || d_ < 1) throw std::length_error("EqSumCheck: a polynomial of at least one variable and one product");
@@ -1112,12 +1203,14 @@ private:
         return slice(z_, v, v + 1);
     }
     CyclotomicConfig cfg_;
-    VirtualPolynomial g_;
+    G g_;
     RqNTTVec z_;
     int order_;
     size_t n_, d_, round_;
     RqNTTVec prefix_, h_;
 };
+using EqSumCheck = EqSumCheckOver<VirtualPolynomial>;
+using RangeSumCheck = EqSumCheckOver<RangePolynomial>;
 
 // The leaves of a permutation argument from ONE call over the three tables (K = 3, M = 2): {num, den} = {beta + f + gamma id,
 // beta + f + gamma sigma}; the mask of each row leaves out the table it does not use.  beta, gamma, one: one ring element each.

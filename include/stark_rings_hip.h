@@ -447,6 +447,45 @@ int sr_vpoly_wround_fold_evals_dev(sr_ctx *ctx, uint64_t *d_out, uint64_t *const
 int sr_vpoly_wround_fold_evals(sr_ctx *ctx, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
                                const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
                                const uint64_t *coeffs, size_t num_vars, const uint64_t *r, int order);
+/* Range-check (norm-check) rounds (csrc/range_check.hpp): the claim a lattice folding scheme runs in every fold and for every decomposed
+ * witness,
+ *     sum_b eq(beta, b) * sum_i mu_i * prod_{j = -(B-1)}^{B-1} ( f_i(b) - j ) = 0,
+ * which says that every entry of every f_i lies in (-B, B).  With eq as a per-pair weight (see above) the round message is
+ *   d_out[t] = sum_{b < half} w[b] * sum_i mu_i * P_B( lo_i[b] + t (hi_i[b] - lo_i[b]) ),   t = 0 .. 2 B - 1
+ *   P_B(x)   = prod_{j = -(B-1)}^{B-1} (x - R::from(j))
+ * with the pairs (lo, hi) of sr_vpoly_wround_evals_dev in the same order (SR_MLE_LEADING: f[2b], f[2b+1]; SR_MLE_TRAILING: f[b],
+ * f[b + half]).  The degree is 2 bound - 1 and a message has 2 bound elements.  A table is read ONCE per launch whatever the bound: no
+ * shifted copies f - j exist, none is folded, and the kernels evaluate P_B(x) = x prod_{j=1}^{B-1} (x^2 - j^2) with j^2 as base-field
+ * constants.  d_weights holds 2^(num_vars - 1) ring elements, one per pair, stored in full, never written.  d_coeffs holds n_tables
+ * elements (mu), or is NULL for one().  d_tables and n_evals are HOST arrays consumed at call time.  1 <= num_vars < 48,
+ * 1 <= n_tables <= SR_RANGE_MAX_TABLES, 2 <= bound <= SR_RANGE_MAX_BOUND; every ring id; CRT / NTT form, canonical in, canonical out.
+ * All arithmetic is exact on canonical values: the output depends on neither the grid, the split, the association nor how P_B is
+ * factored.  Nothing is allocated, no context scratch is touched, every workspace word is written before it is read, the launches are one
+ * linear chain on one stream (capturable on a fresh context).
+ *
+ * Truncated storage: a pair of table i is visited exactly while its first element is stored; an absent second element is zero and is
+ * never loaded; unvisited pairs contribute nothing, which is exact since P_B(0) = 0; a weight whose pair no table visits is not read.
+ * Every table empty: one launch zeroes d_out.
+ *
+ * SR_E_INVALID (nothing launched, the reason in sr_last_error): a null pointer (d_weights is checked first); bound, n_tables, order or
+ * num_vars outside their ranges; n_evals[i] > 2^num_vars; a workspace below the plan's; d_out or d_work overlapping a table, the
+ * weights, the coefficients or each other.
+ *
+ * sr_range_wround_plan is pure host arithmetic (no device, no context): *work_elems == 0 exactly when *launches == 1, *work_elems <=
+ * SR_MLE_ROUND_MAX_GROUPS * 2 bound; the records are those of sr_vpoly_round_plan.  Points per launch, the largest number that keeps
+ * the kernel without scratch within 256 registers (BabyBear 128), whatever n_tables and bound:
+ *   Goldilocks 7, BabyBear 8, Stark 3, goldilocks24 2, babybear72 2, frog16 2
+ * so a call takes ceil(2 bound / points) launches, each of which reads the tables and the weights once, plus the sum over the records
+ * where there are several.  The host-pointer form stages whole tables (and the weights) through context-owned temporaries as
+ * sr_vpoly_wround_evals does; chunked staging is not implemented. */
+#define SR_RANGE_MAX_TABLES 8
+#define SR_RANGE_MAX_BOUND 8
+int sr_range_wround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int bound, int order, size_t *work_elems, int *launches);
+int sr_range_wround_evals_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_weights, const uint64_t *const *d_tables, const size_t *n_evals,
+                              int n_tables, int bound, const uint64_t *d_coeffs, size_t num_vars, int order, uint64_t *d_work,
+                              size_t work_elems, void *stream);
+int sr_range_wround_evals(sr_ctx *ctx, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
+                          int n_tables, int bound, const uint64_t *coeffs, size_t num_vars, int order);
 /* Sparse multilinear extensions: the arithmetic of crates/poly's SparseMultilinearExtension (mle/sparse.rs) on device-resident
  * values.  Elements are ring elements in CRT / NTT form in the usual flat layout, canonical in and canonical out, for every ring id.
  *

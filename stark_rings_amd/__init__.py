@@ -10,6 +10,8 @@ Layout:
                         with the round message of a sum-check over a product, or a sum of products (VirtualPolynomial), of dense MLEs,
                         and EqSumCheck: a whole sum-check of eq(z, .) g with eq as per-pair weights, not a table
   wsumcheck.py          the device-pointer forms of the weighted sum-check rounds (sr_vpoly_wround_evals_dev, sr_vpoly_wround_fold_evals_dev)
+  range_check.py        range-check (norm-check) rounds: sum_i mu_i prod_j (f_i - j) over |j| < B from one read of each table, and
+                        RangePolynomial, the claim EqSumCheck runs a whole norm check on
   grand_product.py      ProductTree: every layer of a table's binary product tree, the circuit of the layered grand-product argument
   frac_tree.py          FractionTree: every layer of a sum of fractions p/q, the circuit of the layered logUp (lookup, range) argument
   lincomb.py            linear combinations of up to 16 tables with ring-element coefficients, up to 4 outputs from one pass
@@ -34,6 +36,7 @@ from .rings import (  # noqa: F401
 from .mle import DenseMultilinearExtension, EqSumCheck, SparseMultilinearExtension, VirtualPolynomial  # noqa: F401
 from .grand_product import ProductTree  # noqa: F401
 from .wsumcheck import vpoly_wround_evals_dev, vpoly_wround_fold_evals_dev  # noqa: F401
+from .range_check import RangePolynomial, range_wround_evals, range_wround_evals_dev, range_wround_plan  # noqa: F401
 from .frac_tree import FractionTree, frac_tree_dev, frac_tree_plan  # noqa: F401  (the host-pointer form: frac_tree.frac_tree)
 from .lincomb import lincomb_dev, lincomb_plan  # noqa: F401  (the host-pointer form: lincomb.lincomb)
 from .lookup import LookupCheck, PermutationCheck, fingerprint, permutation_leaves  # noqa: F401

@@ -83,6 +83,12 @@ SYMBOLS = {
                                              _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sr_vpoly_wround_evals": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int,
                                          _c.c_void_p, _c.c_size_t, _c.c_int]),
+    "sr_range_wround_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t),
+                                        _c.POINTER(_c.c_int)]),
+    "sr_range_wround_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p,
+                                             _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_range_wround_evals": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p,
+                                         _c.c_size_t, _c.c_int]),
     "sr_vpoly_wround_fold_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t),
                                              _c.POINTER(_c.c_int)]),
     "sr_vpoly_wround_fold_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,

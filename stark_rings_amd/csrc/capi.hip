@@ -41,6 +41,7 @@
 #include "prod_tree.hpp"
 #include "frac_tree.hpp"
 #include "lincomb.hpp"
+#include "range_check.hpp"
 
 namespace {
 
@@ -1839,6 +1840,36 @@ int check_round_work(const RoundFamily &f, const sr::sumcheck::Plan &p, const ui
         return refuse(f, "workspace too small (sr_" + std::string(f.name) + "_plan asks for " + std::to_string(p.work_elems) + " elements)");
     return SR_OK;
 }
+// range-check rounds (csrc/range_check.hpp): the family for the messages and the workspace check, the shared argument checks of the two
+// forms of sr_range_wround_evals, and the launches
+const RoundFamily kRangeWround{"range_wround", SR_RANGE_MAX_TABLES, false, false, true};
+int range_plan_for(int ring, int k, size_t num_vars, int n_tables, int bound, int order, sr::range::Plan *p) {
+    const RoundFamily &f = kRangeWround;
+    if (n_tables < 1 || n_tables > SR_RANGE_MAX_TABLES) return refuse(f, "n_tables must be 1 .. " + std::to_string(SR_RANGE_MAX_TABLES));
+    if (bound < 2 || bound > SR_RANGE_MAX_BOUND) return refuse(f, "bound must be 2 .. " + std::to_string(SR_RANGE_MAX_BOUND));
+    if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) return refuse(f, "unknown order");
+    if (num_vars >= 48) return refuse(f, "num_vars must be below 48");
+    if (num_vars == 0) return refuse(f, "a round needs num_vars >= 1");
+    return sr::range::plan(ring, k, num_vars, n_tables, bound, order, p) ? (int)SR_OK : refuse(f, "no plan for these arguments");
+}
+int check_range_wround(sr_ctx *c, const void *out, const void *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables, int bound,
+                       size_t num_vars, int order, sr::range::Plan *p) {
+    if (!weights) return refuse(kRangeWround, "null pointer (d_weights)");
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!out || !tables || !n_evals) return refuse(kRangeWround, "null pointer");
+    if (int rc = range_plan_for(c->ring, c->k, num_vars, n_tables, bound, order, p)) return rc;
+    return check_round_tables(c, kRangeWround, tables, nullptr, n_evals, n_tables, num_vars);
+}
+int dev_range_wround(sr_ctx *c, const sr::range::Plan &p, int order, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables,
+                     const size_t *n_evals, int n_tables, int bound, const uint64_t *coef, size_t num_vars, uint64_t *work, hipStream_t st) {
+    sr::range::Tables tb{};
+    const uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)coef |
+                           (p.groups > 1 ? (uintptr_t)work : 0);
+    return round_dispatch(c, st, "range wround", [&](auto t, const auto &kc) {
+        return sr::range::launch<typename decltype(t)::type>(kc, p, order, out, weights, tb, n_tables, bound, coef, num_vars, c->k, (bits & 15u) == 0,
+                                                             work, st);
+    });
+}
 // elements the fold of a table of n stored elements writes
 size_t round_fold_n_out(size_t n, size_t num_vars, int order) {
     const size_t half = (size_t)1 << (num_vars - 1);
@@ -3228,6 +3259,54 @@ int sr_vpoly_wround_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_ta
                       for (int j = 0; j < n_tables; j++)
                           if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
                       return SR_OK;
+                  });
+}
+int sr_range_wround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int bound, int order, size_t *work_elems, int *launches) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!work_elems || !launches) return fail(SR_E_INVALID, "range_wround_plan: null result pointer");
+    sr::range::Plan p;
+    if (int rc = range_plan_for(ring, log2_degree, num_vars, n_tables, bound, order, &p)) return rc;
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    return SR_OK;
+}
+int sr_range_wround_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
+                              int n_tables, int bound, const uint64_t *coef, size_t num_vars, int order, uint64_t *work, size_t work_elems,
+                              void *stream) {
+    sr::range::Plan p;
+    if (int rc = check_range_wround(c, out, weights, tables, n_evals, n_tables, bound, num_vars, order, &p)) return rc;
+    if (int rc = check_round_work(kRangeWround, p, work, work_elems)) return rc;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const size_t cw = coef ? n_tables * w : 0, ww = w << (num_vars - 1);
+    for (int j = 0; j < n_tables; j++) {
+        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return refuse(kRangeWround, "d_out overlaps a table");
+        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return refuse(kRangeWround, "d_work overlaps a table");
+    }
+    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return refuse(kRangeWround, "d_out overlaps d_work");
+    if (ranges_overlap(out, p.np_total * w, coef, cw)) return refuse(kRangeWround, "d_out overlaps d_coeffs");
+    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return refuse(kRangeWround, "d_work overlaps d_coeffs");
+    if (ranges_overlap(out, p.np_total * w, weights, ww)) return refuse(kRangeWround, "d_out overlaps d_weights");
+    if (ranges_overlap(work, p.work_elems * w, weights, ww)) return refuse(kRangeWround, "d_work overlaps d_weights");
+    const Call call(c, stream);
+    return dev_range_wround(c, p, order, out, weights, tables, n_evals, n_tables, bound, coef, num_vars, work, call.st);
+}
+int sr_range_wround_evals(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                          int bound, const uint64_t *coef, size_t num_vars, int order) {
+    sr::range::Plan p;
+    if (int rc = check_range_wround(c, out, weights, tables, n_evals, n_tables, bound, num_vars, order, &p)) return rc;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const TableSlot in(n_evals, n_tables, w);
+    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients; HOST_4: the weights
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {coef, nullptr, coef ? n_tables * w : 0},
+                      {weights, nullptr, w << (num_vars - 1)}},
+                  [&](void *const *d) -> int {
+                      uint64_t *dt[SR_RANGE_MAX_TABLES];
+                      in.at(d[0], n_tables, dt);
+                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
+                      return dev_range_wround(c, p, order, (uint64_t *)d[1], (const uint64_t *)d[4], dt, n_evals, n_tables, bound,
+                                              coef ? (const uint64_t *)d[3] : nullptr, num_vars, (uint64_t *)d[2], c->stream);
                   });
 }
 int sr_eq_table_dev(sr_ctx *c, uint64_t *out, const uint64_t *point, size_t n_vars, void *stream) {

@@ -1,0 +1,39 @@
+"""Builds and runs tests/cpp/test_range_api.cpp: RangePolynomial, RangeSumCheck and the range_wround_* calls of include/stark_rings.hpp
+(the C++ mirror of sr_range_wround_plan / sr_range_wround_evals: the norm check from one read of each table) against the
+VirtualPolynomial of the shifted tables (f, f - 1, f + 1) built from the mirror's older calls."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "build_tmp", "test_range_api")
+
+
+def _build():
+    import oracle_lib
+
+    oracle_lib.build()
+    os.makedirs(os.path.dirname(BIN), exist_ok=True)
+    src = os.path.join(ROOT, "tests", "cpp", "test_range_api.cpp")
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-o", BIN, src,
+           "-L" + os.path.join(ROOT, "stark_rings_amd"), "-lstarkrings_hip",
+           "-L" + os.path.join(ROOT, "oracle"), "-lsr_oracle",
+           "-Wl,-rpath," + os.path.join(ROOT, "stark_rings_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"),
+           "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-lpthread"]
+    subprocess.check_call(cmd, cwd=ROOT)
+
+
+def test_cpp_range_mirror_compiles():
+    """CPU: the new methods and their test compile and link against the C ABI."""
+    _build()
+    assert os.path.exists(BIN)
+
+
+@pytest.mark.gpu
+def test_cpp_range_mirror_parity():
+    _build()
+    r = subprocess.run([BIN], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all ok" in r.stdout
