@@ -33,6 +33,10 @@
 //     Add<R>, in one pass                  386-395                     tables and 4 outputs); DenseMultilinearExtension::linear_combination;
 //                                                                      fingerprint, permutation_leaves, class PermutationCheck / LookupCheck /
 //                                                                      LayerClaim: leaves, trees and layer claims of both arguments
+//     From<u64> beside the tables          polynomials/                IndexColumn, lincomb_index_plan / lincomb_index / lincomb_index_dev,
+//     (integer columns),                   multilinear_polynomial.rs   from_u64, index_count, linear_combination_indexed,
+//     identity_permutation[_mles]          :79-133                     permutation_leaves_indexed, identity_permutation[_mles],
+//                                                                      LookupCheck::from_indices (sr_lincomb_index, sr_index_count)
 //   a sum of products of dense MLEs      (HyperPlonk's VirtualPolynomial) class VirtualPolynomial: add_mle_list, mul_by_mle, degree, round_evals, sum
 //                                                                      (sr_vpoly_round_evals: one pass, every distinct table read once),
 //                                                                      fold_round_evals (sr_vpoly_round_fold_evals: fold at the challenge
@@ -492,6 +496,86 @@ inline std::vector<std::vector<uint64_t>> lincomb(const CyclotomicConfig &cfg, c
     return outs;
 }
 
+// A column of integers as an input of a linear combination (sr_index_column): stored uint64_t values -- at most n, the rest of the
+// column counts as 0 -- or the progression start, start + 1, .., which occupies no memory.  It enters as coef * R::from(col[e]), the
+// reference's From<u64> (from_scalar(BaseRing::from(x)) in CRT/NTT form).
+struct IndexColumn {
+    std::vector<uint64_t> values;
+    bool is_progression = false;
+    uint64_t start = 0;
+    static IndexColumn stored(std::vector<uint64_t> v) {
+        IndexColumn c;
+        c.values = std::move(v);
+        return c;
+    }
+    static IndexColumn progression(uint64_t first) {
+        IndexColumn c;
+        c.is_progression = true;
+        c.start = first;
+        return c;
+    }
+};
+// sr_lincomb_index_plan: {kernel launches, outputs one launch produces}
+inline std::pair<int, int> lincomb_index_plan(sr_ring ring, int log2_degree, int n_tables, int n_index, int n_outputs) {
+    int launches = 0, per = 0;
+    CyclotomicConfig::check(sr_lincomb_index_plan(ring, log2_degree, n_tables, n_index, n_outputs, &launches, &per), "sr_lincomb_index_plan");
+    return {launches, per};
+}
+// sr_lincomb_index_dev on device pointers (columns: a host array whose `values` are device pointers); allocates nothing
+inline void lincomb_index_dev(const CyclotomicConfig &cfg, uint64_t *const *d_outs, int n_outputs, const uint64_t *const *d_tables,
+                              const size_t *n_evals, int n_tables, const sr_index_column *columns, int n_index, const uint64_t *d_coef,
+                              const uint32_t *uses, size_t n, void *stream = nullptr) {
+    CyclotomicConfig::check(sr_lincomb_index_dev(cfg.raw(), d_outs, n_outputs, d_tables, n_evals, n_tables, columns, n_index, d_coef, uses, n, stream),
+                            "sr_lincomb_index_dev");
+}
+// sr_lincomb_index on host words: out_m[e] = [bit K+J] coef[m][K+J] + sum_k [bit k] coef[m][k] * T_k[e] + sum_j [bit K+j] coef[m][K+j] *
+// R::from(col_j[e]); coef holds uses.size() rows of tables.size() + columns.size() + 1 elements: tables, columns, the constant
+inline std::vector<std::vector<uint64_t>> lincomb_index(const CyclotomicConfig &cfg, const std::vector<const std::vector<uint64_t> *> &tables,
+                                                        const std::vector<IndexColumn> &columns, const std::vector<uint64_t> &coef,
+                                                        const std::vector<uint32_t> &uses, size_t n) {
+    const size_t w = cfg.words_per_elem(), terms = tables.size() + columns.size();
+    if (tables.size() > SR_LINCOMB_MAX_TABLES || columns.size() > SR_LINCOMB_MAX_INDEX_COLUMNS || terms < 1 || terms > SR_LINCOMB_MAX_TABLES)
+        throw std::length_error("lincomb_index: 0 .. 16 tables, 0 .. 8 index columns, 1 .. 16 of both together");
+    if (uses.empty() || uses.size() > SR_LINCOMB_MAX_OUTPUTS) throw std::length_error("lincomb_index: 1 .. 4 outputs");
+    if (coef.size() != uses.size() * (terms + 1) * w) throw std::length_error("lincomb_index: coef must hold n_outputs x (n_tables + n_index + 1) elements");
+    std::vector<std::vector<uint64_t>> outs(uses.size(), std::vector<uint64_t>(n * w));
+    const uint64_t dummy = 0;
+    uint64_t sink = 0;
+    std::vector<const uint64_t *> pt;
+    std::vector<size_t> sizes;
+    std::vector<uint64_t *> po;
+    std::vector<sr_index_column> pc;
+    for (const std::vector<uint64_t> *t : tables) {
+        if (t->size() % w) throw std::length_error("Should be of correct length");
+        pt.push_back(t->empty() ? &dummy : t->data());
+        sizes.push_back(t->size() / w);
+    }
+    for (const IndexColumn &c : columns) {
+        if (c.is_progression) pc.push_back(sr_index_column{nullptr, 0, c.start});
+        else pc.push_back(sr_index_column{c.values.empty() ? &dummy : c.values.data(), c.values.size(), 0});
+    }
+    for (auto &o : outs) po.push_back(o.empty() ? &sink : o.data());
+    CyclotomicConfig::check(sr_lincomb_index(cfg.raw(), po.data(), (int)uses.size(), pt.data(), sizes.data(), (int)tables.size(), pc.data(),
+                                             (int)columns.size(), coef.data(), uses.data(), n),
+                            "sr_lincomb_index");
+    return outs;
+}
+// sr_index_count on host words: counts[t] = #{ i : idx[i] == t } for t < n_bins; throws on an index that is not below n_bins
+inline std::vector<uint64_t> index_count(const CyclotomicConfig &cfg, const std::vector<uint64_t> &idx, size_t n_bins) {
+    std::vector<uint64_t> counts(n_bins, 0);
+    uint64_t sink = 0, none = 0;
+    CyclotomicConfig::check(sr_index_count(cfg.raw(), n_bins ? counts.data() : &sink, idx.empty() ? &none : idx.data(), idx.size(), n_bins),
+                            "sr_index_count");
+    return counts;
+}
+// The table R::from(col[e]), e < n, as words: one call with no table, one column and the coefficient one()
+inline std::vector<uint64_t> from_u64(const CyclotomicConfig &cfg, const IndexColumn &column, size_t n, const std::vector<uint64_t> &one_words) {
+    if (one_words.size() != cfg.words_per_elem()) throw std::length_error("from_u64: one is one ring element");
+    std::vector<uint64_t> coef(one_words);
+    coef.resize(2 * one_words.size(), 0);
+    return std::move(lincomb_index(cfg, {}, {column}, coef, {0x1u}, n)[0]);
+}
+
 // DenseMultilinearExtension<RqNTT> of crates/poly (src/mle/dense.rs): a table of 2^num_vars ring elements in CRT/NTT form, of which
 // only the first len() are stored -- the rest is zero (dense.rs:35-54, 397-407).  Host buffers over sr_mle_fix_variables /
 // sr_mul_elem_add_batch; `r * a` is the slot product of the ring.  Throws where the reference asserts.
@@ -556,6 +640,36 @@ public:
         const uint32_t mask = (((uint32_t)1 << mles.size()) - 1) | (constant ? (uint32_t)1 << mles.size() : 0);
         auto outs = lincomb(first.cfg_, tables, coef, {mask}, n);
         return DenseMultilinearExtension(first.cfg_, first.nv_, std::move(outs[0]));
+    }
+    // linear_combination with integer columns beside the MLEs (sr_lincomb_index): sum_k coeffs[k] * mles[k] + sum_j coeffs[K + j] *
+    // R::from(columns[j]) (+ constant) over num_vars variables of the ring cfg (there may be no MLE to take them from).  The result
+    // stores the longest input (a progression is as long as the table), or all 2^num_vars with a constant.
+    static DenseMultilinearExtension linear_combination_indexed(const CyclotomicConfig &cfg, size_t num_vars,
+                                                                const std::vector<const DenseMultilinearExtension *> &mles,
+                                                                const std::vector<IndexColumn> &columns, const RqNTTVec &coeffs,
+                                                                const RqNTTVec *constant = nullptr) {
+        const size_t w = cfg.words_per_elem(), terms = mles.size() + columns.size();
+        if (num_vars >= 48) throw std::length_error("linear_combination_indexed: num_vars must be below 48");
+        if (coeffs.len() != terms || (constant && constant->len() != 1))
+            throw std::length_error("linear_combination_indexed: one coefficient per MLE and column, and a constant of one ring element");
+        std::vector<const std::vector<uint64_t> *> tables;
+        size_t n = 0;
+        for (const DenseMultilinearExtension *m : mles) {
+            if (m->cfg_.raw() != cfg.raw() || m->nv_ != num_vars) throw std::length_error("linear_combination_indexed: the MLEs differ in ring or num_vars");
+            tables.push_back(&m->w_);
+            n = std::max(n, m->len());
+        }
+        for (const IndexColumn &c : columns) {
+            if (!c.is_progression && c.values.size() > ((size_t)1 << num_vars)) throw std::length_error("linear_combination_indexed: more values than 2^num_vars");
+            n = std::max(n, c.is_progression ? (size_t)1 << num_vars : c.values.size());
+        }
+        if (constant) n = (size_t)1 << num_vars;
+        std::vector<uint64_t> coef(coeffs.words());
+        if (constant) coef.insert(coef.end(), constant->words().begin(), constant->words().end());
+        else coef.resize(coef.size() + w, 0);
+        const uint32_t mask = (((uint32_t)1 << terms) - 1) | (constant ? (uint32_t)1 << terms : 0);
+        auto outs = lincomb_index(cfg, tables, columns, coef, {mask}, n);
+        return DenseMultilinearExtension(cfg, num_vars, std::move(outs[0]));
     }
     RqNTTVec to_evaluations() const {  // all 2^num_vars elements
         std::vector<uint64_t> all(w_);
@@ -1241,6 +1355,35 @@ inline std::vector<uint64_t> fingerprint(const CyclotomicConfig &cfg, const std:
     return std::move(lincomb(cfg, columns, coef, {mask}, columns[0]->size() / w)[0]);
 }
 
+// permutation_leaves with id and sigma as integers: {num, den} = {beta + f + gamma R::from(id_start + e), beta + f + gamma
+// R::from(sigma_idx[e])} from ONE call with K = 1, J = 2, M = 2; id is a progression, sigma_idx one uint64_t per row of f
+inline std::pair<std::vector<uint64_t>, std::vector<uint64_t>> permutation_leaves_indexed(const CyclotomicConfig &cfg, const std::vector<uint64_t> &f,
+                                                                                          const std::vector<uint64_t> &sigma_idx, const RqNTTVec &beta,
+                                                                                          const RqNTTVec &gamma, const RqNTTVec &one,
+                                                                                          uint64_t id_start = 0) {
+    const size_t w = cfg.words_per_elem();
+    if (f.size() % w || sigma_idx.size() != f.size() / w) throw std::length_error("permutation_leaves_indexed: sigma_idx holds one integer per row of f");
+    if (beta.len() != 1 || gamma.len() != 1 || one.len() != 1)
+        throw std::length_error("permutation_leaves_indexed: beta, gamma and one are one ring element each");
+    std::vector<uint64_t> coef;
+    for (int row = 0; row < 2; row++)
+        for (const RqNTTVec *c : {&one, &gamma, &gamma, &beta}) coef.insert(coef.end(), c->words().begin(), c->words().end());
+    auto outs = lincomb_index(cfg, {&f}, {IndexColumn::progression(id_start), IndexColumn::stored(sigma_idx)}, coef, {0xBu, 0xDu}, f.size() / w);
+    return {std::move(outs[0]), std::move(outs[1])};
+}
+// The reference's identity_permutation (polynomials/multilinear_polynomial.rs:79-89): R::from(0), .., R::from(num_chunks 2^num_vars - 1)
+inline std::vector<uint64_t> identity_permutation(const CyclotomicConfig &cfg, size_t num_vars, size_t num_chunks, const RqNTTVec &one) {
+    return from_u64(cfg, IndexColumn::progression(0), num_chunks << num_vars, one.words());
+}
+// identity_permutation_mles (:91-105): chunk i holds R::from(i 2^num_vars + e)
+inline std::vector<DenseMultilinearExtension> identity_permutation_mles(const CyclotomicConfig &cfg, size_t num_vars, size_t num_chunks,
+                                                                        const RqNTTVec &one) {
+    std::vector<DenseMultilinearExtension> out;
+    for (size_t i = 0; i < num_chunks; i++)
+        out.emplace_back(cfg, num_vars, from_u64(cfg, IndexColumn::progression((uint64_t)i << num_vars), (size_t)1 << num_vars, one.words()));
+    return out;
+}
+
 // The layer claim of a tree as an object that owns its operands: the halves of the layer below, the polynomial over them and the
 // EqSumCheck of eq(z, .) times it (VirtualPolynomial refers to its MLEs, so they live here).
 class LayerClaim {
@@ -1295,6 +1438,14 @@ public:
                 size_t num_vars_w, size_t num_vars_t)
         : cfg_(cfg), witness_(cfg, std::move(witness_q), num_vars_w, SR_MLE_TRAILING),
           table_(cfg, std::move(multiplicities), std::move(table_q), num_vars_t, SR_MLE_TRAILING) {}
+    // The check with its multiplicities counted from indices: indices[i] is the table row that witness row i was taken from; the
+    // numerators of the table side are R::from(count[j]) (sr_index_count, then from_u64).  Throws on an index beyond the table.
+    static LookupCheck from_indices(CyclotomicConfig cfg, std::vector<uint64_t> witness_q, std::vector<uint64_t> table_q,
+                                    const std::vector<uint64_t> &indices, size_t num_vars_w, size_t num_vars_t, const RqNTTVec &one) {
+        const size_t rows = table_q.size() / cfg.words_per_elem();
+        std::vector<uint64_t> mult = from_u64(cfg, IndexColumn::stored(index_count(cfg, indices, rows)), rows, one.words());
+        return LookupCheck(cfg, std::move(witness_q), std::move(table_q), std::move(mult), num_vars_w, num_vars_t);
+    }
     const FractionTree &witness() const { return witness_; }
     const FractionTree &table() const { return table_; }
     bool holds() const {

@@ -613,6 +613,43 @@ int sr_lincomb_dev(sr_ctx *ctx, uint64_t *const *d_outs, int n_outputs, const ui
                    int n_tables, const uint64_t *d_coef, const uint32_t *uses, size_t n, void *stream);
 int sr_lincomb(sr_ctx *ctx, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                const uint64_t *coef, const uint32_t *uses, size_t n);
+/* Integer columns (csrc/lincomb_index.hpp): a linear combination whose inputs are tables of ring elements AND columns of integers,
+ *   out_m[e] = [bit K+J of uses[m]] coef[m][K+J]  +  sum_{k < K, bit k} coef[m][k] * T_k[e]
+ *            + sum_{j < J, bit K+j} coef[m][K+j] * R::from(col_j[e])                  e < n, 0 <= K <= 16, 0 <= J <= 8, 1 <= K + J <= 16
+ * -- sr_lincomb (mle/dense.rs:288-317, :370-374, :386-395) with R::from(u64) = from_scalar(BaseRing::from(x)) in CRT / NTT form as a
+ * further kind of operand: x mod p in every coefficient of a power-of-two ring, in component 0 of every slot of goldilocks24 /
+ * babybear72 / frog16 (what sr_add_scalar_batch adds with ntt_form != 0), so coef * R::from(x) scales every base-field component of
+ * coef by x mod p (sr_scale_batch); x >= p (Goldilocks, frog16) is reduced.  A column is n_evals <= n stored uint64_t (the rest count
+ * as 0 and are never read) or, with values == NULL, the progression start, start + 1, .. which reads no memory: the reference's
+ * identity_permutation[_mles] / random_permutation[_mles] (crates/poly/src/polynomials/multilinear_polynomial.rs:79-133), the table
+ * side of a logUp lookup over small integers and its multiplicities need no ring table.  A row of coef has K + J + 1 elements -- tables,
+ * columns, the constant -- and the mask bits follow that order.  The array `columns` is a HOST array in both forms, consumed at call
+ * time (its entries travel in the kernel arguments); in the _dev form `values` is a DEVICE pointer.
+ * sr_lincomb_index_dev keeps sr_lincomb_dev's promises: nothing allocated, no context scratch, capturable without warm-up, canonical in
+ * gives canonical out, n == 0 succeeds and launches nothing, n < 2^48, in place for one output; with n_index == 0 it is sr_lincomb_dev.
+ * SR_E_INVALID, each with its own message and before any device work: a null context (first), counts outside the bounds above, a null
+ * pointer where one is needed, a mask of zero, a mask bit above K + J, a table or column that no output uses, n_evals > n, values !=
+ * NULL with start != 0, a progression with start + (n - 1) > 2^64 - 1, an output overlapping a column's array or d_coef, and the
+ * aliasing rules of sr_lincomb_dev for tables and outputs.
+ * sr_lincomb_index_plan: pure host arithmetic, as sr_lincomb_plan; K + J <= 4 keeps the coefficients in registers (two outputs on
+ * Goldilocks and BabyBear, one on goldilocks24), otherwise four outputs per launch on BabyBear, three on Goldilocks, one elsewhere.
+ * sr_index_count[_dev]: counts[t] = #{ i : idx[i] == t } as uint64_t for t < n_bins, n and n_bins below 2^48.  The call clears counts
+ * itself, on the stream.  The _dev form skips an index >= n_bins and counts it with the out-of-range columns of spmv
+ * (sr_spmv_bad_index_count); the host form validates and returns SR_E_INVALID.  Up to 4096 bins are counted in LDS per workgroup. */
+enum { SR_LINCOMB_MAX_INDEX_COLUMNS = 8 };
+typedef struct sr_index_column {
+    const uint64_t *values; /* n_evals integers (a DEVICE pointer in the _dev form), or NULL: the progression start, start + 1, .. */
+    size_t n_evals;         /* stored entries <= n, the rest count as 0; ignored for a progression */
+    uint64_t start;         /* first value of a progression; 0 when values != NULL */
+} sr_index_column;
+int sr_lincomb_index_plan(int ring, int log2_degree, int n_tables, int n_index, int n_outputs, int *launches, int *outputs_per_launch);
+int sr_lincomb_index_dev(sr_ctx *ctx, uint64_t *const *d_outs, int n_outputs, const uint64_t *const *d_tables, const size_t *n_evals,
+                         int n_tables, const sr_index_column *columns, int n_index, const uint64_t *d_coef, const uint32_t *uses, size_t n,
+                         void *stream);
+int sr_lincomb_index(sr_ctx *ctx, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                     const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n);
+int sr_index_count_dev(sr_ctx *ctx, uint64_t *d_counts, const uint64_t *d_idx, size_t n, size_t n_bins, void *stream);
+int sr_index_count(sr_ctx *ctx, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins);
 /* Norms of a coefficient slice on the device: WithLinfNorm::linf_norm / WithL2Norm::l2_norm_squared over [Fq]
  * (crates/ring/src/traits.rs:6-36; per element balanced_decomposition/convertible_ring.rs:49-66; the signed representative of
  * fq_convertible.rs:20-34 and stark_prime/decomposition.rs:40-52).

@@ -55,6 +55,13 @@ SYMBOLS = {
     "sr_lincomb_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
                                   _c.c_void_p]),
     "sr_lincomb": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, u64p, _c.c_void_p, _c.c_size_t]),
+    "sr_lincomb_index_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sr_lincomb_index_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                        _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_lincomb_index": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, u64p, _c.c_void_p,
+                                    _c.c_size_t]),
+    "sr_index_count_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p]),
+    "sr_index_count": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t, _c.c_size_t]),
     "sr_mle_round_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
     "sr_mle_round_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_void_p,
                                           _c.c_size_t, _c.c_void_p]),

@@ -41,6 +41,7 @@
 #include "prod_tree.hpp"
 #include "frac_tree.hpp"
 #include "lincomb.hpp"
+#include "lincomb_index.hpp"
 #include "range_check.hpp"
 
 namespace {
@@ -2322,6 +2323,123 @@ int check_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_
     }
     return SR_OK;
 }
+// ---- linear combinations with integer columns, multiplicities (csrc/lincomb_index.hpp): as above, nothing allocated -----------------
+// n_index == 0 is dev_lincomb, bit for bit
+int dev_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                      const sr_index_column *cols, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n, hipStream_t st) {
+    namespace li = sr::lincomb_index;
+    if (n_index == 0) return dev_lincomb(c, outs, n_outputs, tables, n_evals, n_tables, coef, uses, n, st);
+    if (n == 0) return SR_OK;
+    sr::lincomb::Plan p;
+    if (!li::plan(c->ring, n_tables, n_index, n_outputs, &p)) return fail(SR_E_INVALID, "lincomb_index: no plan for these arguments");
+    const size_t w = (size_t)c->degree * c->limbs;
+    const int terms = n_tables + n_index;
+    uintptr_t all = (uintptr_t)coef;
+    for (int k = 0; k < n_tables; k++) all |= (uintptr_t)tables[k];
+    for (int m = 0; m < n_outputs; m++) all |= (uintptr_t)outs[m];
+    const bool aligned = (all & 15u) == 0;
+    const bool reg = p.launches == 1 && terms <= li::kRegTerms;
+    for (int m0 = 0; m0 < n_outputs; m0 += p.outputs_per_launch) {
+        const int mm = n_outputs - m0 < p.outputs_per_launch ? n_outputs - m0 : p.outputs_per_launch;
+        li::Args a{};
+        for (int k = 0; k < n_tables; k++) {
+            a.t[k] = tables[k];
+            a.ne[k] = n_evals ? n_evals[k] : n;
+        }
+        for (int j = 0; j < n_index; j++) {
+            a.col[j] = cols[j].values;
+            a.cne[j] = cols[j].values ? cols[j].n_evals : 0;
+            a.start[j] = cols[j].start;
+        }
+        for (int m = 0; m < mm; m++) {
+            a.out[m] = outs[m0 + m];
+            a.uses[m] = uses[m0 + m];
+        }
+        a.coef = coef + (size_t)m0 * (terms + 1) * w;
+        ProfScope prof(c, st, K_POINTWISE);
+        hipError_t e;
+        switch (c->ring) {
+            case SR_RING_GOLDILOCKS_POW2: e = li::launch<sr::Goldilocks>({}, reg, mm, a, n_tables, n_index, n, c->k, aligned, st); break;
+            case SR_RING_BABYBEAR_POW2: e = li::launch<sr::BabyBear>({}, reg, mm, a, n_tables, n_index, n, c->k, aligned, st); break;
+            case SR_RING_STARK_POW2: e = li::launch<sr::Stark>({}, reg, mm, a, n_tables, n_index, n, c->k, aligned, st); break;
+            case SR_RING_GOLDILOCKS_24: e = li::launch<sr::SlotG24>(c->small, reg, mm, a, n_tables, n_index, n, 0, aligned, st); break;
+            case SR_RING_BABYBEAR_72: e = li::launch<sr::SlotB72>(c->small, false, mm, a, n_tables, n_index, n, 0, aligned, st); break;
+            default: e = li::launch<sr::SlotFrog>(c->frog, false, mm, a, n_tables, n_index, n, 0, aligned, st); break;
+        }
+        if (e != hipSuccess) return fail(SR_E_HIP, std::string("lincomb_index launch: ") + hipGetErrorString(e));
+    }
+    return SR_OK;
+}
+// the argument checks the two forms of sr_lincomb_index share; everything here is host arithmetic on the arguments
+int check_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                        const sr_index_column *cols, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (n_tables < 0 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_index: n_tables outside 0 .. 16");
+    if (n_index < 0 || n_index > SR_LINCOMB_MAX_INDEX_COLUMNS) return fail(SR_E_INVALID, "lincomb_index: n_index outside 0 .. 8");
+    const int terms = n_tables + n_index;
+    if (terms < 1 || terms > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_index: n_tables + n_index outside 1 .. 16");
+    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb_index: n_outputs outside 1 .. 4");
+    if (!outs || (n_tables && !tables) || (n_index && !cols) || !coef || !uses) return fail(SR_E_INVALID, "lincomb_index: null argument");
+    uint32_t any = 0;
+    for (int m = 0; m < n_outputs; m++) {
+        if (uses[m] == 0) return fail(SR_E_INVALID, "lincomb_index: an output with an empty mask");
+        if (uses[m] >> (terms + 1)) return fail(SR_E_INVALID, "lincomb_index: a mask bit above n_tables + n_index");
+        any |= uses[m];
+    }
+    for (int k = 0; k < n_tables; k++)
+        if (!((any >> k) & 1u)) return fail(SR_E_INVALID, "lincomb_index: a table that no output uses");
+    for (int j = 0; j < n_index; j++)
+        if (!((any >> (n_tables + j)) & 1u)) return fail(SR_E_INVALID, "lincomb_index: a column that no output uses");
+    if (n >= (size_t)1 << 48) return fail(SR_E_INVALID, "lincomb_index: n must be below 2^48");
+    for (int k = 0; k < n_tables; k++)
+        if (n_evals && n_evals[k] > n) return fail(SR_E_INVALID, "lincomb_index: n_evals exceeds n");
+    for (int j = 0; j < n_index; j++) {
+        if (cols[j].values) {
+            if (cols[j].n_evals > n) return fail(SR_E_INVALID, "lincomb_index: a column's n_evals exceeds n");
+            if (cols[j].start != 0) return fail(SR_E_INVALID, "lincomb_index: a stored column with a non-zero start");
+        } else if (n && cols[j].start > UINT64_MAX - (uint64_t)(n - 1)) {
+            return fail(SR_E_INVALID, "lincomb_index: a progression wraps past 2^64 - 1");
+        }
+    }
+    for (int k = 0; k < n_tables; k++)
+        if (!tables[k]) return fail(SR_E_INVALID, "lincomb_index: null table");
+    for (int m = 0; m < n_outputs; m++)
+        if (!outs[m]) return fail(SR_E_INVALID, "lincomb_index: null output");
+    if (int rc = check_count(c, n)) return rc;  // everything above is decided without reading the context
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    for (int m = 0; m < n_outputs; m++) {
+        for (int j = 0; j < m; j++)
+            if (ranges_overlap(outs[m], n * w, outs[j], n * w)) return fail(SR_E_INVALID, "lincomb_index: two outputs overlap");
+        if (ranges_overlap(outs[m], n * w, coef, (size_t)n_outputs * (terms + 1) * w))
+            return fail(SR_E_INVALID, "lincomb_index: an output overlaps the coefficients");
+        for (int j = 0; j < n_index; j++)
+            if (cols[j].values && ranges_overlap(outs[m], n * w, cols[j].values, cols[j].n_evals * 8))
+                return fail(SR_E_INVALID, "lincomb_index: an output overlaps a column");
+        for (int k = 0; k < n_tables; k++) {
+            if (!ranges_overlap(outs[m], n * w, tables[k], (n_evals ? n_evals[k] : n) * w)) continue;
+            if (outs[m] != tables[k]) return fail(SR_E_INVALID, "lincomb_index: an output overlaps a table");
+            if (n_outputs != 1) return fail(SR_E_INVALID, "lincomb_index: in place needs n_outputs == 1");
+        }
+    }
+    return SR_OK;
+}
+// counts[t] = #{ i : idx[i] == t }: the clear and one launch on the stream; an index >= n_bins goes to d_counter[1] (gather's, spmv's)
+int dev_index_count(sr_ctx *c, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins, hipStream_t st) {
+    if (n_bins) HIP_TRY(hipMemsetAsync(counts, 0, n_bins * 8, st));
+    if (n == 0) return SR_OK;
+    ProfScope ps(c, st, K_OTHER);
+    const hipError_t e = sr::lincomb_index::launch_count(counts, idx, n, n_bins, c->d_counter + 1, st);
+    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("index_count launch: ") + hipGetErrorString(e));
+}
+int check_index_count(sr_ctx *c, const uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (n >= (size_t)1 << 48) return fail(SR_E_INVALID, "index_count: n must be below 2^48");
+    if (n_bins >= (size_t)1 << 48) return fail(SR_E_INVALID, "index_count: n_bins must be below 2^48");
+    if (n_bins && !counts) return fail(SR_E_INVALID, "index_count: null counts");
+    if (n && !idx) return fail(SR_E_INVALID, "index_count: null indices");
+    if (ranges_overlap(counts, n_bins * 8, idx, n * 8)) return fail(SR_E_INVALID, "index_count: counts overlaps the indices");
+    return SR_OK;
+}
 // d_counter[i] (sr_ctx_create_ex) to the host, then cleared
 int read_counter(sr_ctx *c, int i, unsigned long long *out, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(out, c->d_counter + i, sizeof *out, hipMemcpyDeviceToHost, st));
@@ -2988,6 +3106,83 @@ int sr_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *
                               return SR_OK;
                           });
     return rc;
+}
+int sr_lincomb_index_plan(int ring, int log2_degree, int n_tables, int n_index, int n_outputs, int *launches, int *outputs_per_launch) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (!launches || !outputs_per_launch) return fail(SR_E_INVALID, "lincomb_index_plan: null result pointer");
+    if (n_tables < 0 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_index_plan: n_tables outside 0 .. 16");
+    if (n_index < 0 || n_index > SR_LINCOMB_MAX_INDEX_COLUMNS) return fail(SR_E_INVALID, "lincomb_index_plan: n_index outside 0 .. 8");
+    if (n_tables + n_index < 1 || n_tables + n_index > SR_LINCOMB_MAX_TABLES)
+        return fail(SR_E_INVALID, "lincomb_index_plan: n_tables + n_index outside 1 .. 16");
+    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb_index_plan: n_outputs outside 1 .. 4");
+    sr::lincomb::Plan p;
+    if (!sr::lincomb_index::plan(ring, n_tables, n_index, n_outputs, &p)) return fail(SR_E_INVALID, "lincomb_index_plan: no plan for these arguments");
+    *launches = p.launches;
+    *outputs_per_launch = p.outputs_per_launch;
+    return SR_OK;
+}
+int sr_lincomb_index_dev(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                         const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n, void *stream) {
+    if (int rc = check_lincomb_index(c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n)) return rc;
+    const Call call(c, stream);
+    return dev_lincomb_index(c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n, call.st);
+}
+int sr_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                     const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n) {
+    if (int rc = check_lincomb_index(c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n)) return rc;
+    if (n == 0) return SR_OK;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8, ob = (n * w + 15) & ~(size_t)15;
+    // HOST_0: the stored parts of the tables, one behind the other on 16-byte boundaries; HOST_1: the outputs; HOST_2: the
+    // coefficients; HOST_3: the stored parts of the index arrays, copied as they are
+    size_t off[SR_LINCOMB_MAX_TABLES], total = 0, coff[SR_LINCOMB_MAX_INDEX_COLUMNS], ctotal = 0;
+    for (int k = 0; k < n_tables; k++) {
+        off[k] = total;
+        total += ((n_evals ? n_evals[k] : n) * w + 15) & ~(size_t)15;
+    }
+    for (int j = 0; j < n_index; j++) {
+        coff[j] = ctotal;
+        ctotal += 16 + (((columns[j].values ? columns[j].n_evals * 8 : 0) + 15) & ~(size_t)15);  // never empty: a stored column keeps a non-null pointer
+    }
+    return staged(c, {{nullptr, nullptr, total}, {nullptr, nullptr, ob * n_outputs}, {coef, nullptr, (size_t)n_outputs * (n_tables + n_index + 1) * w},
+                      {nullptr, nullptr, ctotal}},
+                  [&](void *const *d) -> int {
+                      const uint64_t *dt[SR_LINCOMB_MAX_TABLES];
+                      uint64_t *dout[SR_LINCOMB_MAX_OUTPUTS];
+                      sr_index_column dc[SR_LINCOMB_MAX_INDEX_COLUMNS];
+                      for (int k = 0; k < n_tables; k++) {
+                          dt[k] = (const uint64_t *)((char *)d[0] + off[k]);
+                          const size_t b = (n_evals ? n_evals[k] : n) * w;
+                          if (b) HIP_TRY(hipMemcpyAsync((void *)dt[k], tables[k], b, hipMemcpyHostToDevice, c->stream));
+                      }
+                      for (int j = 0; j < n_index; j++) {
+                          dc[j] = columns[j];
+                          if (!columns[j].values) continue;
+                          dc[j].values = (const uint64_t *)((char *)d[3] + coff[j]);
+                          const size_t b = columns[j].n_evals * 8;
+                          if (b) HIP_TRY(hipMemcpyAsync((void *)dc[j].values, columns[j].values, b, hipMemcpyHostToDevice, c->stream));
+                      }
+                      for (int m = 0; m < n_outputs; m++) dout[m] = (uint64_t *)((char *)d[1] + ob * m);
+                      if (int r = dev_lincomb_index(c, dout, n_outputs, dt, n_evals, n_tables, dc, n_index, (const uint64_t *)d[2], uses, n, c->stream))
+                          return r;
+                      for (int m = 0; m < n_outputs; m++) HIP_TRY(hipMemcpyAsync(outs[m], dout[m], n * w, hipMemcpyDeviceToHost, c->stream));
+                      return SR_OK;
+                  });
+}
+int sr_index_count_dev(sr_ctx *c, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins, void *stream) {
+    if (int rc = check_index_count(c, counts, idx, n, n_bins)) return rc;
+    const Call call(c, stream);
+    return dev_index_count(c, counts, idx, n, n_bins, call.st);
+}
+int sr_index_count(sr_ctx *c, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins) {
+    if (int rc = check_index_count(c, counts, idx, n, n_bins)) return rc;
+    for (size_t i = 0; i < n; i++)
+        if (idx[i] >= n_bins) return fail(SR_E_INVALID, "index_count: an index is not below n_bins");
+    if (n_bins == 0) return SR_OK;
+    const Call call(c);
+    return staged(c, {{idx, nullptr, n * 8}, {nullptr, counts, n_bins * 8}},
+                  [&](void *const *d) { return dev_index_count(c, (uint64_t *)d[1], (const uint64_t *)d[0], n, n_bins, c->stream); });
 }
 int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches) {
     return round_plan_entry(kMleRound, ring, log2_degree, num_vars, n_tables, 0, 0, mode, work_elems, launches);

@@ -1,4 +1,5 @@
-"""Permutation and lookup checks end to end on device-resident tables: the leaves (sr_lincomb_dev, lincomb.py), the layered circuits
+"""Permutation and lookup checks end to end on device-resident tables: the leaves (sr_lincomb_dev, lincomb.py; from integer columns
+sr_lincomb_index_dev, index_columns.py), the multiplicities of a lookup (sr_index_count_dev), the layered circuits
 (ProductTree, FractionTree) and their layer claims (EqSumCheck).  Thin builders over those calls; nothing here computes on the host
 except the comparison of two root elements.
 
@@ -9,6 +10,7 @@ except the comparison of two root elements.
 """
 from .frac_tree import FractionTree
 from .grand_product import ProductTree
+from .index_columns import IndexColumn, _column, _one, from_u64_dev, index_count_dev, lincomb_index_dev
 from .lincomb import lincomb_dev
 from .rings import MLE_TRAILING, RingError
 
@@ -61,13 +63,58 @@ def permutation_leaves(ring, f, ident, sigma, beta, gamma, stream=None, num=None
     return num, den
 
 
-def _one(ring, like):
-    """the ring's one in CRT/NTT form on the device of `like`: what sr_product_batch returns for no element"""
+def fingerprint_indexed(ring, tables, columns, coeffs, const=None, n=None, stream=None, out=None):
+    """fingerprint() with integer columns beside the tables: sum_k coeffs[k] * tables[k] + sum_j coeffs[K + j] * R::from(columns[j])
+    (+ const) in one pass (sr_lincomb_index_dev).  columns: IndexColumn or u64 tensors; n: the rows, needed when there is no table
+    and no stored column to take it from."""
     import torch
 
-    out = torch.empty(ring.words_per_elem, dtype=like.dtype, device=like.device)
-    ring.product_dev(out, like[:0])
+    w, K = ring.words_per_elem, len(tables)
+    cols = [_column(c) for c in columns]
+    if n is None:
+        n = ring._batch_of(tables[0].numel()) if tables else max([c.n_evals for c in cols if not c.is_progression], default=None)
+    if n is None:
+        raise RingError("fingerprint_indexed: n is needed when every input is a progression")
+    if any(t.numel() != n * w for t in tables):
+        raise RingError("fingerprint_indexed: the tables differ in length")
+    T = K + len(cols)
+    if coeffs.numel() != T * w or (const is not None and const.numel() != w):
+        raise RingError("fingerprint_indexed: one coefficient per table and column, and a constant of one ring element")
+    rows = torch.cat([coeffs.reshape(-1), const.reshape(-1) if const is not None else coeffs.new_zeros(w)])
+    if out is None:
+        out = torch.empty(n * w, dtype=coeffs.dtype, device=coeffs.device)
+    if stream is not None:
+        rows.record_stream(stream)
+        out.record_stream(stream)
+    mask = (1 << T) - 1 | (1 << T if const is not None else 0)
+    lincomb_index_dev(ring, [out], list(tables), cols, rows, [mask], n, None, stream)
     return out
+
+
+def permutation_leaves_indexed(ring, f, sigma_idx, beta, gamma, id_start=0, stream=None, num=None, den=None):
+    """permutation_leaves() with id and sigma as integers: (num, den) = (beta + f + gamma R::from(id_start + e), beta + f + gamma
+    R::from(sigma_idx[e])) from ONE call with K = 1, J = 2, M = 2.  id is a progression and reads nothing; sigma_idx is a tensor of n
+    u64.  Per wire column c of 2^v rows, id_start = c 2^v."""
+    import torch
+
+    w = ring.words_per_elem
+    n = ring._batch_of(f.numel())
+    if sigma_idx.numel() != n:
+        raise RingError("permutation_leaves_indexed: sigma_idx holds one integer per row of f")
+    if beta.numel() != w or gamma.numel() != w:
+        raise RingError("permutation_leaves_indexed: beta and gamma are one ring element each")
+    one = _one(ring, f)
+    g, b = gamma.reshape(-1), beta.reshape(-1)
+    rows = torch.cat([one, g, g, b, one, g, g, b])   # rows (f, id, sigma, const); the entry a mask drops is never read
+    if num is None:
+        num = torch.empty_like(f)
+    if den is None:
+        den = torch.empty_like(f)
+    if stream is not None:
+        for t in (rows, num, den):
+            t.record_stream(stream)
+    lincomb_index_dev(ring, [num, den], [f], [IndexColumn(start=id_start), IndexColumn(sigma_idx)], rows, [0b1011, 0b1101], n, None, stream)
+    return num, den
 
 
 def _same(a, b):
@@ -107,6 +154,16 @@ class LookupCheck:
         self.stream = stream
         self.witness = FractionTree(ring, None, witness_q, num_vars_w, n_w, MLE_TRAILING, stream)
         self.table = FractionTree(ring, multiplicities, table_q, num_vars_t, n_t, MLE_TRAILING, stream)
+
+    @classmethod
+    def from_indices(cls, ring, witness_q, table_q, indices, num_vars_w, num_vars_t, n_w=None, n_t=None, stream=None):
+        """The check with its multiplicities counted on the device: indices[i] (u64, one per stored witness row) is the table row that
+        witness row i was taken from; the numerators of the table side are R::from(count[j]) (sr_index_count_dev, then
+        from_u64_dev).  An index at or beyond the table's stored rows is skipped and counted (ring.spmv_bad_index_count)."""
+        rows_t = ring._batch_of(table_q.numel()) if n_t is None else int(n_t)
+        counts = index_count_dev(ring, indices, rows_t, stream=stream)
+        mult = from_u64_dev(ring, counts, rows_t, stream=stream)
+        return cls(ring, witness_q, table_q, mult, num_vars_w, num_vars_t, n_w, n_t, stream)
 
     def roots(self):
         """((P_w, Q_w), (P_t, Q_t))"""
