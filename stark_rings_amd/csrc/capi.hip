@@ -1058,6 +1058,12 @@ int check(const sr_ctx *c, std::initializer_list<const void *> bufs, size_t n_el
         if (!p) return fail(SR_E_INVALID, "null buffer");
     return check_count(c, n_elems, per_elem);
 }
+// the ring and degree checks of every *_plan entry point and of sr_ctx_create_ex: host arithmetic, no context
+int check_plan_ring(int ring, int log2_degree) {
+    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    return SR_OK;
+}
 
 // ---- per-ring device dispatch (pow2 rings and the reference-native small rings) --------------
 int lanes_autoselect(sr_ctx *c, size_t batch);  // sr_plan.lanes = 0: measure once which plan this process's queues favour (below)
@@ -1596,24 +1602,52 @@ int check_mle(sr_ctx *c, const void *out, const void *evals, size_t n_evals, siz
     return check_count(c, p.work_elems);
 }
 
-// ---- sum-check round messages (csrc/sumcheck.hpp, sumcheck_fold.hpp, sumcheck_vpoly.hpp, sumcheck_vpoly_fold.hpp): every launch under
-// K_POINTWISE, nothing allocated, no context scratch.  The four families share the ring dispatch, the table collector and the argument checks.
+// ---- sum-check round messages (csrc/sumcheck.hpp, sumcheck_fold.hpp, sumcheck_vpoly.hpp, sumcheck_vpoly_fold.hpp, sumcheck_weighted.hpp,
+// range_check.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch.  Seven families and one record of operands
+// (RoundCall); the argument check, the aliasing rule, the launches and (with the host-pointer entry points, below) the staging each
+// exist once and read that record.
 struct RoundFamily {
     const char *name;  // the prefix of every message
     int max_tables;
-    bool terms, fold;  // a sum of products (n_terms, degree); a fold as well (an order, no SR_MLE_ROUND_SUM, two variables)
+    bool terms, fold;       // a sum of products (n_terms, degree); a fold as well (an order, no SR_MLE_ROUND_SUM, two variables)
     bool weighted = false;  // a per-pair weight (csrc/sumcheck_weighted.hpp): an order, no SR_MLE_ROUND_SUM
+    bool range = false;     // a bound in place of terms and one coefficient per table (csrc/range_check.hpp); d_coeffs may alias a table
+    // log2 of the weights' element count: one per pair of the tables the message is over (of a fold: the folded ones)
+    size_t weight_log2(size_t num_vars) const { return num_vars - (fold ? 2 : 1); }
 };
 const RoundFamily kMleRound{"mle_round", SR_MLE_ROUND_MAX_TABLES, false, false}, kVpolyRound{"vpoly_round", SR_VPOLY_MAX_TABLES, true, false},
     kMleRoundFold{"mle_round_fold", SR_MLE_ROUND_MAX_TABLES, false, true}, kVpolyRoundFold{"vpoly_round_fold", SR_VPOLY_MAX_TABLES, true, true},
-    kVpolyWround{"vpoly_wround", SR_VPOLY_MAX_TABLES, true, false, true}, kVpolyWroundFold{"vpoly_wround_fold", SR_VPOLY_MAX_TABLES, true, true, true};
+    kVpolyWround{"vpoly_wround", SR_VPOLY_MAX_TABLES, true, false, true}, kVpolyWroundFold{"vpoly_wround_fold", SR_VPOLY_MAX_TABLES, true, true, true},
+    kRangeWround{"range_wround", SR_RANGE_MAX_TABLES, false, false, true, true};
+// Every operand of a round call.  The first seven exist in every family; an operand that a family does not have stays null (0).
+struct RoundCall {
+    const RoundFamily &f;
+    uint64_t *out;
+    const uint64_t *const *tables;
+    const size_t *n_evals;
+    int n_tables;
+    size_t num_vars;
+    int mode;                               // an order where the family takes no SR_MLE_ROUND_SUM
+    uint64_t *const *out_tables = nullptr;  // folds: the folded tables, the elements written to each, the challenge
+    size_t *n_evals_out = nullptr;
+    const uint64_t *r = nullptr;
+    const uint64_t *weights = nullptr;      // weighted: 2^weight_log2 elements
+    const sr_vpoly_term *terms = nullptr;   // sums of products
+    int n_terms = 0;
+    int bound = 0;                          // range
+    const uint64_t *coef = nullptr;         // n_coef() elements, or null for one() everywhere
+    uint64_t *work = nullptr;               // the *_evals_dev forms: the caller's workspace
+    size_t work_elems = 0;
+    sr::sumcheck::Plan plan{};              // check_round sets it
+    int n_coef() const { return f.range ? n_tables : n_terms; }
+};
 extern "C++" {
 template <class T> struct FamilyType {
     using type = T;
 };
-// fn(the family type of the context's ring, its constants) enqueues the launches of a call; `what` opens the message of a failed launch
+// fn(the family type of the context's ring, its constants) enqueues the launches of a call of family f
 template <class Fn>
-int round_dispatch(sr_ctx *c, hipStream_t st, const char *what, Fn fn) {
+int round_dispatch(sr_ctx *c, hipStream_t st, const RoundFamily &f, Fn fn) {
     ProfScope ps(c, st, K_POINTWISE);
     const sr::sumcheck::NoConsts none;
     hipError_t e;
@@ -1625,293 +1659,212 @@ int round_dispatch(sr_ctx *c, hipStream_t st, const char *what, Fn fn) {
         case SR_RING_BABYBEAR_72: e = fn(FamilyType<sr::SlotB72>{}, c->small); break;
         default: e = fn(FamilyType<sr::SlotFrog>{}, c->frog); break;
     }
-    return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-}
-// the tables of a call by value; returns the bits of every table pointer (for the 16-byte alignment test)
-template <class TB>
-uintptr_t collect_tables(TB *tb, const uint64_t *const *tables, const size_t *n_evals, int n_tables) {
-    uintptr_t bits = 0;
-    for (int j = 0; j < n_tables; j++) {
-        tb->p[j] = tables[j];
-        tb->n[j] = n_evals[j];
-        bits |= (uintptr_t)tables[j];
-    }
-    return bits;
+    if (e == hipSuccess) return SR_OK;
+    std::string what(f.name);  // "mle round fold launch: ..."
+    for (char &ch : what) ch = ch == '_' ? ' ' : ch;
+    return fail(SR_E_HIP, what + " launch: " + hipGetErrorString(e));
 }
 }  // extern "C++"
-int dev_mle_round(sr_ctx *c, const sr::sumcheck::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
-                  int n_tables, size_t num_vars, uint64_t *work, hipStream_t st) {
-    sr::sumcheck::Tables tb{};
-    const uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (p.groups > 1 ? (uintptr_t)work : 0);
-    return round_dispatch(c, st, "mle round", [&](auto t, const auto &kc) {
-        return sr::sumcheck::launch<typename decltype(t)::type>(kc, p, mode, out, tb, n_tables, num_vars, c->k, (bits & 15u) == 0, work, st);
-    });
-}
-int dev_vpoly_round(sr_ctx *c, const sr::vpoly::Plan &p, int mode, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals,
-                    int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, uint64_t *work, hipStream_t st) {
-    sr::vpoly::Tables tb{};
-    sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
-    const uintptr_t bits =
-        collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)coef | (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int k = 0; k < n_terms; k++) {
-        tm[k].n_factors = terms[k].n_factors;
-        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
-    }
-    return round_dispatch(c, st, "vpoly round", [&](auto t, const auto &kc) {
-        return sr::vpoly::launch<typename decltype(t)::type>(kc, p, mode, out, tb, n_tables, tm, n_terms, coef, num_vars, c->k, (bits & 15u) == 0,
-                                                             work, st);
-    });
-}
-// fold at the challenge and the next round's message in one pass
-int dev_mle_round_fold(sr_ctx *c, const sr::sumcheck_fold::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
-                       const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, uint64_t *work,
-                       hipStream_t st) {
-    sr::sumcheck::Tables tb{};
-    sr::sumcheck_fold::Folded fo{};
-    uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)r | (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int j = 0; j < n_tables; j++) {
-        fo.p[j] = out_tables[j];
-        bits |= (uintptr_t)out_tables[j];
-    }
-    return round_dispatch(c, st, "mle round fold", [&](auto t, const auto &kc) {
-        return sr::sumcheck_fold::launch<typename decltype(t)::type>(kc, p, order, out, tb, fo, r, n_tables, num_vars, n_out, c->k, (bits & 15u) == 0,
-                                                                     work, st);
-    });
-}
-// a sum of products: fold every distinct table slot at the challenge and the next round's message in one pass
-int dev_vpoly_round_fold(sr_ctx *c, const sr::vpoly_fold::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
-                         const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
-                         const uint64_t *coef, size_t num_vars, const uint64_t *r, uint64_t *work, hipStream_t st) {
+// The launches of a checked call on `st`.  aligned: every operand the kernels touch starts on a 16-byte boundary (the workspace only
+// where the plan has more than one record group to sum).
+int dev_round(sr_ctx *c, const RoundCall &a, hipStream_t st) {
+    const RoundFamily &f = a.f;
+    const sr::sumcheck::Plan &p = a.plan;
+    const int nt = a.n_tables, k = c->k;
     sr::vpoly::Tables tb{};
     sr::vpoly_fold::Folded fo{};
     sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
-    uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)r | (uintptr_t)coef | (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int j = 0; j < n_tables; j++) {
-        fo.p[j] = out_tables[j];
-        bits |= (uintptr_t)out_tables[j];
+    uintptr_t bits = (uintptr_t)a.out | (uintptr_t)a.weights | (uintptr_t)a.coef | (uintptr_t)a.r | (p.groups > 1 ? (uintptr_t)a.work : 0);
+    for (int j = 0; j < nt; j++) {
+        tb.p[j] = a.tables[j];
+        tb.n[j] = a.n_evals[j];
+        bits |= (uintptr_t)a.tables[j];
+        if (!f.fold) continue;
+        fo.p[j] = a.out_tables[j];
+        bits |= (uintptr_t)a.out_tables[j];
     }
-    for (int k = 0; k < n_terms; k++) {
-        tm[k].n_factors = terms[k].n_factors;
-        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
+    for (int i = 0; i < a.n_terms; i++) {
+        tm[i].n_factors = a.terms[i].n_factors;
+        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[i].table[s] = a.terms[i].table[s];
     }
-    return round_dispatch(c, st, "vpoly round fold", [&](auto t, const auto &kc) {
-        return sr::vpoly_fold::launch<typename decltype(t)::type>(kc, p, order, out, tb, fo, r, n_tables, tm, n_terms, coef, num_vars, n_out, c->k,
-                                                                  (bits & 15u) == 0, work, st);
-    });
-}
-// the weighted siblings of the two calls above (csrc/sumcheck_weighted.hpp): weights holds one element per pair
-int dev_vpoly_wround(sr_ctx *c, const sr::wsumcheck::Plan &p, int order, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables,
-                     const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars,
-                     uint64_t *work, hipStream_t st) {
-    sr::vpoly::Tables tb{};
-    sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
-    const uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)coef |
-                           (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int k = 0; k < n_terms; k++) {
-        tm[k].n_factors = terms[k].n_factors;
-        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
+    const bool aligned = (bits & 15u) == 0;
+    // a product of at most four tables takes the narrower records of sumcheck.hpp
+    const bool product = !f.terms && !f.range;
+    sr::sumcheck::Tables tb4{};
+    sr::sumcheck_fold::Folded fo4{};
+    for (int j = 0; product && j < nt; j++) {
+        tb4.p[j] = tb.p[j];
+        tb4.n[j] = tb.n[j];
+        fo4.p[j] = fo.p[j];
     }
-    return round_dispatch(c, st, "vpoly wround", [&](auto t, const auto &kc) {
-        return sr::wsumcheck::launch<typename decltype(t)::type>(kc, p, order, out, weights, tb, n_tables, tm, n_terms, coef, num_vars, c->k,
-                                                                 (bits & 15u) == 0, work, st);
-    });
-}
-int dev_vpoly_wround_fold(sr_ctx *c, const sr::wsumcheck::Plan &p, int order, uint64_t *out, uint64_t *const *out_tables, size_t *n_out,
-                          const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
-                          int n_terms, const uint64_t *coef, size_t num_vars, const uint64_t *r, uint64_t *work, hipStream_t st) {
-    sr::vpoly::Tables tb{};
-    sr::vpoly_fold::Folded fo{};
-    sr::vpoly::Term tm[SR_VPOLY_MAX_TERMS];
-    uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)r | (uintptr_t)coef |
-                     (p.groups > 1 ? (uintptr_t)work : 0);
-    for (int j = 0; j < n_tables; j++) {
-        fo.p[j] = out_tables[j];
-        bits |= (uintptr_t)out_tables[j];
-    }
-    for (int k = 0; k < n_terms; k++) {
-        tm[k].n_factors = terms[k].n_factors;
-        for (int s = 0; s < SR_VPOLY_MAX_FACTORS; s++) tm[k].table[s] = terms[k].table[s];
-    }
-    return round_dispatch(c, st, "vpoly wround fold", [&](auto t, const auto &kc) {
-        return sr::wsumcheck::launch_fold<typename decltype(t)::type>(kc, p, order, out, weights, tb, fo, r, n_tables, tm, n_terms, coef, num_vars,
-                                                                      n_out, c->k, (bits & 15u) == 0, work, st);
+    // One round_dispatch per header's launch, in the order the families were written: a launch is instantiated for every ring where
+    // its dispatch stands, and that order is the order of the kernels in the code object.
+    if (product && !f.fold)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::sumcheck::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, tb4, nt, a.num_vars, k, aligned, a.work, st);
+        });
+    if (f.terms && !f.weighted && !f.fold)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::vpoly::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, tb, nt, tm, a.n_terms, a.coef, a.num_vars, k, aligned, a.work,
+                                                                 st);
+        });
+    if (product)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::sumcheck_fold::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, tb4, fo4, a.r, nt, a.num_vars, a.n_evals_out, k, aligned,
+                                                                         a.work, st);
+        });
+    if (!f.weighted)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::vpoly_fold::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, tb, fo, a.r, nt, tm, a.n_terms, a.coef, a.num_vars,
+                                                                      a.n_evals_out, k, aligned, a.work, st);
+        });
+    if (!f.range && !f.fold)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::wsumcheck::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, nt, tm, a.n_terms, a.coef, a.num_vars, k,
+                                                                     aligned, a.work, st);
+        });
+    if (!f.range)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::wsumcheck::launch_fold<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, fo, a.r, nt, tm, a.n_terms, a.coef,
+                                                                          a.num_vars, a.n_evals_out, k, aligned, a.work, st);
+        });
+    return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+        return sr::range::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, nt, a.bound, a.coef, a.num_vars, k, aligned, a.work,
+                                                             st);
     });
 }
 // a refusal of family f: the message is assembled here, on the failing path only
 int refuse(const RoundFamily &f, const std::string &what) { return fail(SR_E_INVALID, std::string(f.name) + ": " + what); }
-// the shape checks the *_plan call and the two forms of the *_evals call of a family share (n_terms, degree: families with terms)
-int round_plan_for(const RoundFamily &f, int ring, int k, size_t num_vars, int n_tables, int n_terms, int degree, int mode, sr::sumcheck::Plan *p) {
+// the shape checks the *_plan call and the two forms of the *_evals call of a family share (n_terms, degree: families with terms;
+// bound: the range check)
+int round_plan_for(const RoundFamily &f, int ring, int k, size_t num_vars, int n_tables, int n_terms, int degree, int bound, int mode,
+                   sr::sumcheck::Plan *p) {
+    const bool ordered = f.fold || f.weighted;
     if (n_tables < 1 || n_tables > f.max_tables) return refuse(f, "n_tables must be 1 .. " + std::to_string(f.max_tables));
     if (f.terms) {
         if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return refuse(f, "n_terms must be 1 .. 8");
         if (degree < 1 || degree > SR_VPOLY_MAX_FACTORS) return refuse(f, "degree (the largest n_factors) must be 1 .. 4");
     }
-    if (f.weighted && !f.fold && mode == SR_MLE_ROUND_SUM)
+    if (f.range && (bound < 2 || bound > SR_RANGE_MAX_BOUND)) return refuse(f, "bound must be 2 .. " + std::to_string(SR_RANGE_MAX_BOUND));
+    if (f.weighted && !f.fold && !f.range && mode == SR_MLE_ROUND_SUM)
         return refuse(f, "SR_MLE_ROUND_SUM takes no weights (a weight of a plain sum is just a table)");
-    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && (f.fold || f.weighted || mode != SR_MLE_ROUND_SUM))
-        return refuse(f, f.fold || f.weighted ? "unknown order" : "unknown mode");
+    if (mode != SR_MLE_LEADING && mode != SR_MLE_TRAILING && (ordered || mode != SR_MLE_ROUND_SUM))
+        return refuse(f, ordered ? "unknown order" : "unknown mode");
     if (num_vars >= 48) return refuse(f, "num_vars must be below 48");
     if (f.fold && num_vars < 2) return refuse(f, "num_vars >= 2 (the folded tables need a variable for the next round)");
-    if (num_vars == 0 && mode != SR_MLE_ROUND_SUM) return refuse(f, "a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
-    const bool ok = f.weighted ? (f.fold ? sr::wsumcheck::fold_plan(ring, k, num_vars, n_tables, degree, mode, p)
-                                         : sr::wsumcheck::plan(ring, k, num_vars, n_tables, degree, mode, p))
-                    : f.fold  ? (f.terms ? sr::vpoly_fold::plan(ring, k, num_vars, n_tables, degree, mode, p)
-                                         : sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, mode, p))
-                    : f.terms ? sr::vpoly::plan(ring, k, num_vars, n_tables, degree, mode, p)
-                              : sr::sumcheck::plan(ring, k, num_vars, n_tables, mode, p);
+    if (num_vars == 0 && mode != SR_MLE_ROUND_SUM)
+        return refuse(f, f.range ? "a round needs num_vars >= 1" : "a round needs num_vars >= 1 (only SR_MLE_ROUND_SUM takes 0)");
+    const bool ok = f.range      ? sr::range::plan(ring, k, num_vars, n_tables, bound, mode, p)
+                    : f.weighted ? (f.fold ? sr::wsumcheck::fold_plan(ring, k, num_vars, n_tables, degree, mode, p)
+                                           : sr::wsumcheck::plan(ring, k, num_vars, n_tables, degree, mode, p))
+                    : f.fold     ? (f.terms ? sr::vpoly_fold::plan(ring, k, num_vars, n_tables, degree, mode, p)
+                                            : sr::sumcheck_fold::plan(ring, k, num_vars, n_tables, mode, p))
+                    : f.terms    ? sr::vpoly::plan(ring, k, num_vars, n_tables, degree, mode, p)
+                                 : sr::sumcheck::plan(ring, k, num_vars, n_tables, mode, p);
     return ok ? (int)SR_OK : refuse(f, "no plan for these arguments");
 }
-// the body of the four *_plan entry points
-int round_plan_entry(const RoundFamily &f, int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int mode,
+// the body of the seven *_plan entry points
+int round_plan_entry(const RoundFamily &f, int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int bound, int mode,
                      size_t *work_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
     if (!work_elems || !launches) return fail(SR_E_INVALID, std::string(f.name) + "_plan: null result pointer");
     sr::sumcheck::Plan p;
-    if (int rc = round_plan_for(f, ring, log2_degree, num_vars, n_tables, n_terms, degree, mode, &p)) return rc;
+    if (int rc = round_plan_for(f, ring, log2_degree, num_vars, n_tables, n_terms, degree, bound, mode, &p)) return rc;
     *work_elems = p.work_elems;
     *launches = p.launches;
     return SR_OK;
-}
-// the per-table checks of the four families; out_tables: the fold's outputs, null otherwise
-int check_round_tables(sr_ctx *c, const RoundFamily &f, const uint64_t *const *tables, uint64_t *const *out_tables, const size_t *n_evals,
-                       int n_tables, size_t num_vars) {
-    for (int j = 0; j < n_tables; j++) {
-        if (n_evals[j] > (size_t)1 << num_vars) return refuse(f, "n_evals exceeds 2^num_vars");
-        if (n_evals[j] && (!tables[j] || (out_tables && !out_tables[j]))) return refuse(f, "null pointer (a table)");
-        if (int rc = check_count(c, n_evals[j])) return rc;
-    }
-    return SR_OK;
-}
-// the argument checks the two forms of sr_mle_round_evals share
-int check_mle_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, int mode,
-                    sr::sumcheck::Plan *p) {
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !tables || !n_evals) return refuse(kMleRound, "null pointer");
-    if (int rc = round_plan_for(kMleRound, c->ring, c->k, num_vars, n_tables, 0, 0, mode, p)) return rc;
-    return check_round_tables(c, kMleRound, tables, nullptr, n_evals, n_tables, num_vars);
-}
-// the argument checks of the two families with terms (f: kVpolyRound, or kVpolyRoundFold with its outputs and r)
-int check_vpoly_terms(sr_ctx *c, const RoundFamily &f, const void *out, uint64_t *const *out_tables, const size_t *n_out, const void *r,
-                      const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, size_t num_vars,
-                      int mode, sr::vpoly::Plan *p) {
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !tables || !n_evals || !terms || (f.fold && (!out_tables || !n_out || !r))) return refuse(f, "null pointer");
-    if (n_tables < 1 || n_tables > f.max_tables) return refuse(f, "n_tables must be 1 .. " + std::to_string(f.max_tables));
-    if (n_terms < 1 || n_terms > SR_VPOLY_MAX_TERMS) return refuse(f, "n_terms must be 1 .. 8");
-    int degree = 0;
-    unsigned used = 0;
-    for (int k = 0; k < n_terms; k++) {
-        if (terms[k].n_factors < 1 || terms[k].n_factors > SR_VPOLY_MAX_FACTORS)
-            return refuse(f, "n_factors must be 1 .. 4 (term " + std::to_string(k) + ")");
-        degree = terms[k].n_factors > degree ? terms[k].n_factors : degree;
-        for (int s = 0; s < terms[k].n_factors; s++) {
-            if (terms[k].table[s] < 0 || terms[k].table[s] >= n_tables)
-                return refuse(f, "table index outside 0 .. n_tables - 1 (term " + std::to_string(k) + ")");
-            used |= 1u << terms[k].table[s];
-        }
-    }
-    if (used != (1u << n_tables) - 1) return refuse(f, "a table that no term uses");
-    if (int rc = round_plan_for(f, c->ring, c->k, num_vars, n_tables, n_terms, degree, mode, p)) return rc;
-    return check_round_tables(c, f, tables, f.fold ? out_tables : nullptr, n_evals, n_tables, num_vars);
-}
-// the argument checks the two forms of sr_vpoly_round_evals share
-int check_vpoly_round(sr_ctx *c, const void *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
-                      int n_terms, size_t num_vars, int mode, sr::vpoly::Plan *p) {
-    return check_vpoly_terms(c, kVpolyRound, out, nullptr, nullptr, nullptr, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, p);
-}
-// the argument checks the two forms of sr_vpoly_round_fold_evals share
-int check_vpoly_round_fold(sr_ctx *c, const void *out, uint64_t *const *out_tables, const size_t *n_out, const uint64_t *const *tables,
-                           const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, size_t num_vars, const void *r, int order,
-                           sr::vpoly_fold::Plan *p) {
-    return check_vpoly_terms(c, kVpolyRoundFold, out, out_tables, n_out, r, tables, n_evals, n_tables, terms, n_terms, num_vars, order, p);
-}
-// the argument checks the two forms of sr_mle_round_fold_evals share
-int check_mle_round_fold(sr_ctx *c, const void *out, uint64_t *const *out_tables, const size_t *n_out, const uint64_t *const *tables,
-                         const size_t *n_evals, int n_tables, size_t num_vars, const void *r, int order, sr::sumcheck_fold::Plan *p) {
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !out_tables || !n_out || !tables || !n_evals || !r) return refuse(kMleRoundFold, "null pointer");
-    if (int rc = round_plan_for(kMleRoundFold, c->ring, c->k, num_vars, n_tables, 0, 0, order, p)) return rc;
-    return check_round_tables(c, kMleRoundFold, tables, out_tables, n_evals, n_tables, num_vars);
-}
-// the workspace of a *_evals_dev call
-int check_round_work(const RoundFamily &f, const sr::sumcheck::Plan &p, const uint64_t *work, size_t work_elems) {
-    if (p.work_elems && !work) return refuse(f, "null pointer (d_work)");
-    if (work_elems < p.work_elems)
-        return refuse(f, "workspace too small (sr_" + std::string(f.name) + "_plan asks for " + std::to_string(p.work_elems) + " elements)");
-    return SR_OK;
-}
-// range-check rounds (csrc/range_check.hpp): the family for the messages and the workspace check, the shared argument checks of the two
-// forms of sr_range_wround_evals, and the launches
-const RoundFamily kRangeWround{"range_wround", SR_RANGE_MAX_TABLES, false, false, true};
-int range_plan_for(int ring, int k, size_t num_vars, int n_tables, int bound, int order, sr::range::Plan *p) {
-    const RoundFamily &f = kRangeWround;
-    if (n_tables < 1 || n_tables > SR_RANGE_MAX_TABLES) return refuse(f, "n_tables must be 1 .. " + std::to_string(SR_RANGE_MAX_TABLES));
-    if (bound < 2 || bound > SR_RANGE_MAX_BOUND) return refuse(f, "bound must be 2 .. " + std::to_string(SR_RANGE_MAX_BOUND));
-    if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) return refuse(f, "unknown order");
-    if (num_vars >= 48) return refuse(f, "num_vars must be below 48");
-    if (num_vars == 0) return refuse(f, "a round needs num_vars >= 1");
-    return sr::range::plan(ring, k, num_vars, n_tables, bound, order, p) ? (int)SR_OK : refuse(f, "no plan for these arguments");
-}
-int check_range_wround(sr_ctx *c, const void *out, const void *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables, int bound,
-                       size_t num_vars, int order, sr::range::Plan *p) {
-    if (!weights) return refuse(kRangeWround, "null pointer (d_weights)");
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (!out || !tables || !n_evals) return refuse(kRangeWround, "null pointer");
-    if (int rc = range_plan_for(c->ring, c->k, num_vars, n_tables, bound, order, p)) return rc;
-    return check_round_tables(c, kRangeWround, tables, nullptr, n_evals, n_tables, num_vars);
-}
-int dev_range_wround(sr_ctx *c, const sr::range::Plan &p, int order, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables,
-                     const size_t *n_evals, int n_tables, int bound, const uint64_t *coef, size_t num_vars, uint64_t *work, hipStream_t st) {
-    sr::range::Tables tb{};
-    const uintptr_t bits = collect_tables(&tb, tables, n_evals, n_tables) | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)coef |
-                           (p.groups > 1 ? (uintptr_t)work : 0);
-    return round_dispatch(c, st, "range wround", [&](auto t, const auto &kc) {
-        return sr::range::launch<typename decltype(t)::type>(kc, p, order, out, weights, tb, n_tables, bound, coef, num_vars, c->k, (bits & 15u) == 0,
-                                                             work, st);
-    });
 }
 // elements the fold of a table of n stored elements writes
 size_t round_fold_n_out(size_t n, size_t num_vars, int order) {
     const size_t half = (size_t)1 << (num_vars - 1);
     return order == SR_MLE_LEADING ? (n + 1) / 2 : (n < half ? n : half);
 }
-
-// the aliasing rules of the two fold families: outputs overlap nothing but, in trailing order, their own input (coef, cw: the
-// coefficients of a sum of products and their bytes, or null and 0)
-int check_fold_overlaps(const RoundFamily &f, const sr::sumcheck::Plan &p, size_t w, const uint64_t *out, uint64_t *const *out_tables,
-                        const size_t *n_out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const uint64_t *coef, size_t cw,
-                        const uint64_t *r, int order, const uint64_t *work) {
-    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return refuse(f, "d_out overlaps d_work");
-    if (ranges_overlap(out, p.np_total * w, r, w)) return refuse(f, "d_out overlaps d_r");
-    if (ranges_overlap(work, p.work_elems * w, r, w)) return refuse(f, "d_work overlaps d_r");
-    if (ranges_overlap(out, p.np_total * w, coef, cw)) return refuse(f, "d_out overlaps d_coeffs");
-    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return refuse(f, "d_work overlaps d_coeffs");
-    if (ranges_overlap(r, w, coef, cw)) return refuse(f, "d_r overlaps d_coeffs");
-    for (int j = 0; j < n_tables; j++) {
-        if (ranges_overlap(coef, cw, tables[j], n_evals[j] * w)) return refuse(f, "d_coeffs overlaps a table");
-        if (ranges_overlap(coef, cw, out_tables[j], n_out[j] * w)) return refuse(f, "d_coeffs overlaps a folded table");
-        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return refuse(f, "d_out overlaps a table");
-        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return refuse(f, "d_work overlaps a table");
-        if (ranges_overlap(r, w, tables[j], n_evals[j] * w)) return refuse(f, "d_r overlaps a table");
-        if (ranges_overlap(out, p.np_total * w, out_tables[j], n_out[j] * w)) return refuse(f, "d_out overlaps a folded table");
-        if (ranges_overlap(work, p.work_elems * w, out_tables[j], n_out[j] * w))
-            return refuse(f, "d_work overlaps a folded table");
-        if (ranges_overlap(r, w, out_tables[j], n_out[j] * w)) return refuse(f, "d_r overlaps a folded table");
-        for (int i = 0; i < j; i++)
-            if (ranges_overlap(out_tables[i], n_out[i] * w, out_tables[j], n_out[j] * w))
-                return refuse(f, "two folded tables overlap");
-        for (int i = 0; i < n_tables; i++) {
-            if (!ranges_overlap(out_tables[j], n_out[j] * w, tables[i], n_evals[i] * w)) continue;
-            // in place: the table's own output only, trailing order only, and no other input may be that table (it would be folded twice)
-            if (order != SR_MLE_TRAILING || out_tables[j] != tables[j])
-                return refuse(f,
-                            "a folded table overlaps an input table (only a trailing-order fold may run in place, with "
-                            "d_out_tables[j] == d_tables[j])");
-            if (i != j) return refuse(f, "an input table that appears twice cannot be folded in place");
+// The aliasing rule of the *_evals_dev forms.  What a call writes -- d_out, d_work, every folded table -- overlaps no other operand,
+// another folded table included; the one exception is a trailing-order fold in place, d_out_tables[j] == d_tables[j], where that
+// table appears once among the inputs.  Of what a call only reads, d_r, d_coeffs and the tables are disjoint from each other, except
+// that tables may alias tables (and, in the range check, d_coeffs a table); d_weights may alias any of them.
+int check_round_aliasing(const sr_ctx *c, const RoundCall &a) {
+    const RoundFamily &f = a.f;
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    enum Kind { WRITTEN, FOLDED, READ, TABLE, WEIGHTS };  // a refusal names its two operands in this order
+    struct {
+        const void *p;
+        size_t bytes;
+        const char *name;
+        Kind kind;
+        int j;
+    } ops[5 + 2 * SR_VPOLY_MAX_TABLES];
+    int n = 0;
+    ops[n++] = {a.out, a.plan.np_total * w, "d_out", WRITTEN, 0};
+    ops[n++] = {a.work, a.plan.work_elems * w, "d_work", WRITTEN, 0};
+    ops[n++] = {a.r, a.r ? w : 0, "d_r", READ, 0};
+    ops[n++] = {a.coef, a.coef ? a.n_coef() * w : 0, "d_coeffs", READ, 0};
+    for (int j = 0; f.fold && j < a.n_tables; j++)
+        ops[n++] = {a.out_tables[j], round_fold_n_out(a.n_evals[j], a.num_vars, a.mode) * w, "a folded table", FOLDED, j};
+    for (int j = 0; j < a.n_tables; j++) ops[n++] = {a.tables[j], a.n_evals[j] * w, "a table", TABLE, j};
+    ops[n++] = {a.weights, a.weights ? w << f.weight_log2(a.num_vars) : 0, "d_weights", WEIGHTS, 0};
+    for (int x = 0; x < n; x++)
+        for (int y = x + 1; y < n; y++) {
+            const auto &p = ops[x], &q = ops[y];
+            if (!ranges_overlap(p.p, p.bytes, q.p, q.bytes)) continue;
+            if (p.kind == FOLDED && q.kind == FOLDED) return refuse(f, "two folded tables overlap");
+            if (p.kind == FOLDED && q.kind == TABLE) {
+                // in place: the table's own output only, trailing order only, and no other input may be that table (it would be folded twice)
+                if (a.mode != SR_MLE_TRAILING || p.p != a.tables[p.j])
+                    return refuse(f,
+                                  "a folded table overlaps an input table (only a trailing-order fold may run in place, with "
+                                  "d_out_tables[j] == d_tables[j])");
+                if (q.j != p.j) return refuse(f, "an input table that appears twice cannot be folded in place");
+                continue;
+            }
+            const bool written = p.kind <= FOLDED || q.kind == FOLDED;
+            const bool inputs = p.kind == READ && (q.kind == READ || (q.kind == TABLE && !f.range));
+            if (written || inputs) return refuse(f, std::string(p.name) + " overlaps " + q.name);
         }
-    }
     return SR_OK;
+}
+// The argument checks of every family.  dev: the *_evals_dev form, which names its weights d_weights (as both forms of the range check
+// do) and brings a workspace and device pointers that may alias.  Sets a.plan.
+int check_round(sr_ctx *c, RoundCall &a, bool dev) {
+    const RoundFamily &f = a.f;
+    if (f.weighted && !a.weights) return refuse(f, dev || f.range ? "null pointer (d_weights)" : "null pointer (weights)");
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!a.out || !a.tables || !a.n_evals || (f.terms && !a.terms) || (f.fold && (!a.out_tables || !a.n_evals_out || !a.r)))
+        return refuse(f, "null pointer");
+    int degree = 0;
+    if (f.terms) {  // the counts that bound the scan of the terms, ahead of round_plan_for
+        if (a.n_tables < 1 || a.n_tables > f.max_tables) return refuse(f, "n_tables must be 1 .. " + std::to_string(f.max_tables));
+        if (a.n_terms < 1 || a.n_terms > SR_VPOLY_MAX_TERMS) return refuse(f, "n_terms must be 1 .. 8");
+        unsigned used = 0;
+        for (int i = 0; i < a.n_terms; i++) {
+            const sr_vpoly_term &t = a.terms[i];
+            if (t.n_factors < 1 || t.n_factors > SR_VPOLY_MAX_FACTORS) return refuse(f, "n_factors must be 1 .. 4 (term " + std::to_string(i) + ")");
+            degree = t.n_factors > degree ? t.n_factors : degree;
+            for (int s = 0; s < t.n_factors; s++) {
+                if (t.table[s] < 0 || t.table[s] >= a.n_tables)
+                    return refuse(f, "table index outside 0 .. n_tables - 1 (term " + std::to_string(i) + ")");
+                used |= 1u << t.table[s];
+            }
+        }
+        if (used != (1u << a.n_tables) - 1) return refuse(f, "a table that no term uses");
+    }
+    if (int rc = round_plan_for(f, c->ring, c->k, a.num_vars, a.n_tables, a.n_terms, degree, a.bound, a.mode, &a.plan)) return rc;
+    for (int j = 0; j < a.n_tables; j++) {
+        if (a.n_evals[j] > (size_t)1 << a.num_vars) return refuse(f, "n_evals exceeds 2^num_vars");
+        if (a.n_evals[j] && (!a.tables[j] || (f.fold && !a.out_tables[j]))) return refuse(f, "null pointer (a table)");
+        if (int rc = check_count(c, a.n_evals[j])) return rc;
+    }
+    if (!dev) return SR_OK;
+    if (a.plan.work_elems && !a.work) return refuse(f, "null pointer (d_work)");
+    if (a.work_elems < a.plan.work_elems)
+        return refuse(f, "workspace too small (sr_" + std::string(f.name) + "_plan asks for " + std::to_string(a.plan.work_elems) + " elements)");
+    return check_round_aliasing(c, a);
+}
+// a *_evals_dev entry point: the checks, then the device guard, the mutex and the caller's stream, then the launches
+int round_dev(sr_ctx *c, RoundCall &a, void *stream) {
+    if (int rc = check_round(c, a, true)) return rc;
+    const Call call(c, stream);
+    return dev_round(c, a, call.st);
 }
 
 // ---- sparse multilinear extensions (csrc/sparse_mle.hpp): nothing allocated, no context scratch ----------------------------------
@@ -2063,12 +2016,6 @@ int dev_symm_recompose(sr_ctx *c, const sr::symm::RecomposePlan &p, uint64_t *ou
         default: e = sy::launch_slot_recompose<sr::SlotFrog>(c->frog, p, out, mat, powers, n, d, work, st); break;
     }
     return e == hipSuccess ? (int)SR_OK : fail(SR_E_HIP, std::string("symmetric recompose launch: ") + hipGetErrorString(e));
-}
-// the ring and degree checks of the two plan entry points
-int check_plan_ring(int ring, int log2_degree) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
-    return SR_OK;
 }
 int gram_plan_for(int ring, int k, size_t n, size_t m, sr::symm::GramPlan *p) {
     if (!sr::symm::gram_plan(ring, k, n, m, p)) return fail(SR_E_INVALID, "gram: n (n + 1) / 2 overflows or the grid exceeds one launch");
@@ -2286,43 +2233,6 @@ int dev_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t 
     }
     return SR_OK;
 }
-// the argument checks the two forms of sr_lincomb share; everything here is host arithmetic on the arguments
-int check_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
-                  const uint64_t *coef, const uint32_t *uses, size_t n) {
-    if (!c) return fail(SR_E_INVALID, "null context");
-    if (n_tables < 1 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb: n_tables outside 1 .. 16");
-    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb: n_outputs outside 1 .. 4");
-    if (!outs || !tables || !coef || !uses) return fail(SR_E_INVALID, "lincomb: null argument");
-    uint32_t any = 0;
-    for (int m = 0; m < n_outputs; m++) {
-        if (uses[m] == 0) return fail(SR_E_INVALID, "lincomb: an output with an empty mask");
-        if (uses[m] >> (n_tables + 1)) return fail(SR_E_INVALID, "lincomb: a mask bit above n_tables");
-        any |= uses[m];
-    }
-    for (int k = 0; k < n_tables; k++)
-        if (!((any >> k) & 1u)) return fail(SR_E_INVALID, "lincomb: a table that no output uses");
-    if (n >= (size_t)1 << 48) return fail(SR_E_INVALID, "lincomb: n must be below 2^48");
-    for (int k = 0; k < n_tables; k++)
-        if (n_evals && n_evals[k] > n) return fail(SR_E_INVALID, "lincomb: n_evals exceeds n");
-    for (int k = 0; k < n_tables; k++)
-        if (!tables[k]) return fail(SR_E_INVALID, "lincomb: null table");
-    for (int m = 0; m < n_outputs; m++)
-        if (!outs[m]) return fail(SR_E_INVALID, "lincomb: null output");
-    if (int rc = check_count(c, n)) return rc;  // everything above is decided without reading the context
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    for (int m = 0; m < n_outputs; m++) {
-        for (int j = 0; j < m; j++)
-            if (ranges_overlap(outs[m], n * w, outs[j], n * w)) return fail(SR_E_INVALID, "lincomb: two outputs overlap");
-        if (ranges_overlap(outs[m], n * w, coef, (size_t)n_outputs * (n_tables + 1) * w))
-            return fail(SR_E_INVALID, "lincomb: an output overlaps the coefficients");
-        for (int k = 0; k < n_tables; k++) {
-            if (!ranges_overlap(outs[m], n * w, tables[k], (n_evals ? n_evals[k] : n) * w)) continue;
-            if (outs[m] != tables[k]) return fail(SR_E_INVALID, "lincomb: an output overlaps a table");
-            if (n_outputs != 1) return fail(SR_E_INVALID, "lincomb: in place needs n_outputs == 1");
-        }
-    }
-    return SR_OK;
-}
 // ---- linear combinations with integer columns, multiplicities (csrc/lincomb_index.hpp): as above, nothing allocated -----------------
 // n_index == 0 is dev_lincomb, bit for bit
 int dev_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
@@ -2370,58 +2280,94 @@ int dev_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uin
     }
     return SR_OK;
 }
-// the argument checks the two forms of sr_lincomb_index share; everything here is host arithmetic on the arguments
-int check_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
-                        const sr_index_column *cols, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n) {
+// Which call the shared checks and the shared staging speak for.  sr_lincomb is sr_lincomb_index without index columns: its terms
+// are its tables, so there is at least one.
+struct LincombCall {
+    const char *name, *n_terms;  // the prefix of every message; what the message calls the term count
+    int min_tables;
+};
+const LincombCall kLincomb{"lincomb", "n_tables", 1}, kLincombIndex{"lincomb_index", "n_tables + n_index", 0};
+// entry: "" or "_plan"
+int refuse(const LincombCall &who, const char *entry, const std::string &what) {
+    return fail(SR_E_INVALID, std::string(who.name) + entry + ": " + what);
+}
+// the counts the *_plan call and the two forms of the call share
+int check_lincomb_counts(const LincombCall &who, const char *entry, int n_tables, int n_index, int n_outputs) {
+    if (n_tables < who.min_tables || n_tables > SR_LINCOMB_MAX_TABLES)
+        return refuse(who, entry, "n_tables outside " + std::to_string(who.min_tables) + " .. 16");
+    if (n_index < 0 || n_index > SR_LINCOMB_MAX_INDEX_COLUMNS) return refuse(who, entry, "n_index outside 0 .. 8");
+    if (n_tables + n_index < 1 || n_tables + n_index > SR_LINCOMB_MAX_TABLES) return refuse(who, entry, std::string(who.n_terms) + " outside 1 .. 16");
+    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return refuse(who, entry, "n_outputs outside 1 .. 4");
+    return SR_OK;
+}
+// the body of the two *_plan entry points
+int lincomb_plan_entry(const LincombCall &who, int ring, int log2_degree, int n_tables, int n_index, int n_outputs, int *launches,
+                       int *outputs_per_launch) {
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
+    if (!launches || !outputs_per_launch) return refuse(who, "_plan", "null result pointer");
+    if (int rc = check_lincomb_counts(who, "_plan", n_tables, n_index, n_outputs)) return rc;
+    sr::lincomb::Plan p;
+    if (!sr::lincomb_index::plan(ring, n_tables, n_index, n_outputs, &p)) return refuse(who, "_plan", "no plan for these arguments");
+    *launches = p.launches;
+    *outputs_per_launch = p.outputs_per_launch;
+    return SR_OK;
+}
+// the argument checks the two forms of sr_lincomb and of sr_lincomb_index share; everything here is host arithmetic on the arguments
+int check_lincomb_index(const LincombCall &who, sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables,
+                        const size_t *n_evals, int n_tables, const sr_index_column *cols, int n_index, const uint64_t *coef, const uint32_t *uses,
+                        size_t n) {
     if (!c) return fail(SR_E_INVALID, "null context");
-    if (n_tables < 0 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_index: n_tables outside 0 .. 16");
-    if (n_index < 0 || n_index > SR_LINCOMB_MAX_INDEX_COLUMNS) return fail(SR_E_INVALID, "lincomb_index: n_index outside 0 .. 8");
+    if (int rc = check_lincomb_counts(who, "", n_tables, n_index, n_outputs)) return rc;
     const int terms = n_tables + n_index;
-    if (terms < 1 || terms > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_index: n_tables + n_index outside 1 .. 16");
-    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb_index: n_outputs outside 1 .. 4");
-    if (!outs || (n_tables && !tables) || (n_index && !cols) || !coef || !uses) return fail(SR_E_INVALID, "lincomb_index: null argument");
+    if (!outs || (n_tables && !tables) || (n_index && !cols) || !coef || !uses) return refuse(who, "", "null argument");
     uint32_t any = 0;
     for (int m = 0; m < n_outputs; m++) {
-        if (uses[m] == 0) return fail(SR_E_INVALID, "lincomb_index: an output with an empty mask");
-        if (uses[m] >> (terms + 1)) return fail(SR_E_INVALID, "lincomb_index: a mask bit above n_tables + n_index");
+        if (uses[m] == 0) return refuse(who, "", "an output with an empty mask");
+        if (uses[m] >> (terms + 1)) return refuse(who, "", std::string("a mask bit above ") + who.n_terms);
         any |= uses[m];
     }
     for (int k = 0; k < n_tables; k++)
-        if (!((any >> k) & 1u)) return fail(SR_E_INVALID, "lincomb_index: a table that no output uses");
+        if (!((any >> k) & 1u)) return refuse(who, "", "a table that no output uses");
     for (int j = 0; j < n_index; j++)
-        if (!((any >> (n_tables + j)) & 1u)) return fail(SR_E_INVALID, "lincomb_index: a column that no output uses");
-    if (n >= (size_t)1 << 48) return fail(SR_E_INVALID, "lincomb_index: n must be below 2^48");
+        if (!((any >> (n_tables + j)) & 1u)) return refuse(who, "", "a column that no output uses");
+    if (n >= (size_t)1 << 48) return refuse(who, "", "n must be below 2^48");
     for (int k = 0; k < n_tables; k++)
-        if (n_evals && n_evals[k] > n) return fail(SR_E_INVALID, "lincomb_index: n_evals exceeds n");
+        if (n_evals && n_evals[k] > n) return refuse(who, "", "n_evals exceeds n");
     for (int j = 0; j < n_index; j++) {
         if (cols[j].values) {
-            if (cols[j].n_evals > n) return fail(SR_E_INVALID, "lincomb_index: a column's n_evals exceeds n");
-            if (cols[j].start != 0) return fail(SR_E_INVALID, "lincomb_index: a stored column with a non-zero start");
+            if (cols[j].n_evals > n) return refuse(who, "", "a column's n_evals exceeds n");
+            if (cols[j].start != 0) return refuse(who, "", "a stored column with a non-zero start");
         } else if (n && cols[j].start > UINT64_MAX - (uint64_t)(n - 1)) {
-            return fail(SR_E_INVALID, "lincomb_index: a progression wraps past 2^64 - 1");
+            return refuse(who, "", "a progression wraps past 2^64 - 1");
         }
     }
     for (int k = 0; k < n_tables; k++)
-        if (!tables[k]) return fail(SR_E_INVALID, "lincomb_index: null table");
+        if (!tables[k]) return refuse(who, "", "null table");
     for (int m = 0; m < n_outputs; m++)
-        if (!outs[m]) return fail(SR_E_INVALID, "lincomb_index: null output");
+        if (!outs[m]) return refuse(who, "", "null output");
     if (int rc = check_count(c, n)) return rc;  // everything above is decided without reading the context
     const size_t w = (size_t)c->degree * c->limbs * 8;
     for (int m = 0; m < n_outputs; m++) {
         for (int j = 0; j < m; j++)
-            if (ranges_overlap(outs[m], n * w, outs[j], n * w)) return fail(SR_E_INVALID, "lincomb_index: two outputs overlap");
-        if (ranges_overlap(outs[m], n * w, coef, (size_t)n_outputs * (terms + 1) * w))
-            return fail(SR_E_INVALID, "lincomb_index: an output overlaps the coefficients");
+            if (ranges_overlap(outs[m], n * w, outs[j], n * w)) return refuse(who, "", "two outputs overlap");
+        if (ranges_overlap(outs[m], n * w, coef, (size_t)n_outputs * (terms + 1) * w)) return refuse(who, "", "an output overlaps the coefficients");
         for (int j = 0; j < n_index; j++)
             if (cols[j].values && ranges_overlap(outs[m], n * w, cols[j].values, cols[j].n_evals * 8))
-                return fail(SR_E_INVALID, "lincomb_index: an output overlaps a column");
+                return refuse(who, "", "an output overlaps a column");
         for (int k = 0; k < n_tables; k++) {
             if (!ranges_overlap(outs[m], n * w, tables[k], (n_evals ? n_evals[k] : n) * w)) continue;
-            if (outs[m] != tables[k]) return fail(SR_E_INVALID, "lincomb_index: an output overlaps a table");
-            if (n_outputs != 1) return fail(SR_E_INVALID, "lincomb_index: in place needs n_outputs == 1");
+            if (outs[m] != tables[k]) return refuse(who, "", "an output overlaps a table");
+            if (n_outputs != 1) return refuse(who, "", "in place needs n_outputs == 1");
         }
     }
     return SR_OK;
+}
+// the *_dev form of the two calls
+int lincomb_dev(const LincombCall &who, sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals,
+                int n_tables, const sr_index_column *cols, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n, void *stream) {
+    if (int rc = check_lincomb_index(who, c, outs, n_outputs, tables, n_evals, n_tables, cols, n_index, coef, uses, n)) return rc;
+    const Call call(c, stream);
+    return dev_lincomb_index(c, outs, n_outputs, tables, n_evals, n_tables, cols, n_index, coef, uses, n, call.st);
 }
 // counts[t] = #{ i : idx[i] == t }: the clear and one launch on the stream; an index >= n_bins goes to d_counter[1] (gather's, spmv's)
 int dev_index_count(sr_ctx *c, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins, hipStream_t st) {
@@ -2494,6 +2440,82 @@ int upload_tables(sr_ctx *c, uint64_t *const *d, const uint64_t *const *tables, 
     for (int j = 0; j < n_tables; j++)
         if (n[j]) HIP_TRY(hipMemcpyAsync(d[j], tables[j], n[j] * w, hipMemcpyHostToDevice, c->stream));
     return SR_OK;
+}
+// A host-pointer round call (the families of RoundCall, above): the checks, then the operands to their slots -- HOST_0: the tables;
+// HOST_1: the message; HOST_2: the workspace; HOST_3: the folded tables; HOST_4: r, the coefficients and the weights, each on a 16-byte
+// boundary (an absent operand takes no room) -- and the same call on the device copies.  A fold's tables come back by the counts
+// the launch left in n_evals_out.
+int round_host(sr_ctx *c, RoundCall &a) {
+    if (int rc = check_round(c, a, false)) return rc;
+    const RoundFamily &f = a.f;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8;
+    const int nt = a.n_tables, nf = f.fold ? nt : 0;
+    size_t n_out[SR_VPOLY_MAX_TABLES];
+    for (int j = 0; j < nf; j++) n_out[j] = round_fold_n_out(a.n_evals[j], a.num_vars, a.mode);
+    const uint64_t *const rest[3] = {a.r, a.coef, a.weights};
+    const size_t rest_bytes[3] = {a.r ? w : 0, a.coef ? a.n_coef() * w : 0, a.weights ? w << f.weight_log2(a.num_vars) : 0};
+    const TableSlot in(a.n_evals, nt, w), folded(n_out, nf, w), aux(rest_bytes, 3, 1);
+    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, a.out, a.plan.np_total * w}, {nullptr, nullptr, a.plan.work_elems * w},
+                      {nullptr, nullptr, folded.total}, {nullptr, nullptr, aux.total}},
+                  [&](void *const *d) -> int {
+                      uint64_t *dt[SR_VPOLY_MAX_TABLES], *df[SR_VPOLY_MAX_TABLES], *ds[3];
+                      in.at(d[0], nt, dt);
+                      folded.at(d[3], nf, df);
+                      aux.at(d[4], 3, ds);
+                      if (int rc = upload_tables(c, dt, a.tables, a.n_evals, nt, w)) return rc;
+                      if (int rc = upload_tables(c, ds, rest, rest_bytes, 3, 1)) return rc;
+                      RoundCall dev = a;
+                      dev.out = (uint64_t *)d[1], dev.work = (uint64_t *)d[2], dev.tables = dt, dev.out_tables = nf ? df : nullptr;
+                      dev.r = a.r ? ds[0] : nullptr, dev.coef = a.coef ? ds[1] : nullptr, dev.weights = a.weights ? ds[2] : nullptr;
+                      if (int rc = dev_round(c, dev, c->stream)) return rc;
+                      for (int j = 0; j < nf; j++)
+                          if (a.n_evals_out[j])
+                              HIP_TRY(hipMemcpyAsync(a.out_tables[j], df[j], a.n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
+                      return SR_OK;
+                  });
+}
+// The host-pointer form of sr_lincomb and sr_lincomb_index.  HOST_0: the stored parts of the tables, one behind the other on 16-byte
+// boundaries; HOST_1: the outputs; HOST_2: the coefficients; HOST_3: the stored parts of the index arrays, copied as they are
+int lincomb_host(const LincombCall &who, sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals,
+                 int n_tables, const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n) {
+    if (int rc = check_lincomb_index(who, c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n)) return rc;
+    if (n == 0) return SR_OK;
+    const Call call(c);
+    const size_t w = (size_t)c->degree * c->limbs * 8, ob = (n * w + 15) & ~(size_t)15;
+    size_t off[SR_LINCOMB_MAX_TABLES], total = 0, coff[SR_LINCOMB_MAX_INDEX_COLUMNS], ctotal = 0;
+    for (int k = 0; k < n_tables; k++) {
+        off[k] = total;
+        total += ((n_evals ? n_evals[k] : n) * w + 15) & ~(size_t)15;
+    }
+    for (int j = 0; j < n_index; j++) {
+        coff[j] = ctotal;
+        ctotal += 16 + (((columns[j].values ? columns[j].n_evals * 8 : 0) + 15) & ~(size_t)15);  // never empty: a stored column keeps a non-null pointer
+    }
+    return staged(c, {{nullptr, nullptr, total}, {nullptr, nullptr, ob * n_outputs}, {coef, nullptr, (size_t)n_outputs * (n_tables + n_index + 1) * w},
+                      {nullptr, nullptr, ctotal}},
+                  [&](void *const *d) -> int {
+                      const uint64_t *dt[SR_LINCOMB_MAX_TABLES];
+                      uint64_t *dout[SR_LINCOMB_MAX_OUTPUTS];
+                      sr_index_column dc[SR_LINCOMB_MAX_INDEX_COLUMNS];
+                      for (int k = 0; k < n_tables; k++) {
+                          dt[k] = (const uint64_t *)((char *)d[0] + off[k]);
+                          const size_t b = (n_evals ? n_evals[k] : n) * w;
+                          if (b) HIP_TRY(hipMemcpyAsync((void *)dt[k], tables[k], b, hipMemcpyHostToDevice, c->stream));
+                      }
+                      for (int j = 0; j < n_index; j++) {
+                          dc[j] = columns[j];
+                          if (!columns[j].values) continue;
+                          dc[j].values = (const uint64_t *)((char *)d[3] + coff[j]);
+                          const size_t b = columns[j].n_evals * 8;
+                          if (b) HIP_TRY(hipMemcpyAsync((void *)dc[j].values, columns[j].values, b, hipMemcpyHostToDevice, c->stream));
+                      }
+                      for (int m = 0; m < n_outputs; m++) dout[m] = (uint64_t *)((char *)d[1] + ob * m);
+                      if (int r = dev_lincomb_index(c, dout, n_outputs, dt, n_evals, n_tables, dc, n_index, (const uint64_t *)d[2], uses, n, c->stream))
+                          return r;
+                      for (int m = 0; m < n_outputs; m++) HIP_TRY(hipMemcpyAsync(outs[m], dout[m], n * w, hipMemcpyDeviceToHost, c->stream));
+                      return SR_OK;
+                  });
 }
 // Sum / Product on host buffers: the n elements go to a device temporary as a whole (like the linear-algebra calls)
 int host_fold(sr_ctx *c, uint64_t *out, const uint64_t *in, size_t n, bool mul) {
@@ -2779,8 +2801,7 @@ int sr_ctx_create_ex(int ring, int log2_degree, int device, const sr_plan *plan,
             return fail(SR_E_INVALID, "sr_plan: stark_whole_max must be 0 or 9..12");
         if (plan->lanes > 2) return fail(SR_E_INVALID, "sr_plan: lanes must be 0 (default), 1 or 2");
     }
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(SR_E_NO_DEVICE, "no HIP device available (this backend has no CPU fallback)");
@@ -2966,8 +2987,7 @@ int sr_mul_elem_batch_dev(sr_ctx *c, uint64_t *d, const uint64_t *elem, size_t b
     return dev_mul_elem(c, d, elem, batch, call.st);
 }
 int sr_mle_plan(int ring, int log2_degree, size_t num_vars, size_t n_fixed, int order, size_t *work_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
     if (!work_elems || !launches) return fail(SR_E_INVALID, "mle_plan: null result pointer");
     if (num_vars >= 48) return fail(SR_E_INVALID, "mle_plan: num_vars must be below 48");
     sr::mle::Plan p;
@@ -3010,8 +3030,7 @@ int sr_mle_fix_variables(sr_ctx *c, uint64_t *out, const uint64_t *evals, size_t
                   });
 }
 int sr_prod_tree_plan(int ring, int log2_degree, size_t num_vars, int order, size_t *layer_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
     if (!layer_elems || !launches) return fail(SR_E_INVALID, "prod_tree_plan: null result pointer");
     if (num_vars >= 48) return fail(SR_E_INVALID, "prod_tree_plan: num_vars must be below 48");
     sr::ptree::Plan p;
@@ -3034,8 +3053,7 @@ int sr_prod_tree(sr_ctx *c, uint64_t *layers, const uint64_t *leaves, size_t n_l
     });
 }
 int sr_frac_tree_plan(int ring, int log2_degree, size_t num_vars, int order, size_t *layer_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
     if (!layer_elems || !launches) return fail(SR_E_INVALID, "frac_tree_plan: null result pointer");
     if (num_vars >= 48) return fail(SR_E_INVALID, "frac_tree_plan: num_vars must be below 48");
     sr::ftree::Plan p;
@@ -3062,113 +3080,26 @@ int sr_frac_tree(sr_ctx *c, uint64_t *p_layers, uint64_t *q_layers, const uint64
                   });
 }
 int sr_lincomb_plan(int ring, int log2_degree, int n_tables, int n_outputs, int *launches, int *outputs_per_launch) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
-    if (!launches || !outputs_per_launch) return fail(SR_E_INVALID, "lincomb_plan: null result pointer");
-    if (n_tables < 1 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_plan: n_tables outside 1 .. 16");
-    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb_plan: n_outputs outside 1 .. 4");
-    sr::lincomb::Plan p;
-    if (!sr::lincomb::plan(ring, n_tables, n_outputs, &p)) return fail(SR_E_INVALID, "lincomb_plan: no plan for these arguments");
-    *launches = p.launches;
-    *outputs_per_launch = p.outputs_per_launch;
-    return SR_OK;
+    return lincomb_plan_entry(kLincomb, ring, log2_degree, n_tables, 0, n_outputs, launches, outputs_per_launch);
 }
 int sr_lincomb_dev(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                    const uint64_t *coef, const uint32_t *uses, size_t n, void *stream) {
-    if (int rc = check_lincomb(c, outs, n_outputs, tables, n_evals, n_tables, coef, uses, n)) return rc;
-    const Call call(c, stream);
-    return dev_lincomb(c, outs, n_outputs, tables, n_evals, n_tables, coef, uses, n, call.st);
+    return lincomb_dev(kLincomb, c, outs, n_outputs, tables, n_evals, n_tables, nullptr, 0, coef, uses, n, stream);
 }
 int sr_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                const uint64_t *coef, const uint32_t *uses, size_t n) {
-    if (int rc = check_lincomb(c, outs, n_outputs, tables, n_evals, n_tables, coef, uses, n)) return rc;
-    if (n == 0) return SR_OK;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8, ob = (n * w + 15) & ~(size_t)15;
-    // HOST_0: the stored parts of the tables, one behind the other on 16-byte boundaries; HOST_1: the outputs; HOST_2: the coefficients
-    size_t off[SR_LINCOMB_MAX_TABLES], total = 0;
-    for (int k = 0; k < n_tables; k++) {
-        off[k] = total;
-        total += ((n_evals ? n_evals[k] : n) * w + 15) & ~(size_t)15;
-    }
-    const int rc = staged(c, {{nullptr, nullptr, total}, {nullptr, nullptr, ob * n_outputs}, {coef, nullptr, (size_t)n_outputs * (n_tables + 1) * w}},
-                          [&](void *const *d) -> int {
-                              const uint64_t *dt[SR_LINCOMB_MAX_TABLES];
-                              uint64_t *dout[SR_LINCOMB_MAX_OUTPUTS];
-                              for (int k = 0; k < n_tables; k++) {
-                                  dt[k] = (const uint64_t *)((char *)d[0] + off[k]);
-                                  const size_t b = (n_evals ? n_evals[k] : n) * w;
-                                  if (b) HIP_TRY(hipMemcpyAsync((void *)dt[k], tables[k], b, hipMemcpyHostToDevice, c->stream));
-                              }
-                              for (int m = 0; m < n_outputs; m++) dout[m] = (uint64_t *)((char *)d[1] + ob * m);
-                              if (int r = dev_lincomb(c, dout, n_outputs, dt, n_evals, n_tables, (const uint64_t *)d[2], uses, n, c->stream)) return r;
-                              for (int m = 0; m < n_outputs; m++) HIP_TRY(hipMemcpyAsync(outs[m], dout[m], n * w, hipMemcpyDeviceToHost, c->stream));
-                              return SR_OK;
-                          });
-    return rc;
+    return lincomb_host(kLincomb, c, outs, n_outputs, tables, n_evals, n_tables, nullptr, 0, coef, uses, n);
 }
 int sr_lincomb_index_plan(int ring, int log2_degree, int n_tables, int n_index, int n_outputs, int *launches, int *outputs_per_launch) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
-    if (!launches || !outputs_per_launch) return fail(SR_E_INVALID, "lincomb_index_plan: null result pointer");
-    if (n_tables < 0 || n_tables > SR_LINCOMB_MAX_TABLES) return fail(SR_E_INVALID, "lincomb_index_plan: n_tables outside 0 .. 16");
-    if (n_index < 0 || n_index > SR_LINCOMB_MAX_INDEX_COLUMNS) return fail(SR_E_INVALID, "lincomb_index_plan: n_index outside 0 .. 8");
-    if (n_tables + n_index < 1 || n_tables + n_index > SR_LINCOMB_MAX_TABLES)
-        return fail(SR_E_INVALID, "lincomb_index_plan: n_tables + n_index outside 1 .. 16");
-    if (n_outputs < 1 || n_outputs > SR_LINCOMB_MAX_OUTPUTS) return fail(SR_E_INVALID, "lincomb_index_plan: n_outputs outside 1 .. 4");
-    sr::lincomb::Plan p;
-    if (!sr::lincomb_index::plan(ring, n_tables, n_index, n_outputs, &p)) return fail(SR_E_INVALID, "lincomb_index_plan: no plan for these arguments");
-    *launches = p.launches;
-    *outputs_per_launch = p.outputs_per_launch;
-    return SR_OK;
+    return lincomb_plan_entry(kLincombIndex, ring, log2_degree, n_tables, n_index, n_outputs, launches, outputs_per_launch);
 }
 int sr_lincomb_index_dev(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                          const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n, void *stream) {
-    if (int rc = check_lincomb_index(c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n)) return rc;
-    const Call call(c, stream);
-    return dev_lincomb_index(c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n, call.st);
+    return lincomb_dev(kLincombIndex, c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n, stream);
 }
 int sr_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                      const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n) {
-    if (int rc = check_lincomb_index(c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n)) return rc;
-    if (n == 0) return SR_OK;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8, ob = (n * w + 15) & ~(size_t)15;
-    // HOST_0: the stored parts of the tables, one behind the other on 16-byte boundaries; HOST_1: the outputs; HOST_2: the
-    // coefficients; HOST_3: the stored parts of the index arrays, copied as they are
-    size_t off[SR_LINCOMB_MAX_TABLES], total = 0, coff[SR_LINCOMB_MAX_INDEX_COLUMNS], ctotal = 0;
-    for (int k = 0; k < n_tables; k++) {
-        off[k] = total;
-        total += ((n_evals ? n_evals[k] : n) * w + 15) & ~(size_t)15;
-    }
-    for (int j = 0; j < n_index; j++) {
-        coff[j] = ctotal;
-        ctotal += 16 + (((columns[j].values ? columns[j].n_evals * 8 : 0) + 15) & ~(size_t)15);  // never empty: a stored column keeps a non-null pointer
-    }
-    return staged(c, {{nullptr, nullptr, total}, {nullptr, nullptr, ob * n_outputs}, {coef, nullptr, (size_t)n_outputs * (n_tables + n_index + 1) * w},
-                      {nullptr, nullptr, ctotal}},
-                  [&](void *const *d) -> int {
-                      const uint64_t *dt[SR_LINCOMB_MAX_TABLES];
-                      uint64_t *dout[SR_LINCOMB_MAX_OUTPUTS];
-                      sr_index_column dc[SR_LINCOMB_MAX_INDEX_COLUMNS];
-                      for (int k = 0; k < n_tables; k++) {
-                          dt[k] = (const uint64_t *)((char *)d[0] + off[k]);
-                          const size_t b = (n_evals ? n_evals[k] : n) * w;
-                          if (b) HIP_TRY(hipMemcpyAsync((void *)dt[k], tables[k], b, hipMemcpyHostToDevice, c->stream));
-                      }
-                      for (int j = 0; j < n_index; j++) {
-                          dc[j] = columns[j];
-                          if (!columns[j].values) continue;
-                          dc[j].values = (const uint64_t *)((char *)d[3] + coff[j]);
-                          const size_t b = columns[j].n_evals * 8;
-                          if (b) HIP_TRY(hipMemcpyAsync((void *)dc[j].values, columns[j].values, b, hipMemcpyHostToDevice, c->stream));
-                      }
-                      for (int m = 0; m < n_outputs; m++) dout[m] = (uint64_t *)((char *)d[1] + ob * m);
-                      if (int r = dev_lincomb_index(c, dout, n_outputs, dt, n_evals, n_tables, dc, n_index, (const uint64_t *)d[2], uses, n, c->stream))
-                          return r;
-                      for (int m = 0; m < n_outputs; m++) HIP_TRY(hipMemcpyAsync(outs[m], dout[m], n * w, hipMemcpyDeviceToHost, c->stream));
-                      return SR_OK;
-                  });
+    return lincomb_host(kLincombIndex, c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n);
 }
 int sr_index_count_dev(sr_ctx *c, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins, void *stream) {
     if (int rc = check_index_count(c, counts, idx, n, n_bins)) return rc;
@@ -3185,324 +3116,130 @@ int sr_index_count(sr_ctx *c, uint64_t *counts, const uint64_t *idx, size_t n, s
                   [&](void *const *d) { return dev_index_count(c, (uint64_t *)d[1], (const uint64_t *)d[0], n, n_bins, c->stream); });
 }
 int sr_mle_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int mode, size_t *work_elems, int *launches) {
-    return round_plan_entry(kMleRound, ring, log2_degree, num_vars, n_tables, 0, 0, mode, work_elems, launches);
+    return round_plan_entry(kMleRound, ring, log2_degree, num_vars, n_tables, 0, 0, 0, mode, work_elems, launches);
 }
 int sr_mle_round_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars,
                            int mode, uint64_t *work, size_t work_elems, void *stream) {
-    sr::sumcheck::Plan p;
-    if (int rc = check_mle_round(c, out, tables, n_evals, n_tables, num_vars, mode, &p)) return rc;
-    if (int rc = check_round_work(kMleRound, p, work, work_elems)) return rc;
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    for (int j = 0; j < n_tables; j++) {
-        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round: d_out overlaps a table");
-        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "mle_round: d_work overlaps a table");
-    }
-    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "mle_round: d_out overlaps d_work");
-    const Call call(c, stream);
-    return dev_mle_round(c, p, mode, out, tables, n_evals, n_tables, num_vars, work, call.st);
+    RoundCall a{kMleRound, out, tables, n_evals, n_tables, num_vars, mode};
+    a.work = work, a.work_elems = work_elems;
+    return round_dev(c, a, stream);
 }
 int sr_mle_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, size_t num_vars, int mode) {
-    sr::sumcheck::Plan p;
-    if (int rc = check_mle_round(c, out, tables, n_evals, n_tables, num_vars, mode, &p)) return rc;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    const TableSlot in(n_evals, n_tables, w);
-    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace
-    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}}, [&](void *const *d) -> int {
-        uint64_t *dt[SR_MLE_ROUND_MAX_TABLES];
-        in.at(d[0], n_tables, dt);
-        if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
-        return dev_mle_round(c, p, mode, (uint64_t *)d[1], dt, n_evals, n_tables, num_vars, (uint64_t *)d[2], c->stream);
-    });
+    RoundCall a{kMleRound, out, tables, n_evals, n_tables, num_vars, mode};
+    return round_host(c, a);
 }
 int sr_vpoly_round_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int mode, size_t *work_elems,
                         int *launches) {
-    return round_plan_entry(kVpolyRound, ring, log2_degree, num_vars, n_tables, n_terms, degree, mode, work_elems, launches);
+    return round_plan_entry(kVpolyRound, ring, log2_degree, num_vars, n_tables, n_terms, degree, 0, mode, work_elems, launches);
 }
 int sr_vpoly_round_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                              const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int mode, uint64_t *work,
                              size_t work_elems, void *stream) {
-    sr::vpoly::Plan p;
-    if (int rc = check_vpoly_round(c, out, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, &p)) return rc;
-    if (int rc = check_round_work(kVpolyRound, p, work, work_elems)) return rc;
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    const size_t cw = coef ? n_terms * w : 0;
-    for (int j = 0; j < n_tables; j++) {
-        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "vpoly_round: d_out overlaps a table");
-        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "vpoly_round: d_work overlaps a table");
-        if (ranges_overlap(coef, cw, tables[j], n_evals[j] * w)) return fail(SR_E_INVALID, "vpoly_round: d_coeffs overlaps a table");
-    }
-    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return fail(SR_E_INVALID, "vpoly_round: d_out overlaps d_work");
-    if (ranges_overlap(out, p.np_total * w, coef, cw)) return fail(SR_E_INVALID, "vpoly_round: d_out overlaps d_coeffs");
-    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return fail(SR_E_INVALID, "vpoly_round: d_work overlaps d_coeffs");
-    const Call call(c, stream);
-    return dev_vpoly_round(c, p, mode, out, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, work, call.st);
+    RoundCall a{kVpolyRound, out, tables, n_evals, n_tables, num_vars, mode};
+    a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    a.work = work, a.work_elems = work_elems;
+    return round_dev(c, a, stream);
 }
 int sr_vpoly_round_evals(sr_ctx *c, uint64_t *out, const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms,
                          int n_terms, const uint64_t *coef, size_t num_vars, int mode) {
-    sr::vpoly::Plan p;
-    if (int rc = check_vpoly_round(c, out, tables, n_evals, n_tables, terms, n_terms, num_vars, mode, &p)) return rc;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    const TableSlot in(n_evals, n_tables, w);
-    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients
-    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {coef, nullptr, coef ? n_terms * w : 0}},
-                  [&](void *const *d) -> int {
-                      uint64_t *dt[SR_VPOLY_MAX_TABLES];
-                      in.at(d[0], n_tables, dt);
-                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
-                      return dev_vpoly_round(c, p, mode, (uint64_t *)d[1], dt, n_evals, n_tables, terms, n_terms, coef ? (const uint64_t *)d[3] : nullptr,
-                                             num_vars, (uint64_t *)d[2], c->stream);
-                  });
+    RoundCall a{kVpolyRound, out, tables, n_evals, n_tables, num_vars, mode};
+    a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    return round_host(c, a);
 }
 int sr_mle_round_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int order, size_t *work_elems, int *launches) {
-    return round_plan_entry(kMleRoundFold, ring, log2_degree, num_vars, n_tables, 0, 0, order, work_elems, launches);
+    return round_plan_entry(kMleRoundFold, ring, log2_degree, num_vars, n_tables, 0, 0, 0, order, work_elems, launches);
 }
 int sr_mle_round_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
                                 const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, int order, uint64_t *work,
                                 size_t work_elems, void *stream) {
-    sr::sumcheck_fold::Plan p;
-    if (int rc = check_mle_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, order, &p)) return rc;
-    if (int rc = check_round_work(kMleRoundFold, p, work, work_elems)) return rc;
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    size_t n_out[SR_MLE_ROUND_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
-    if (int rc = check_fold_overlaps(kMleRoundFold, p, w, out, out_tables, n_out, tables, n_evals, n_tables, nullptr, 0, r, order, work)) return rc;
-    const Call call(c, stream);
-    return dev_mle_round_fold(c, p, order, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, work, call.st);
+    RoundCall a{kMleRoundFold, out, tables, n_evals, n_tables, num_vars, order};
+    a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
+    a.work = work, a.work_elems = work_elems;
+    return round_dev(c, a, stream);
 }
 int sr_mle_round_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
                             const size_t *n_evals, int n_tables, size_t num_vars, const uint64_t *r, int order) {
-    sr::sumcheck_fold::Plan p;
-    if (int rc = check_mle_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, num_vars, r, order, &p)) return rc;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    size_t n_out[SR_MLE_ROUND_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
-    const TableSlot in(n_evals, n_tables, w), folded(n_out, n_tables, w);
-    // HOST_0: the tables; HOST_1: the message; HOST_2: the workspace; HOST_3: the folded tables; HOST_4: r
-    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {nullptr, nullptr, folded.total},
-                      {r, nullptr, w}},
-                  [&](void *const *d) -> int {
-                      uint64_t *dt[SR_MLE_ROUND_MAX_TABLES], *dout[SR_MLE_ROUND_MAX_TABLES];
-                      in.at(d[0], n_tables, dt);
-                      folded.at(d[3], n_tables, dout);
-                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
-                      if (int rc = dev_mle_round_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dt, n_evals, n_tables, num_vars,
-                                                      (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
-                          return rc;
-                      for (int j = 0; j < n_tables; j++)
-                          if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
-                      return SR_OK;
-                  });
+    RoundCall a{kMleRoundFold, out, tables, n_evals, n_tables, num_vars, order};
+    a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
+    return round_host(c, a);
 }
 int sr_vpoly_round_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order, size_t *work_elems,
                              int *launches) {
-    return round_plan_entry(kVpolyRoundFold, ring, log2_degree, num_vars, n_tables, n_terms, degree, order, work_elems, launches);
+    return round_plan_entry(kVpolyRoundFold, ring, log2_degree, num_vars, n_tables, n_terms, degree, 0, order, work_elems, launches);
 }
 int sr_vpoly_round_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
                                   const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef,
                                   size_t num_vars, const uint64_t *r, int order, uint64_t *work, size_t work_elems, void *stream) {
-    sr::vpoly_fold::Plan p;
-    if (int rc = check_vpoly_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, terms, n_terms, num_vars, r, order, &p)) return rc;
-    if (int rc = check_round_work(kVpolyRoundFold, p, work, work_elems)) return rc;
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    size_t n_out[SR_VPOLY_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
-    if (int rc = check_fold_overlaps(kVpolyRoundFold, p, w, out, out_tables, n_out, tables, n_evals, n_tables, coef, coef ? n_terms * w : 0, r, order,
-                                     work))
-        return rc;
-    const Call call(c, stream);
-    return dev_vpoly_round_fold(c, p, order, out, out_tables, n_evals_out, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, r, work, call.st);
+    RoundCall a{kVpolyRoundFold, out, tables, n_evals, n_tables, num_vars, order};
+    a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
+    a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    a.work = work, a.work_elems = work_elems;
+    return round_dev(c, a, stream);
 }
 int sr_vpoly_round_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *const *tables,
                               const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars,
                               const uint64_t *r, int order) {
-    sr::vpoly_fold::Plan p;
-    if (int rc = check_vpoly_round_fold(c, out, out_tables, n_evals_out, tables, n_evals, n_tables, terms, n_terms, num_vars, r, order, &p)) return rc;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    size_t n_out[SR_VPOLY_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
-    const TableSlot in(n_evals, n_tables, w), folded(n_out, n_tables, w);
-    // HOST_0: the tables; HOST_1: the message; HOST_2: the workspace; HOST_3: the folded tables; HOST_4: r, then (on the next 16-byte
-    // boundary) the coefficients
-    const size_t coef_at = (w + 15) & ~(size_t)15, cw = coef ? n_terms * w : 0;
-    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {nullptr, nullptr, folded.total},
-                      {nullptr, nullptr, coef_at + cw}},
-                  [&](void *const *d) -> int {
-                      uint64_t *dt[SR_VPOLY_MAX_TABLES], *dout[SR_VPOLY_MAX_TABLES];
-                      in.at(d[0], n_tables, dt);
-                      folded.at(d[3], n_tables, dout);
-                      const uint64_t *dcoef = coef ? (const uint64_t *)((const char *)d[4] + coef_at) : nullptr;
-                      HIP_TRY(hipMemcpyAsync(d[4], r, w, hipMemcpyHostToDevice, c->stream));
-                      if (coef) HIP_TRY(hipMemcpyAsync((void *)dcoef, coef, cw, hipMemcpyHostToDevice, c->stream));
-                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
-                      if (int rc = dev_vpoly_round_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dt, n_evals, n_tables, terms, n_terms, dcoef,
-                                                        num_vars, (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
-                          return rc;
-                      for (int j = 0; j < n_tables; j++)
-                          if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
-                      return SR_OK;
-                  });
+    RoundCall a{kVpolyRoundFold, out, tables, n_evals, n_tables, num_vars, order};
+    a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
+    a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    return round_host(c, a);
 }
 int sr_vpoly_wround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order, size_t *work_elems,
                          int *launches) {
-    return round_plan_entry(kVpolyWround, ring, log2_degree, num_vars, n_tables, n_terms, degree, order, work_elems, launches);
+    return round_plan_entry(kVpolyWround, ring, log2_degree, num_vars, n_tables, n_terms, degree, 0, order, work_elems, launches);
 }
 int sr_vpoly_wround_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
                               int n_tables, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int order,
                               uint64_t *work, size_t work_elems, void *stream) {
-    sr::wsumcheck::Plan p;
-    if (!weights) return refuse(kVpolyWround, "null pointer (d_weights)");
-    if (int rc = check_vpoly_terms(c, kVpolyWround, out, nullptr, nullptr, nullptr, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
-        return rc;
-    if (int rc = check_round_work(kVpolyWround, p, work, work_elems)) return rc;
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    const size_t cw = coef ? n_terms * w : 0, ww = w << (num_vars - 1);
-    for (int j = 0; j < n_tables; j++) {
-        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return refuse(kVpolyWround, "d_out overlaps a table");
-        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return refuse(kVpolyWround, "d_work overlaps a table");
-        if (ranges_overlap(coef, cw, tables[j], n_evals[j] * w)) return refuse(kVpolyWround, "d_coeffs overlaps a table");
-    }
-    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return refuse(kVpolyWround, "d_out overlaps d_work");
-    if (ranges_overlap(out, p.np_total * w, coef, cw)) return refuse(kVpolyWround, "d_out overlaps d_coeffs");
-    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return refuse(kVpolyWround, "d_work overlaps d_coeffs");
-    if (ranges_overlap(out, p.np_total * w, weights, ww)) return refuse(kVpolyWround, "d_out overlaps d_weights");
-    if (ranges_overlap(work, p.work_elems * w, weights, ww)) return refuse(kVpolyWround, "d_work overlaps d_weights");
-    const Call call(c, stream);
-    return dev_vpoly_wround(c, p, order, out, weights, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, work, call.st);
+    RoundCall a{kVpolyWround, out, tables, n_evals, n_tables, num_vars, order};
+    a.weights = weights, a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    a.work = work, a.work_elems = work_elems;
+    return round_dev(c, a, stream);
 }
 int sr_vpoly_wround_evals(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                           const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, int order) {
-    sr::wsumcheck::Plan p;
-    if (!weights) return refuse(kVpolyWround, "null pointer (weights)");
-    if (int rc = check_vpoly_terms(c, kVpolyWround, out, nullptr, nullptr, nullptr, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
-        return rc;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    const TableSlot in(n_evals, n_tables, w);
-    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients; HOST_4: the weights
-    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {coef, nullptr, coef ? n_terms * w : 0},
-                      {weights, nullptr, w << (num_vars - 1)}},
-                  [&](void *const *d) -> int {
-                      uint64_t *dt[SR_VPOLY_MAX_TABLES];
-                      in.at(d[0], n_tables, dt);
-                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
-                      return dev_vpoly_wround(c, p, order, (uint64_t *)d[1], (const uint64_t *)d[4], dt, n_evals, n_tables, terms, n_terms,
-                                              coef ? (const uint64_t *)d[3] : nullptr, num_vars, (uint64_t *)d[2], c->stream);
-                  });
+    RoundCall a{kVpolyWround, out, tables, n_evals, n_tables, num_vars, order};
+    a.weights = weights, a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    return round_host(c, a);
 }
 int sr_vpoly_wround_fold_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_terms, int degree, int order, size_t *work_elems,
                               int *launches) {
-    return round_plan_entry(kVpolyWroundFold, ring, log2_degree, num_vars, n_tables, n_terms, degree, order, work_elems, launches);
+    return round_plan_entry(kVpolyWroundFold, ring, log2_degree, num_vars, n_tables, n_terms, degree, 0, order, work_elems, launches);
 }
 int sr_vpoly_wround_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
                                    const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
                                    const uint64_t *coef, size_t num_vars, const uint64_t *r, int order, uint64_t *work, size_t work_elems,
                                    void *stream) {
-    sr::wsumcheck::Plan p;
-    if (!weights) return refuse(kVpolyWroundFold, "null pointer (d_weights)");
-    if (int rc = check_vpoly_terms(c, kVpolyWroundFold, out, out_tables, n_evals_out, r, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
-        return rc;
-    if (int rc = check_round_work(kVpolyWroundFold, p, work, work_elems)) return rc;
-    const size_t w = (size_t)c->degree * c->limbs * 8, ww = w << (num_vars - 2);
-    size_t n_out[SR_VPOLY_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
-    if (int rc = check_fold_overlaps(kVpolyWroundFold, p, w, out, out_tables, n_out, tables, n_evals, n_tables, coef, coef ? n_terms * w : 0, r, order,
-                                     work))
-        return rc;
-    if (ranges_overlap(out, p.np_total * w, weights, ww)) return refuse(kVpolyWroundFold, "d_out overlaps d_weights");
-    if (ranges_overlap(work, p.work_elems * w, weights, ww)) return refuse(kVpolyWroundFold, "d_work overlaps d_weights");
-    for (int j = 0; j < n_tables; j++)
-        if (ranges_overlap(out_tables[j], n_out[j] * w, weights, ww)) return refuse(kVpolyWroundFold, "a folded table overlaps d_weights");
-    const Call call(c, stream);
-    return dev_vpoly_wround_fold(c, p, order, out, out_tables, n_evals_out, weights, tables, n_evals, n_tables, terms, n_terms, coef, num_vars, r, work,
-                                 call.st);
+    RoundCall a{kVpolyWroundFold, out, tables, n_evals, n_tables, num_vars, order};
+    a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
+    a.weights = weights, a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    a.work = work, a.work_elems = work_elems;
+    return round_dev(c, a, stream);
 }
 int sr_vpoly_wround_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
                                const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_vpoly_term *terms, int n_terms,
                                const uint64_t *coef, size_t num_vars, const uint64_t *r, int order) {
-    sr::wsumcheck::Plan p;
-    if (!weights) return refuse(kVpolyWroundFold, "null pointer (weights)");
-    if (int rc = check_vpoly_terms(c, kVpolyWroundFold, out, out_tables, n_evals_out, r, tables, n_evals, n_tables, terms, n_terms, num_vars, order, &p))
-        return rc;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    size_t n_out[SR_VPOLY_MAX_TABLES];
-    for (int j = 0; j < n_tables; j++) n_out[j] = round_fold_n_out(n_evals[j], num_vars, order);
-    const TableSlot in(n_evals, n_tables, w), folded(n_out, n_tables, w);
-    // HOST_0: the tables; HOST_1: the message; HOST_2: the workspace; HOST_3: the folded tables; HOST_4: r, then (each on the next 16-byte
-    // boundary) the coefficients and the weights
-    const size_t coef_at = (w + 15) & ~(size_t)15, cw = coef ? n_terms * w : 0, weights_at = (coef_at + cw + 15) & ~(size_t)15,
-                 ww = w << (num_vars - 2);
-    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {nullptr, nullptr, folded.total},
-                      {nullptr, nullptr, weights_at + ww}},
-                  [&](void *const *d) -> int {
-                      uint64_t *dt[SR_VPOLY_MAX_TABLES], *dout[SR_VPOLY_MAX_TABLES];
-                      in.at(d[0], n_tables, dt);
-                      folded.at(d[3], n_tables, dout);
-                      const uint64_t *dcoef = coef ? (const uint64_t *)((const char *)d[4] + coef_at) : nullptr;
-                      const uint64_t *dweights = (const uint64_t *)((const char *)d[4] + weights_at);
-                      HIP_TRY(hipMemcpyAsync(d[4], r, w, hipMemcpyHostToDevice, c->stream));
-                      if (coef) HIP_TRY(hipMemcpyAsync((void *)dcoef, coef, cw, hipMemcpyHostToDevice, c->stream));
-                      HIP_TRY(hipMemcpyAsync((void *)dweights, weights, ww, hipMemcpyHostToDevice, c->stream));
-                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
-                      if (int rc = dev_vpoly_wround_fold(c, p, order, (uint64_t *)d[1], dout, n_evals_out, dweights, dt, n_evals, n_tables, terms,
-                                                         n_terms, dcoef, num_vars, (const uint64_t *)d[4], (uint64_t *)d[2], c->stream))
-                          return rc;
-                      for (int j = 0; j < n_tables; j++)
-                          if (n_evals_out[j]) HIP_TRY(hipMemcpyAsync(out_tables[j], dout[j], n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
-                      return SR_OK;
-                  });
+    RoundCall a{kVpolyWroundFold, out, tables, n_evals, n_tables, num_vars, order};
+    a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
+    a.weights = weights, a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    return round_host(c, a);
 }
 int sr_range_wround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int bound, int order, size_t *work_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
-    if (!work_elems || !launches) return fail(SR_E_INVALID, "range_wround_plan: null result pointer");
-    sr::range::Plan p;
-    if (int rc = range_plan_for(ring, log2_degree, num_vars, n_tables, bound, order, &p)) return rc;
-    *work_elems = p.work_elems;
-    *launches = p.launches;
-    return SR_OK;
+    return round_plan_entry(kRangeWround, ring, log2_degree, num_vars, n_tables, 0, 0, bound, order, work_elems, launches);
 }
 int sr_range_wround_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
                               int n_tables, int bound, const uint64_t *coef, size_t num_vars, int order, uint64_t *work, size_t work_elems,
                               void *stream) {
-    sr::range::Plan p;
-    if (int rc = check_range_wround(c, out, weights, tables, n_evals, n_tables, bound, num_vars, order, &p)) return rc;
-    if (int rc = check_round_work(kRangeWround, p, work, work_elems)) return rc;
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    const size_t cw = coef ? n_tables * w : 0, ww = w << (num_vars - 1);
-    for (int j = 0; j < n_tables; j++) {
-        if (ranges_overlap(out, p.np_total * w, tables[j], n_evals[j] * w)) return refuse(kRangeWround, "d_out overlaps a table");
-        if (ranges_overlap(work, p.work_elems * w, tables[j], n_evals[j] * w)) return refuse(kRangeWround, "d_work overlaps a table");
-    }
-    if (ranges_overlap(out, p.np_total * w, work, p.work_elems * w)) return refuse(kRangeWround, "d_out overlaps d_work");
-    if (ranges_overlap(out, p.np_total * w, coef, cw)) return refuse(kRangeWround, "d_out overlaps d_coeffs");
-    if (ranges_overlap(work, p.work_elems * w, coef, cw)) return refuse(kRangeWround, "d_work overlaps d_coeffs");
-    if (ranges_overlap(out, p.np_total * w, weights, ww)) return refuse(kRangeWround, "d_out overlaps d_weights");
-    if (ranges_overlap(work, p.work_elems * w, weights, ww)) return refuse(kRangeWround, "d_work overlaps d_weights");
-    const Call call(c, stream);
-    return dev_range_wround(c, p, order, out, weights, tables, n_evals, n_tables, bound, coef, num_vars, work, call.st);
+    RoundCall a{kRangeWround, out, tables, n_evals, n_tables, num_vars, order};
+    a.weights = weights, a.bound = bound, a.coef = coef;
+    a.work = work, a.work_elems = work_elems;
+    return round_dev(c, a, stream);
 }
 int sr_range_wround_evals(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                           int bound, const uint64_t *coef, size_t num_vars, int order) {
-    sr::range::Plan p;
-    if (int rc = check_range_wround(c, out, weights, tables, n_evals, n_tables, bound, num_vars, order, &p)) return rc;
-    const Call call(c);
-    const size_t w = (size_t)c->degree * c->limbs * 8;
-    const TableSlot in(n_evals, n_tables, w);
-    // HOST_0: the tables; HOST_1: the result; HOST_2: the workspace; HOST_3: the coefficients; HOST_4: the weights
-    return staged(c, {{nullptr, nullptr, in.total}, {nullptr, out, p.np_total * w}, {nullptr, nullptr, p.work_elems * w}, {coef, nullptr, coef ? n_tables * w : 0},
-                      {weights, nullptr, w << (num_vars - 1)}},
-                  [&](void *const *d) -> int {
-                      uint64_t *dt[SR_RANGE_MAX_TABLES];
-                      in.at(d[0], n_tables, dt);
-                      if (int rc = upload_tables(c, dt, tables, n_evals, n_tables, w)) return rc;
-                      return dev_range_wround(c, p, order, (uint64_t *)d[1], (const uint64_t *)d[4], dt, n_evals, n_tables, bound,
-                                              coef ? (const uint64_t *)d[3] : nullptr, num_vars, (uint64_t *)d[2], c->stream);
-                  });
+    RoundCall a{kRangeWround, out, tables, n_evals, n_tables, num_vars, order};
+    a.weights = weights, a.bound = bound, a.coef = coef;
+    return round_host(c, a);
 }
 int sr_eq_table_dev(sr_ctx *c, uint64_t *out, const uint64_t *point, size_t n_vars, void *stream) {
     if (int rc = check(c, {out, n_vars ? (const void *)point : (const void *)1})) return rc;
@@ -3542,8 +3279,7 @@ int sr_smle_fix_pattern(const uint64_t *idx, size_t nnz, size_t num_vars, size_t
     return SR_OK;
 }
 int sr_smle_plan(int ring, int log2_degree, size_t nnz, size_t n_out, size_t n_fixed, size_t *work_elems, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
-    if (is_pow2_ring(ring) && (log2_degree < 0 || log2_degree > 24)) return fail(SR_E_INVALID, "log2_degree out of range");
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
     if (!work_elems || !launches) return fail(SR_E_INVALID, "smle_plan: null result pointer");
     sr::smle::Plan p;
     if (int rc = smle_plan_for(ring, log2_degree, nnz, n_out, n_fixed, &p)) return rc;
@@ -3592,7 +3328,7 @@ int sr_smle_fix_variables(sr_ctx *c, uint64_t *out_vals, uint64_t *out_idx, size
                   });
 }
 int sr_norm_plan(int ring, size_t n_coeffs, size_t group, int which, size_t *out_words_per_group, size_t *work_words, int *launches) {
-    if (ring < SR_RING_GOLDILOCKS_POW2 || ring > SR_RING_FROG_16) return fail(SR_E_INVALID, "unknown ring id");
+    if (int rc = check_plan_ring(ring, 0)) return rc;  // no degree: the norms count coefficients
     if (!out_words_per_group || !work_words || !launches) return fail(SR_E_INVALID, "norm_plan: null result pointer");
     sr::norms::Plan p;
     if (int rc = check_norm(ring == SR_RING_STARK_POW2 ? 4 : 1, n_coeffs, group, which, &p)) return rc;

@@ -12,12 +12,8 @@ exist and none is folded.  The three calls are functions of this module, not met
 a closed table of the *_dev methods of CyclotomicRing.  RangePolynomial is the claim without eq with exactly the members EqSumCheck
 (mle.py) uses of its g, so that EqSumCheck(RangePolynomial(ring, tables, bound), z, order) runs a whole norm check.
 """
-import ctypes
-
-import numpy as np
-
 from .mle import DenseMultilinearExtension
-from .rings import MLE_LEADING, MLE_TRAILING, STARK_POW2, RingError, _np_ptr
+from .rings import MLE_LEADING, MLE_TRAILING, RingError, _np_ptr
 
 RANGE_MAX_TABLES = 8
 RANGE_MAX_BOUND = 8
@@ -25,12 +21,7 @@ RANGE_MAX_BOUND = 8
 
 def range_wround_plan(ring, num_vars, n_tables, bound, order=MLE_LEADING):
     """sr_range_wround_plan: (work_elems, launches) of a range-check round message -- host arithmetic only."""
-    work = ctypes.c_size_t()
-    launches = ctypes.c_int()
-    k = ring.degree.bit_length() - 1 if ring.ring <= STARK_POW2 else 0
-    ring._check(ring._lib.sr_range_wround_plan(ring.ring, k, int(num_vars), int(n_tables), int(bound), int(order), ctypes.byref(work),
-                                               ctypes.byref(launches)))
-    return work.value, launches.value
+    return ring._plan_of(ring._lib.sr_range_wround_plan, num_vars, n_tables, bound, order)
 
 
 def range_wround_evals_dev(ring, out, weights, tables, bound, coeffs, num_vars, order=MLE_LEADING, work=None, stream=None):
@@ -39,33 +30,9 @@ def range_wround_evals_dev(ring, out, weights, tables, bound, coeffs, num_vars, 
     CUDA tensors of n_evals <= 2^num_vars elements; coeffs: a CUDA tensor of one ring element per table, or None for one(); order:
     MLE_LEADING or MLE_TRAILING; work: at least range_wround_plan()[0] elements (None only where the plan needs none).  Allocates
     nothing."""
-    w = ring.words_per_elem
-    po, no = ring._dev(out)
-    n = len(tables)
-    if 2 <= bound <= RANGE_MAX_BOUND and no != w * 2 * bound:
-        raise RingError("range_wround_evals: out must hold 2 bound elements")
-    if weights is None:
-        pwt = ctypes.c_void_p(0)
-    else:
-        pwt, nwt = ring._dev(weights)
-        if 1 <= num_vars < 48 and nwt != w << (num_vars - 1):
-            raise RingError("range_wround_evals: weights must hold one element per pair (2^%d)" % (num_vars - 1))
-    ptrs = (ctypes.c_void_p * max(n, 1))()
-    sizes = (ctypes.c_size_t * max(n, 1))()
-    for j, t in enumerate(tables):
-        sizes[j] = ring._batch_of(t.numel())
-        ptrs[j] = ring._dev(t)[0] if t.numel() else None
-    if coeffs is None:
-        pc = ctypes.c_void_p(0)
-    else:
-        pc, nc = ring._dev(coeffs)
-        if nc != n * w:
-            raise RingError("range_wround_evals: one coefficient per table")
-    if work is None:
-        pw, nw = ctypes.c_void_p(0), 0
-    else:
-        pw, nw = ring._dev(work)
-        nw //= w
+    po, ptrs, sizes, n, pc, pwt, pw, nw = ring._round_dev_args("range_wround_evals", out, 2 * bound if 2 <= bound <= RANGE_MAX_BOUND else None,
+                                                               "2 bound elements", tables, work, coeffs, len(tables), "table", weights,
+                                                               num_vars - 1)
     ring._check(ring._lib.sr_range_wround_evals_dev(ring._ctx, po, pwt, ptrs, sizes, n, int(bound), pc, int(num_vars), int(order), pw, nw,
                                                     ring._stream(stream)))
     return out
@@ -73,20 +40,9 @@ def range_wround_evals_dev(ring, out, weights, tables, bound, coeffs, num_vars, 
 
 def range_wround_evals(ring, weights, tables, bound, coeffs, num_vars, order=MLE_LEADING):
     """Host buffers: sr_range_wround_evals (see range_wround_evals_dev); returns the 2 bound elements."""
-    tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-    weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
-    n, w = len(tables), ring.words_per_elem
-    out = np.empty(w * 2 * max(int(bound), 1), dtype=np.uint64)
-    ptrs = (ctypes.c_void_p * max(n, 1))()
-    sizes = (ctypes.c_size_t * max(n, 1))()
-    for j, t in enumerate(tables):
-        sizes[j] = ring._batch_of(t.size)
-        ptrs[j] = t.ctypes.data if t.size else None
-    if coeffs is not None:
-        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
-        if coeffs.size != n * w:
-            raise RingError("range_wround_evals: one coefficient per table")
-    if weights is not None and 1 <= num_vars < 48 and weights.size != w << (num_vars - 1):
+    tables, weights, coeffs, out, ptrs, sizes, n = ring._round_host_args("range_wround_evals", 2 * max(int(bound), 1), tables, coeffs,
+                                                                         len(tables), "table", weights)
+    if weights is not None and 1 <= num_vars < 48 and weights.size != ring.words_per_elem << (num_vars - 1):
         raise RingError("range_wround_evals: weights must hold one element per pair")
     ring._check(ring._lib.sr_range_wround_evals(ring._ctx, _np_ptr(out), None if weights is None else weights.ctypes.data, ptrs, sizes, n,
                                                 int(bound), None if coeffs is None else coeffs.ctypes.data, int(num_vars), int(order)))

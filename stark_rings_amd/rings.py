@@ -955,13 +955,97 @@ class CyclotomicRing:
         self._check(self._lib.sr_prod_tree(self._ctx, _np_ptr(out), _np_ptr(leaves if n_leaves else z), n_leaves, int(num_vars), int(order)))
         return out[:n_out]
 
-    def mle_round_plan(self, num_vars, n_tables, mode=MLE_LEADING):
-        """sr_mle_round_plan: (work_elems, launches) of a sum-check round message over n_tables tables -- host arithmetic only."""
+    # ---- sum-check round messages: seven families (range_check.py holds the seventh), one set of argument helpers ----
+    def _plan_of(self, fn, num_vars, n_tables, *shape):
+        """(work_elems, launches) of a round family's *_plan call; shape: what the call takes after n_tables (n_terms and degree, or
+        the bound; then the mode or order)"""
         work = ctypes.c_size_t()
         launches = ctypes.c_int()
         k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
-        self._check(self._lib.sr_mle_round_plan(self.ring, k, int(num_vars), int(n_tables), int(mode), ctypes.byref(work), ctypes.byref(launches)))
+        self._check(fn(self.ring, k, int(num_vars), int(n_tables), *[int(s) for s in shape], ctypes.byref(work), ctypes.byref(launches)))
         return work.value, launches.value
+
+    def _round_dev_args(self, what, out, out_elems, out_text, tables, work, coeffs=None, n_coeffs=0, per="term", weights=None, pairs_log2=-1):
+        """the arguments the round-message device calls share: (po, ptrs, sizes, n, pc, pweights, pwork, nwork).  out_elems: what out
+        must hold (None: the library decides), out_text: how the error says it; coeffs: n_coeffs elements, one per `per`, or None;
+        weights: 2^pairs_log2 elements or None"""
+        null = ctypes.c_void_p(0)
+        po, no = self._dev(out)
+        n = len(tables)
+        if out_elems is not None and no != self.words_per_elem * out_elems:
+            raise RingError(what + ": out must hold " + out_text)
+        pwt = null
+        if weights is not None:
+            pwt, nwt = self._dev(weights)
+            if 0 <= pairs_log2 < 48 and nwt != self.words_per_elem << pairs_log2:
+                raise RingError(what + ": weights must hold one element per pair (2^%d)" % pairs_log2)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.numel())
+            ptrs[j] = self._dev(t)[0] if t.numel() else None
+        pc = null
+        if coeffs is not None:
+            pc, nc = self._dev(coeffs)
+            if nc != n_coeffs * self.words_per_elem:
+                raise RingError(what + ": one coefficient per " + per)
+        pw, nw = null, 0
+        if work is not None:
+            pw, nw = self._dev(work)
+            nw //= self.words_per_elem
+        return po, ptrs, sizes, n, pc, pwt, pw, nw
+
+    def _fold_dev_args(self, what, out_tables, sizes, n, num_vars, r, order):
+        """what a fold's device call takes besides: (optrs, osizes, pr)"""
+        if len(out_tables) != n:
+            raise RingError(what + ": one output table per table")
+        pr, nr = self._dev(r)
+        if nr != self.words_per_elem:
+            raise RingError(what + ": r is not one ring element")
+        optrs = (ctypes.c_void_p * max(n, 1))()
+        osizes = (ctypes.c_size_t * max(n, 1))()
+        for j, o in enumerate(out_tables):
+            optrs[j] = self._dev(o)[0] if o.numel() else None
+            if 2 <= num_vars < 48:
+                need = (sizes[j] + 1) // 2 if order == MLE_LEADING else min(sizes[j], 1 << (num_vars - 1))
+                if o.numel() < need * self.words_per_elem:
+                    raise RingError(what + ": an output table is shorter than the folded table")
+        return optrs, osizes, pr
+
+    def _round_host_args(self, what, out_elems, tables, coeffs=None, n_coeffs=0, per="term", weights=None):
+        """the arguments the host-pointer round calls share: (tables, weights, coeffs, out, ptrs, sizes, n); the arrays are returned so
+        that they outlive the call"""
+        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+        weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
+        n = len(tables)
+        out = np.empty(self.words_per_elem * out_elems, dtype=np.uint64)
+        ptrs = (ctypes.c_void_p * max(n, 1))()
+        sizes = (ctypes.c_size_t * max(n, 1))()
+        for j, t in enumerate(tables):
+            sizes[j] = self._batch_of(t.size)
+            ptrs[j] = t.ctypes.data if t.size else None
+        if coeffs is not None:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+            if coeffs.size != n_coeffs * self.words_per_elem:
+                raise RingError(what + ": one coefficient per " + per)
+        return tables, weights, coeffs, out, ptrs, sizes, n
+
+    def _fold_host_args(self, what, tables, r):
+        """what a fold's host-pointer call takes besides: (r, folded, optrs, osizes); tables: the arrays of _round_host_args"""
+        r = np.ascontiguousarray(r, dtype=np.uint64)
+        if r.size != self.words_per_elem:
+            raise RingError(what + ": r is not one ring element")
+        n = len(tables)
+        optrs = (ctypes.c_void_p * max(n, 1))()
+        osizes = (ctypes.c_size_t * max(n, 1))()
+        folded = [np.empty(t.size, dtype=np.uint64) for t in tables]  # never shorter than the folded table
+        for j, t in enumerate(tables):
+            optrs[j] = folded[j].ctypes.data if t.size else None
+        return r, folded, optrs, osizes
+
+    def mle_round_plan(self, num_vars, n_tables, mode=MLE_LEADING):
+        """sr_mle_round_plan: (work_elems, launches) of a sum-check round message over n_tables tables -- host arithmetic only."""
+        return self._plan_of(self._lib.sr_mle_round_plan, num_vars, n_tables, mode)
 
     def mle_round_evals_dev(self, out, tables, num_vars, mode=MLE_LEADING, work=None, stream=None):
         """sr_mle_round_evals_dev: the prover's message of a sum-check round over the product of `tables` (1 .. 4 CUDA tensors, each
@@ -969,33 +1053,14 @@ class CyclotomicRing:
         pairs of prod_j (lo_j + t (hi_j - lo_j)) for t = 0 .. len(tables), the pair being (f[2b], f[2b+1]) or (f[b], f[b + half]);
         MLE_ROUND_SUM: out = sum_b prod_j f_j[b], one element.  work: a tensor of at least mle_round_plan()[0] elements (None only
         where the plan needs none).  Allocates nothing."""
-        po, no = self._dev(out)
-        n = len(tables)
-        if no != self.words_per_elem * (1 if mode == MLE_ROUND_SUM else n + 1):
-            raise RingError("mle_round_evals: out must hold len(tables) + 1 elements (one for MLE_ROUND_SUM)")
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.numel())
-            ptrs[j] = self._dev(t)[0] if t.numel() else None
-        if work is None:
-            pw, nw = ctypes.c_void_p(0), 0
-        else:
-            pw, nw = self._dev(work)
-            nw //= self.words_per_elem
+        po, ptrs, sizes, n, _, _, pw, nw = self._round_dev_args("mle_round_evals", out, 1 if mode == MLE_ROUND_SUM else len(tables) + 1,
+                                                                "len(tables) + 1 elements (one for MLE_ROUND_SUM)", tables, work)
         self._check(self._lib.sr_mle_round_evals_dev(self._ctx, po, ptrs, sizes, n, int(num_vars), int(mode), pw, nw, self._stream(stream)))
         return out
 
     def mle_round_evals(self, tables, num_vars, mode=MLE_LEADING):
         """Host buffers: sr_mle_round_evals (see mle_round_evals_dev); returns the len(tables) + 1 elements (one for MLE_ROUND_SUM)."""
-        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-        n = len(tables)
-        out = np.empty(self.words_per_elem * (1 if mode == MLE_ROUND_SUM else n + 1), dtype=np.uint64)
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.size)
-            ptrs[j] = t.ctypes.data if t.size else None
+        tables, _, _, out, ptrs, sizes, n = self._round_host_args("mle_round_evals", 1 if mode == MLE_ROUND_SUM else len(tables) + 1, tables)
         self._check(self._lib.sr_mle_round_evals(self._ctx, _np_ptr(out), ptrs, sizes, n, int(num_vars), int(mode)))
         return out
 
@@ -1014,12 +1079,7 @@ class CyclotomicRing:
     def vpoly_round_plan(self, num_vars, n_tables, n_terms, degree, mode=MLE_LEADING):
         """sr_vpoly_round_plan: (work_elems, launches) of a round message over a sum of n_terms products of at most `degree` of
         n_tables tables -- host arithmetic only."""
-        work = ctypes.c_size_t()
-        launches = ctypes.c_int()
-        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
-        self._check(self._lib.sr_vpoly_round_plan(self.ring, k, int(num_vars), int(n_tables), int(n_terms), int(degree), int(mode),
-                                                  ctypes.byref(work), ctypes.byref(launches)))
-        return work.value, launches.value
+        return self._plan_of(self._lib.sr_vpoly_round_plan, num_vars, n_tables, n_terms, degree, mode)
 
     def vpoly_round_evals_dev(self, out, tables, terms, coeffs, num_vars, mode=MLE_LEADING, work=None, stream=None):
         """sr_vpoly_round_evals_dev: the prover's message of a sum-check round over g = sum_k c_k prod_s f_{terms[k][s]} in one pass
@@ -1027,60 +1087,27 @@ class CyclotomicRing:
         lists of 1 .. 4 indices into `tables`; coeffs: a CUDA tensor of len(terms) ring elements, or None for one() everywhere.
         MLE_LEADING / MLE_TRAILING: out[t] for t = 0 .. d, d the longest term; MLE_ROUND_SUM: out = sum_b g(b), one element.  work: a
         tensor of at least vpoly_round_plan()[0] elements (None only where the plan needs none).  Allocates nothing."""
-        po, no = self._dev(out)
-        n = len(tables)
         arr, n_terms, d = self._vpoly_terms(terms)
-        if no != self.words_per_elem * (1 if mode == MLE_ROUND_SUM else d + 1):
-            raise RingError("vpoly_round_evals: out must hold d + 1 elements, d the longest term (one for MLE_ROUND_SUM)")
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.numel())
-            ptrs[j] = self._dev(t)[0] if t.numel() else None
-        if coeffs is None:
-            pc = ctypes.c_void_p(0)
-        else:
-            pc, nc = self._dev(coeffs)
-            if nc != n_terms * self.words_per_elem:
-                raise RingError("vpoly_round_evals: one coefficient per term")
-        if work is None:
-            pw, nw = ctypes.c_void_p(0), 0
-        else:
-            pw, nw = self._dev(work)
-            nw //= self.words_per_elem
+        po, ptrs, sizes, n, pc, _, pw, nw = self._round_dev_args("vpoly_round_evals", out, 1 if mode == MLE_ROUND_SUM else d + 1,
+                                                                 "d + 1 elements, d the longest term (one for MLE_ROUND_SUM)", tables, work,
+                                                                 coeffs, n_terms)
         self._check(self._lib.sr_vpoly_round_evals_dev(self._ctx, po, ptrs, sizes, n, arr, n_terms, pc, int(num_vars), int(mode), pw, nw,
                                                        self._stream(stream)))
         return out
 
     def vpoly_round_evals(self, tables, terms, coeffs, num_vars, mode=MLE_LEADING):
         """Host buffers: sr_vpoly_round_evals (see vpoly_round_evals_dev); returns the d + 1 elements (one for MLE_ROUND_SUM)."""
-        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-        n = len(tables)
         arr, n_terms, d = self._vpoly_terms(terms)
-        out = np.empty(self.words_per_elem * (1 if mode == MLE_ROUND_SUM else max(d, 1) + 1), dtype=np.uint64)
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.size)
-            ptrs[j] = t.ctypes.data if t.size else None
-        pc = None
-        if coeffs is not None:
-            coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
-            if coeffs.size != n_terms * self.words_per_elem:
-                raise RingError("vpoly_round_evals: one coefficient per term")
-            pc = coeffs.ctypes.data
-        self._check(self._lib.sr_vpoly_round_evals(self._ctx, _np_ptr(out), ptrs, sizes, n, arr, n_terms, pc, int(num_vars), int(mode)))
+        tables, _, coeffs, out, ptrs, sizes, n = self._round_host_args("vpoly_round_evals", 1 if mode == MLE_ROUND_SUM else max(d, 1) + 1,
+                                                                       tables, coeffs, n_terms)
+        self._check(self._lib.sr_vpoly_round_evals(self._ctx, _np_ptr(out), ptrs, sizes, n, arr, n_terms,
+                                                   None if coeffs is None else coeffs.ctypes.data, int(num_vars), int(mode)))
         return out
 
     def mle_round_fold_plan(self, num_vars, n_tables, order=MLE_LEADING):
         """sr_mle_round_fold_plan: (work_elems, launches) of the fused fold-and-round call over n_tables tables of num_vars >= 2
         variables -- host arithmetic only."""
-        work = ctypes.c_size_t()
-        launches = ctypes.c_int()
-        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
-        self._check(self._lib.sr_mle_round_fold_plan(self.ring, k, int(num_vars), int(n_tables), int(order), ctypes.byref(work),
-                                                     ctypes.byref(launches)))
-        return work.value, launches.value
+        return self._plan_of(self._lib.sr_mle_round_fold_plan, num_vars, n_tables, order)
 
     def mle_round_fold_evals_dev(self, out, out_tables, tables, num_vars, r, order=MLE_LEADING, work=None, stream=None):
         """sr_mle_round_fold_evals_dev: one pass that folds every table of `tables` (1 .. 4 CUDA tensors of n_evals <= 2^num_vars
@@ -1089,54 +1116,18 @@ class CyclotomicRing:
         (mle_round_evals_dev on them).  out_tables[j] must hold at least the folded length; MLE_TRAILING may fold in place
         (out_tables[j] is tables[j]).  Returns the list of elements written per table; nothing beyond them is touched.  work: a tensor
         of at least mle_round_fold_plan()[0] elements (None only where the plan needs none).  Allocates nothing."""
-        po, no = self._dev(out)
-        n = len(tables)
-        if len(out_tables) != n:
-            raise RingError("mle_round_fold_evals: one output table per table")
-        if no != self.words_per_elem * (n + 1):
-            raise RingError("mle_round_fold_evals: out must hold len(tables) + 1 elements")
-        pr, nr = self._dev(r)
-        if nr != self.words_per_elem:
-            raise RingError("mle_round_fold_evals: r is not one ring element")
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        optrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        osizes = (ctypes.c_size_t * max(n, 1))()
-        for j, (t, o) in enumerate(zip(tables, out_tables)):
-            sizes[j] = self._batch_of(t.numel())
-            ptrs[j] = self._dev(t)[0] if t.numel() else None
-            optrs[j] = self._dev(o)[0] if o.numel() else None
-            if 2 <= num_vars < 48:
-                need = (sizes[j] + 1) // 2 if order == MLE_LEADING else min(sizes[j], 1 << (num_vars - 1))
-                if o.numel() < need * self.words_per_elem:
-                    raise RingError("mle_round_fold_evals: an output table is shorter than the folded table")
-        if work is None:
-            pw, nw = ctypes.c_void_p(0), 0
-        else:
-            pw, nw = self._dev(work)
-            nw //= self.words_per_elem
+        what = "mle_round_fold_evals"
+        po, ptrs, sizes, n, _, _, pw, nw = self._round_dev_args(what, out, len(tables) + 1, "len(tables) + 1 elements", tables, work)
+        optrs, osizes, pr = self._fold_dev_args(what, out_tables, sizes, n, num_vars, r, order)
         self._check(self._lib.sr_mle_round_fold_evals_dev(self._ctx, po, optrs, osizes, ptrs, sizes, n, int(num_vars), pr, int(order), pw, nw,
                                                           self._stream(stream)))
         return [int(osizes[j]) for j in range(n)]
 
     def mle_round_fold_evals(self, tables, num_vars, r, order=MLE_LEADING):
         """Host buffers: sr_mle_round_fold_evals (see mle_round_fold_evals_dev); returns (message, list of folded tables)."""
-        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-        r = np.ascontiguousarray(r, dtype=np.uint64)
-        n, w = len(tables), self.words_per_elem
-        if r.size != w:
-            raise RingError("mle_round_fold_evals: r is not one ring element")
-        out = np.empty(w * (n + 1), dtype=np.uint64)
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        optrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        osizes = (ctypes.c_size_t * max(n, 1))()
-        folded = []
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.size)
-            ptrs[j] = t.ctypes.data if t.size else None
-            folded.append(np.empty(t.size, dtype=np.uint64))  # never shorter than the folded table
-            optrs[j] = folded[j].ctypes.data if t.size else None
+        what, w = "mle_round_fold_evals", self.words_per_elem
+        tables, _, _, out, ptrs, sizes, n = self._round_host_args(what, len(tables) + 1, tables)
+        r, folded, optrs, osizes = self._fold_host_args(what, tables, r)
         self._check(self._lib.sr_mle_round_fold_evals(self._ctx, _np_ptr(out), optrs, osizes, ptrs, sizes, n, int(num_vars), _np_ptr(r),
                                                       int(order)))
         return out, [f[:int(osizes[j]) * w] for j, f in enumerate(folded)]
@@ -1144,12 +1135,7 @@ class CyclotomicRing:
     def vpoly_round_fold_plan(self, num_vars, n_tables, n_terms, degree, order=MLE_LEADING):
         """sr_vpoly_round_fold_plan: (work_elems, launches) of the fused fold-and-round call over a sum of n_terms products of at
         most `degree` of n_tables tables of num_vars >= 2 variables -- host arithmetic only."""
-        work = ctypes.c_size_t()
-        launches = ctypes.c_int()
-        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
-        self._check(self._lib.sr_vpoly_round_fold_plan(self.ring, k, int(num_vars), int(n_tables), int(n_terms), int(degree), int(order),
-                                                       ctypes.byref(work), ctypes.byref(launches)))
-        return work.value, launches.value
+        return self._plan_of(self._lib.sr_vpoly_round_fold_plan, num_vars, n_tables, n_terms, degree, order)
 
     def vpoly_round_fold_evals_dev(self, out, out_tables, tables, terms, coeffs, num_vars, r, order=MLE_LEADING, work=None, stream=None):
         """sr_vpoly_round_fold_evals_dev: one pass that folds every table slot of `tables` (1 .. 8 CUDA tensors of n_evals <=
@@ -1159,79 +1145,24 @@ class CyclotomicRing:
         vpoly_round_evals_dev.  out_tables[j] must hold at least the folded length; MLE_TRAILING may fold in place (out_tables[j] is
         tables[j]).  Returns the list of elements written per table; nothing beyond them is touched.  work: a tensor of at least
         vpoly_round_fold_plan()[0] elements (None only where the plan needs none).  Allocates nothing."""
-        po, no = self._dev(out)
-        n = len(tables)
+        what = "vpoly_round_fold_evals"
         arr, n_terms, d = self._vpoly_terms(terms)
-        if len(out_tables) != n:
-            raise RingError("vpoly_round_fold_evals: one output table per table")
-        if no != self.words_per_elem * (d + 1):
-            raise RingError("vpoly_round_fold_evals: out must hold d + 1 elements, d the longest term")
-        pr, nr = self._dev(r)
-        if nr != self.words_per_elem:
-            raise RingError("vpoly_round_fold_evals: r is not one ring element")
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        optrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        osizes = (ctypes.c_size_t * max(n, 1))()
-        for j, (t, o) in enumerate(zip(tables, out_tables)):
-            sizes[j] = self._batch_of(t.numel())
-            ptrs[j] = self._dev(t)[0] if t.numel() else None
-            optrs[j] = self._dev(o)[0] if o.numel() else None
-            if 2 <= num_vars < 48:
-                need = (sizes[j] + 1) // 2 if order == MLE_LEADING else min(sizes[j], 1 << (num_vars - 1))
-                if o.numel() < need * self.words_per_elem:
-                    raise RingError("vpoly_round_fold_evals: an output table is shorter than the folded table")
-        if coeffs is None:
-            pc = ctypes.c_void_p(0)
-        else:
-            pc, nc = self._dev(coeffs)
-            if nc != n_terms * self.words_per_elem:
-                raise RingError("vpoly_round_fold_evals: one coefficient per term")
-        if work is None:
-            pw, nw = ctypes.c_void_p(0), 0
-        else:
-            pw, nw = self._dev(work)
-            nw //= self.words_per_elem
+        po, ptrs, sizes, n, pc, _, pw, nw = self._round_dev_args(what, out, d + 1, "d + 1 elements, d the longest term", tables, work, coeffs,
+                                                                 n_terms)
+        optrs, osizes, pr = self._fold_dev_args(what, out_tables, sizes, n, num_vars, r, order)
         self._check(self._lib.sr_vpoly_round_fold_evals_dev(self._ctx, po, optrs, osizes, ptrs, sizes, n, arr, n_terms, pc, int(num_vars), pr,
                                                             int(order), pw, nw, self._stream(stream)))
         return [int(osizes[j]) for j in range(n)]
 
     def vpoly_round_fold_evals(self, tables, terms, coeffs, num_vars, r, order=MLE_LEADING):
         """Host buffers: sr_vpoly_round_fold_evals (see vpoly_round_fold_evals_dev); returns (message, list of folded tables)."""
-        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-        r = np.ascontiguousarray(r, dtype=np.uint64)
-        n, w = len(tables), self.words_per_elem
+        what, w = "vpoly_round_fold_evals", self.words_per_elem
         arr, n_terms, d = self._vpoly_terms(terms)
-        if r.size != w:
-            raise RingError("vpoly_round_fold_evals: r is not one ring element")
-        out = np.empty(w * (max(d, 1) + 1), dtype=np.uint64)
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        optrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        osizes = (ctypes.c_size_t * max(n, 1))()
-        folded = []
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.size)
-            ptrs[j] = t.ctypes.data if t.size else None
-            folded.append(np.empty(t.size, dtype=np.uint64))  # never shorter than the folded table
-            optrs[j] = folded[j].ctypes.data if t.size else None
-        pc = None
-        if coeffs is not None:
-            coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
-            if coeffs.size != n_terms * w:
-                raise RingError("vpoly_round_fold_evals: one coefficient per term")
-            pc = coeffs.ctypes.data
-        self._check(self._lib.sr_vpoly_round_fold_evals(self._ctx, _np_ptr(out), optrs, osizes, ptrs, sizes, n, arr, n_terms, pc, int(num_vars),
-                                                        _np_ptr(r), int(order)))
+        tables, _, coeffs, out, ptrs, sizes, n = self._round_host_args(what, max(d, 1) + 1, tables, coeffs, n_terms)
+        r, folded, optrs, osizes = self._fold_host_args(what, tables, r)
+        self._check(self._lib.sr_vpoly_round_fold_evals(self._ctx, _np_ptr(out), optrs, osizes, ptrs, sizes, n, arr, n_terms,
+                                                        None if coeffs is None else coeffs.ctypes.data, int(num_vars), _np_ptr(r), int(order)))
         return out, [f[:int(osizes[j]) * w] for j, f in enumerate(folded)]
-
-    def _plan_of(self, fn, num_vars, n_tables, n_terms, degree, order):
-        work = ctypes.c_size_t()
-        launches = ctypes.c_int()
-        k = self.degree.bit_length() - 1 if self.ring <= STARK_POW2 else 0
-        self._check(fn(self.ring, k, int(num_vars), int(n_tables), int(n_terms), int(degree), int(order), ctypes.byref(work),
-                       ctypes.byref(launches)))
-        return work.value, launches.value
 
     def vpoly_wround_plan(self, num_vars, n_tables, n_terms, degree, order=MLE_LEADING):
         """sr_vpoly_wround_plan: (work_elems, launches) of a weighted round message (vpoly_wround_evals_dev) -- host arithmetic only."""
@@ -1242,45 +1173,15 @@ class CyclotomicRing:
         num_vars >= 2 -- host arithmetic only."""
         return self._plan_of(self._lib.sr_vpoly_wround_fold_plan, num_vars, n_tables, n_terms, degree, order)
 
-    def _wround_dev_args(self, what, out, weights, pairs_log2, tables, terms, coeffs, work):
-        """the arguments the two weighted device calls share: (po, pw8, ptrs, sizes, n, arr, n_terms, pc, pwork, nwork)"""
-        po, no = self._dev(out)
-        n = len(tables)
-        arr, n_terms, d = self._vpoly_terms(terms)
-        if no != self.words_per_elem * (d + 1):
-            raise RingError(what + ": out must hold d + 1 elements, d the longest term")
-        if weights is None:
-            pwt = ctypes.c_void_p(0)
-        else:
-            pwt, nwt = self._dev(weights)
-            if 0 <= pairs_log2 < 48 and nwt != self.words_per_elem << pairs_log2:
-                raise RingError(what + ": weights must hold one element per pair (2^%d)" % pairs_log2)
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.numel())
-            ptrs[j] = self._dev(t)[0] if t.numel() else None
-        if coeffs is None:
-            pc = ctypes.c_void_p(0)
-        else:
-            pc, nc = self._dev(coeffs)
-            if nc != n_terms * self.words_per_elem:
-                raise RingError(what + ": one coefficient per term")
-        if work is None:
-            pw, nw = ctypes.c_void_p(0), 0
-        else:
-            pw, nw = self._dev(work)
-            nw //= self.words_per_elem
-        return po, pwt, ptrs, sizes, n, arr, n_terms, pc, pw, nw
-
     def _vpoly_wround_evals_dev(self, out, weights, tables, terms, coeffs, num_vars, order=MLE_LEADING, work=None, stream=None):
         """sr_vpoly_wround_evals_dev (public as stark_rings_amd.wsumcheck.vpoly_wround_evals_dev): the round message of
         vpoly_round_evals_dev with a per-pair weight,
         out[t] = sum_{b < half} weights[b] * sum_k c_k prod_s (lo_s[b] + t (hi_s[b] - lo_s[b])), t = 0 .. d (d the longest term; the
         weight is not a factor).  weights: a CUDA tensor of 2^(num_vars - 1) ring elements, one per pair, never written; order:
         MLE_LEADING or MLE_TRAILING.  The rest as vpoly_round_evals_dev.  work: at least vpoly_wround_plan()[0] elements."""
-        po, pwt, ptrs, sizes, n, arr, n_terms, pc, pw, nw = self._wround_dev_args("vpoly_wround_evals", out, weights, num_vars - 1, tables, terms,
-                                                                                  coeffs, work)
+        arr, n_terms, d = self._vpoly_terms(terms)
+        po, ptrs, sizes, n, pc, pwt, pw, nw = self._round_dev_args("vpoly_wround_evals", out, d + 1, "d + 1 elements, d the longest term", tables,
+                                                                   work, coeffs, n_terms, "term", weights, num_vars - 1)
         self._check(self._lib.sr_vpoly_wround_evals_dev(self._ctx, po, pwt, ptrs, sizes, n, arr, n_terms, pc, int(num_vars), int(order), pw, nw,
                                                         self._stream(stream)))
         return out
@@ -1292,46 +1193,20 @@ class CyclotomicRing:
         `r` into out_tables exactly as there, and out[t], t = 0 .. d, is vpoly_wround_evals_dev on the folded tables at num_vars - 1
         with the same `weights` (2^(num_vars - 2) ring elements).  Returns the list of elements written per table.  work: at least
         vpoly_wround_fold_plan()[0] elements."""
-        po, pwt, ptrs, sizes, n, arr, n_terms, pc, pw, nw = self._wround_dev_args("vpoly_wround_fold_evals", out, weights, num_vars - 2, tables,
-                                                                                  terms, coeffs, work)
-        if len(out_tables) != n:
-            raise RingError("vpoly_wround_fold_evals: one output table per table")
-        pr, nr = self._dev(r)
-        if nr != self.words_per_elem:
-            raise RingError("vpoly_wround_fold_evals: r is not one ring element")
-        optrs = (ctypes.c_void_p * max(n, 1))()
-        osizes = (ctypes.c_size_t * max(n, 1))()
-        for j, o in enumerate(out_tables):
-            optrs[j] = self._dev(o)[0] if o.numel() else None
-            if 2 <= num_vars < 48:
-                need = (sizes[j] + 1) // 2 if order == MLE_LEADING else min(sizes[j], 1 << (num_vars - 1))
-                if o.numel() < need * self.words_per_elem:
-                    raise RingError("vpoly_wround_fold_evals: an output table is shorter than the folded table")
+        what = "vpoly_wround_fold_evals"
+        arr, n_terms, d = self._vpoly_terms(terms)
+        po, ptrs, sizes, n, pc, pwt, pw, nw = self._round_dev_args(what, out, d + 1, "d + 1 elements, d the longest term", tables, work, coeffs,
+                                                                   n_terms, "term", weights, num_vars - 2)
+        optrs, osizes, pr = self._fold_dev_args(what, out_tables, sizes, n, num_vars, r, order)
         self._check(self._lib.sr_vpoly_wround_fold_evals_dev(self._ctx, po, optrs, osizes, pwt, ptrs, sizes, n, arr, n_terms, pc, int(num_vars),
                                                              pr, int(order), pw, nw, self._stream(stream)))
         return [int(osizes[j]) for j in range(n)]
 
-    def _wround_host_args(self, what, weights, tables, terms, coeffs):
-        tables = [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
-        weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64)
-        n, w = len(tables), self.words_per_elem
-        arr, n_terms, d = self._vpoly_terms(terms)
-        out = np.empty(w * (max(d, 1) + 1), dtype=np.uint64)
-        ptrs = (ctypes.c_void_p * max(n, 1))()
-        sizes = (ctypes.c_size_t * max(n, 1))()
-        for j, t in enumerate(tables):
-            sizes[j] = self._batch_of(t.size)
-            ptrs[j] = t.ctypes.data if t.size else None
-        if coeffs is not None:
-            coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
-            if coeffs.size != n_terms * w:
-                raise RingError(what + ": one coefficient per term")
-        # the arrays are returned so that they outlive the call
-        return tables, weights, coeffs, out, ptrs, sizes, n, arr, n_terms
-
     def vpoly_wround_evals(self, weights, tables, terms, coeffs, num_vars, order=MLE_LEADING):
         """Host buffers: sr_vpoly_wround_evals (see vpoly_wround_evals_dev); returns the d + 1 elements."""
-        tables, weights, coeffs, out, ptrs, sizes, n, arr, n_terms = self._wround_host_args("vpoly_wround_evals", weights, tables, terms, coeffs)
+        arr, n_terms, d = self._vpoly_terms(terms)
+        tables, weights, coeffs, out, ptrs, sizes, n = self._round_host_args("vpoly_wround_evals", max(d, 1) + 1, tables, coeffs, n_terms, "term",
+                                                                             weights)
         if weights is not None and 1 <= num_vars < 48 and weights.size != self.words_per_elem << (num_vars - 1):
             raise RingError("vpoly_wround_evals: weights must hold one element per pair")
         self._check(self._lib.sr_vpoly_wround_evals(self._ctx, _np_ptr(out), None if weights is None else weights.ctypes.data, ptrs, sizes, n, arr,
@@ -1340,20 +1215,12 @@ class CyclotomicRing:
 
     def vpoly_wround_fold_evals(self, weights, tables, terms, coeffs, num_vars, r, order=MLE_LEADING):
         """Host buffers: sr_vpoly_wround_fold_evals (see vpoly_wround_fold_evals_dev); returns (message, list of folded tables)."""
-        tables, weights, coeffs, out, ptrs, sizes, n, arr, n_terms = self._wround_host_args("vpoly_wround_fold_evals", weights, tables, terms,
-                                                                                            coeffs)
-        r = np.ascontiguousarray(r, dtype=np.uint64)
-        w = self.words_per_elem
-        if r.size != w:
-            raise RingError("vpoly_wround_fold_evals: r is not one ring element")
+        what, w = "vpoly_wround_fold_evals", self.words_per_elem
+        arr, n_terms, d = self._vpoly_terms(terms)
+        tables, weights, coeffs, out, ptrs, sizes, n = self._round_host_args(what, max(d, 1) + 1, tables, coeffs, n_terms, "term", weights)
+        r, folded, optrs, osizes = self._fold_host_args(what, tables, r)
         if weights is not None and 2 <= num_vars < 48 and weights.size != w << (num_vars - 2):
             raise RingError("vpoly_wround_fold_evals: weights must hold one element per pair of the folded tables")
-        optrs = (ctypes.c_void_p * max(n, 1))()
-        osizes = (ctypes.c_size_t * max(n, 1))()
-        folded = []
-        for j, t in enumerate(tables):
-            folded.append(np.empty(t.size, dtype=np.uint64))  # never shorter than the folded table
-            optrs[j] = folded[j].ctypes.data if t.size else None
         self._check(self._lib.sr_vpoly_wround_fold_evals(self._ctx, _np_ptr(out), optrs, osizes, None if weights is None else weights.ctypes.data,
                                                          ptrs, sizes, n, arr, n_terms, None if coeffs is None else coeffs.ctypes.data,
                                                          int(num_vars), _np_ptr(r), int(order)))

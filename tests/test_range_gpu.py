@@ -471,6 +471,8 @@ def test_every_device_refusal_names_its_reason_and_launches_nothing(torch_cuda):
                     (dict(work_p=cp), "d_work overlaps d_coeffs")):
         rc, err = call(**kw)
         assert rc == 1 and msg in err and err.startswith("range_wround: "), (kw, rc, err)
+    rc, err = call(num_vars=47, sizes=(ctypes.c_size_t * 8)(1 << 45, 1 << 45))  # within 2^num_vars, beyond what a context addresses
+    assert rc == 1 and err == "element count too large", (rc, err)
     torch.cuda.synchronize()
     for t in (out, work):
         assert bool((t == canary).all())

@@ -420,7 +420,7 @@ def test_every_refusal_names_its_reason_and_launches_nothing(torch_cuda):
         (but(nt=0), "n_tables must be 1 .. 4"), (but(nt=5), "n_tables must be 1 .. 4"),
         (but(order=2), "unknown order"), (but(order=-1), "unknown order"),
         (but(num_vars=48), "num_vars must be below 48"), (but(num_vars=1, sizes=[2, 2]), "num_vars >= 2"), (but(num_vars=0, sizes=[1, 1]), "num_vars >= 2"),
-        (but(sizes=[full, full + 1]), "n_evals exceeds 2^num_vars"),
+        (but(sizes=[full, full + 1]), "n_evals exceeds 2^num_vars"), (but(num_vars=47, sizes=[1 << 45, 1 << 45]), "element count too large"),
         (but(work_n=need - 1), "workspace too small"),
         (but(out_p=wp + eb), "d_out overlaps d_work"), (but(out_p=rp), "d_out overlaps d_r"), (but(work_p=rp), "d_work overlaps d_r"),
         (but(out_p=fp + eb), "d_out overlaps a table"), (but(work_p=f2p), "d_work overlaps a table"), (but(r_p=fp + 3 * eb), "d_r overlaps a table"),

@@ -465,6 +465,7 @@ def test_every_refusal_names_its_reason_and_launches_nothing(torch_cuda):
         ((op, [fp, fp], [full, full], 2, 48, LEADING, wp, need), "num_vars must be below 48"),
         ((op, [fp, fp], [1, 1], 2, 0, TRAILING, wp, need), "num_vars >= 1"),
         ((op, [fp, fp], [full, full + 1], 2, nv, LEADING, wp, need), "n_evals exceeds 2^num_vars"),
+        ((op, [fp, fp], [1 << 45, 1 << 45], 2, 47, LEADING, wp, need), "element count too large"),
         ((op, [fp, fp], [full, full], 2, nv, LEADING, wp, need - 1), "workspace too small"),
         ((fp + 8 * w, [fp, fp], [full, full], 2, nv, LEADING, wp, need), "d_out overlaps a table"),
         ((op, [fp, fp], [full, full], 2, nv, LEADING, fp, need), "d_work overlaps a table"),

@@ -515,6 +515,8 @@ def test_every_refusal_names_its_reason_and_launches_nothing(torch_cuda):
     for kw, msg in bad:
         rc, err = call(**kw)
         assert rc == 1 and msg in err and err.startswith("vpoly_round_fold: "), (kw, rc, err)
+    rc, err = call(**but(num_vars=47, sizes=[1 << 45, 1 << 45]))  # within 2^num_vars, beyond what a context addresses
+    assert rc == 1 and err == "element count too large", (rc, err)
     torch.cuda.synchronize()
     for t in (out, work, g, g2):
         assert bool((t == canary).all())

@@ -598,6 +598,7 @@ def test_every_refusal_names_its_reason_and_launches_nothing(torch_cuda):
         (dict(nv=48), "num_vars must be below 48"),
         (dict(nv=0, sizes=[1] * 4, mode=TRAILING), "num_vars >= 1"),
         (dict(sizes=[full, full, full + 1, full]), "n_evals exceeds 2^num_vars"),
+        (dict(nv=47, sizes=[1 << 45] * 4), "element count too large"),
         (dict(need=need - 1), "workspace too small"),
         (dict(out=fp + 8 * w), "d_out overlaps a table"),
         (dict(work=fp), "d_work overlaps a table"),

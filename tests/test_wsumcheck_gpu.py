@@ -551,13 +551,28 @@ def test_every_device_refusal_names_its_reason_and_launches_nothing(torch_cuda):
     eb = 8 * w
     pa, sa, oa = (ctypes.c_void_p * 8)(fp, f2p), (ctypes.c_size_t * 8)(full, full), (ctypes.c_void_p * 8)(gp, g2p)
 
-    def rnd(out_p=op, wts=wtp, num_vars=nv, order=LEADING, work_p=wp, work_n=16):
-        rc = lib.sr_vpoly_wround_evals_dev(ctx, out_p, wts, pa, sa, 2, arr, 2, cp, num_vars, order, work_p, work_n, st)
+    def rnd(out_p=op, wts=wtp, num_vars=nv, order=LEADING, work_p=wp, work_n=16, co_p=cp, tabs=pa, sizes=sa, terms=arr):
+        rc = lib.sr_vpoly_wround_evals_dev(ctx, out_p, wts, tabs, sizes, 2, terms, 2, co_p, num_vars, order, work_p, work_n, st)
         return rc, _lib.last_error()
 
-    def fold(out_p=op, wts=wtp, num_vars=nv, order=LEADING, work_p=wp, work_n=16, outs=oa, r_p=rp):
-        rc = lib.sr_vpoly_wround_fold_evals_dev(ctx, out_p, outs, n_out, wts, pa, sa, 2, arr, 2, cp, num_vars, r_p, order, work_p, work_n, st)
+    def fold(out_p=op, wts=wtp, num_vars=nv, order=LEADING, work_p=wp, work_n=16, outs=oa, r_p=rp, co_p=cp, tabs=pa, sizes=sa, terms=arr):
+        rc = lib.sr_vpoly_wround_fold_evals_dev(ctx, out_p, outs, n_out, wts, tabs, sizes, 2, terms, 2, co_p, num_vars, r_p, order, work_p, work_n, st)
         return rc, _lib.last_error()
+
+    def terms_of(*lists):
+        t = (VPolyTerm * 8)()
+        for i, idx in enumerate(lists):
+            t[i].n_factors = len(idx)
+            for s, j in enumerate(idx[:4]):
+                t[i].table[s] = j
+        return t
+
+    # what the two weighted families share with the sum-of-products checks: the same text under either prefix
+    shared = [(dict(terms=terms_of([0, 1], [])), "n_factors must be 1 .. 4 (term 1)"), (dict(terms=terms_of([0, 1, 0, 1, 0], [1])), "n_factors must be"),
+              (dict(terms=terms_of([0, 2], [1])), "table index outside 0 .. n_tables - 1 (term 0)"),
+              (dict(terms=terms_of([0, 0], [0])), "a table that no term uses"),
+              (dict(sizes=(ctypes.c_size_t * 8)(full, full + 1)), "n_evals exceeds 2^num_vars"),
+              (dict(tabs=(ctypes.c_void_p * 8)(fp, None)), "null pointer (a table)"), (dict(work_p=None), "null pointer (d_work)")]
 
     for call, prefix, cases in (
             (rnd, "vpoly_wround: ", [(dict(wts=None), "null pointer (d_weights)"), (dict(order=2), "SR_MLE_ROUND_SUM"), (dict(order=3), "unknown order"),
@@ -565,16 +580,29 @@ def test_every_device_refusal_names_its_reason_and_launches_nothing(torch_cuda):
                                      (dict(out_p=None), "null pointer"), (dict(work_p=None), "null pointer"), (dict(work_n=need_r - 1), "workspace too small"),
                                      (dict(out_p=wtp + eb), "d_out overlaps d_weights"), (dict(work_p=wtp), "d_work overlaps d_weights"),
                                      (dict(out_p=fp + eb), "d_out overlaps a table"), (dict(out_p=wp + eb), "d_out overlaps d_work"),
-                                     (dict(out_p=cp + eb), "d_out overlaps d_coeffs")]),
+                                     (dict(out_p=cp + eb), "d_out overlaps d_coeffs"), (dict(work_p=f2p), "d_work overlaps a table"),
+                                     (dict(work_p=cp), "d_work overlaps d_coeffs"), (dict(co_p=f2p + eb), "d_coeffs overlaps a table")] + shared),
             (fold, "vpoly_wround_fold: ", [(dict(wts=None), "null pointer (d_weights)"), (dict(order=2), "unknown order"), (dict(num_vars=1), "num_vars >= 2"),
                                           (dict(r_p=None), "null pointer"), (dict(work_n=need - 1), "workspace too small"),
                                           (dict(out_p=wtp + eb), "d_out overlaps d_weights"), (dict(work_p=wtp), "d_work overlaps d_weights"),
                                           (dict(outs=(ctypes.c_void_p * 8)(gp, wtp)), "a folded table overlaps d_weights"),
                                           (dict(out_p=rp), "d_out overlaps d_r"), (dict(outs=(ctypes.c_void_p * 8)(gp, gp)), "two folded tables overlap"),
-                                          (dict(outs=(ctypes.c_void_p * 8)(fp, g2p)), "only a trailing-order fold may run in place")])):
+                                          (dict(outs=(ctypes.c_void_p * 8)(fp, g2p)), "only a trailing-order fold may run in place"),
+                                          (dict(outs=(ctypes.c_void_p * 8)(fp, g2p), tabs=(ctypes.c_void_p * 8)(fp, fp), order=TRAILING),
+                                           "appears twice cannot be folded in place"),
+                                          (dict(out_p=wp + eb), "d_out overlaps d_work"), (dict(work_p=rp), "d_work overlaps d_r"),
+                                          (dict(out_p=cp + eb), "d_out overlaps d_coeffs"), (dict(work_p=cp), "d_work overlaps d_coeffs"),
+                                          (dict(r_p=cp + eb), "d_r overlaps d_coeffs"), (dict(co_p=f2p + eb), "d_coeffs overlaps a table"),
+                                          (dict(co_p=g2p + eb), "d_coeffs overlaps a folded table"),
+                                          (dict(out_p=fp + eb), "d_out overlaps a table"), (dict(work_p=f2p), "d_work overlaps a table"),
+                                          (dict(r_p=fp + 3 * eb), "d_r overlaps a table"), (dict(out_p=gp + eb), "d_out overlaps a folded table"),
+                                          (dict(work_p=g2p), "d_work overlaps a folded table"),
+                                          (dict(r_p=g2p + eb), "d_r overlaps a folded table")] + shared)):
         for kw, msg in cases:
             rc, err = call(**kw)
             assert rc == 1 and msg in err and err.startswith(prefix), (kw, rc, err)
+        rc, err = call(num_vars=47, sizes=(ctypes.c_size_t * 8)(1 << 45, 1 << 45))  # within 2^num_vars, beyond what a context addresses
+        assert rc == 1 and err == "element count too large", (rc, err)
     torch.cuda.synchronize()
     for t in (out, work, g, g2):
         assert bool((t == canary).all())
