@@ -447,9 +447,30 @@ public:
         CyclotomicConfig::check(sr_product_batch(cfg_.raw(), out.data(), w_.empty() ? dummy_word() : w_.data(), len()), "RqNTT product");
         return RqNTTVec(cfg_, std::move(out));
     }
+    // Field::inverse / ark_ff::batch_inversion on every slot of every element (sr_inverse_batch): 1 / self[e], and self[e] / den[e].  A
+    // zero slot gives zero -- batch_inversion leaves zeros in place -- and is counted: inverse_zero_count() == 0 afterwards is the
+    // `Some` of Field::inverse for every element.
+    RqNTTVec inverse() const { return quotient(nullptr, *this); }
+    RqNTTVec divide(const RqNTTVec &den) const {
+        if (den.w_.size() != w_.size()) throw std::length_error("operand lengths differ");
+        return quotient(this, den);
+    }
+    // sr_inverse_zero_count: the zero slots the calls above met on this configuration's context since the last read; clears the count
+    unsigned long long inverse_zero_count() const {
+        unsigned long long n = 0;
+        CyclotomicConfig::check(sr_inverse_zero_count(cfg_.raw(), &n, nullptr), "sr_inverse_zero_count");
+        return n;
+    }
     std::vector<uint64_t> into_words() && { return std::move(w_); }
 
 private:
+    static RqNTTVec quotient(const RqNTTVec *num, const RqNTTVec &den) {
+        std::vector<uint64_t> out(den.w_.size());
+        CyclotomicConfig::check(sr_inverse_batch(den.cfg_.raw(), out.empty() ? dummy_word() : out.data(), num && !num->w_.empty() ? num->w_.data() : nullptr,
+                                                 den.w_.empty() ? dummy_word() : den.w_.data(), den.len()),
+                                "RqNTT inverse");
+        return RqNTTVec(den.cfg_, std::move(out));
+    }
     static uint64_t *dummy_word() {
         static uint64_t z = 0;
         return &z;
@@ -615,6 +636,14 @@ public:
                                     "DenseMultilinearExtension +=");
         return *this;
     }
+    // the tables 1 / self[b] and self[b] / other[b] over the stored evaluations (RqNTTVec::inverse / divide); the implicit zero tail stays
+    // implicit.  Zero slots give zero and are counted (inverse_zero_count).
+    DenseMultilinearExtension inverse() const { return DenseMultilinearExtension(cfg_, nv_, RqNTTVec(cfg_, w_).inverse().into_words()); }
+    DenseMultilinearExtension divide(const DenseMultilinearExtension &other) const {
+        if (other.nv_ != nv_ || other.w_.size() != w_.size()) throw std::length_error("divide: the operands differ in num_vars or stored length");
+        return DenseMultilinearExtension(cfg_, nv_, RqNTTVec(cfg_, w_).divide(RqNTTVec(cfg_, other.w_)).into_words());
+    }
+    unsigned long long inverse_zero_count() const { return RqNTTVec(cfg_, {}).inverse_zero_count(); }
     // sum_k coeffs[k] * mles[k] (+ constant) from 1 .. 16 MLEs of one ring and one num_vars in one pass (sr_lincomb): MulAssign<R>,
     // AddAssign<(R, &Self)> and Add<R> of dense.rs composed.  coeffs: one ring element per MLE; constant: one ring element or null.  The
     // inputs may be truncated; the result stores the longest input's evaluations, or all 2^num_vars with a constant (which goes to every

@@ -650,6 +650,32 @@ int sr_lincomb_index(sr_ctx *ctx, uint64_t *const *outs, int n_outputs, const ui
                      const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n);
 int sr_index_count_dev(sr_ctx *ctx, uint64_t *d_counts, const uint64_t *d_idx, size_t n, size_t n_bins, void *stream);
 int sr_index_count(sr_ctx *ctx, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins);
+/* Batch inversion (csrc/inverse.hpp): out[e] = num[e] * den[e]^-1 for e < n, slot by slot on tables in CRT / NTT form -- Field::inverse
+ * / ark_ff::batch_inversion(&mut [F]) on every slot: the base field of a power-of-two ring, the Fq3 / Fq9 / Fq4 slots of goldilocks24 /
+ * babybear72 / frog16.  d_num == NULL: every numerator is one().  `*` is the slot product (sr_pointwise_mul_batch), so for a ring
+ * element a none of whose slots is zero, the result is the inverse of a in the ring.
+ * Montgomery's trick: a lane inverts `chunk_elems` consecutive elements of its unit with ONE field inversion x^(|F| - 2) -- three
+ * products per element and unit (four with numerators) plus the inversion shared by the chunk.
+ * Zeros: a zero slot of den[e] cannot be inverted.  It does not disturb its neighbours; its output slot is ZERO, with or without a
+ * numerator (batch_inversion leaves zeros in place), and it is added to a context counter that sr_inverse_zero_count reads and clears
+ * (ordered on `stream`, like sr_spmv_bad_index_count).  The count is in slots: base-field coefficients of a power-of-two ring, Fq3 /
+ * Fq9 / Fq4 slots otherwise.  A ring element is a unit exactly when none of its slots is zero, so a count of 0 says that every element
+ * was invertible -- the `Some` of Field::inverse for the whole table.
+ * Canonical inputs give canonical outputs.  n == 0 writes nothing and succeeds.  d_out may be exactly d_den or exactly d_num (in place).
+ * Nothing is allocated and no context scratch is touched: capturable without warm-up or sr_ctx_reserve_scratch.  Pointers that are only
+ * 8-byte aligned are taken one coefficient per lane, as by the streaming calls.
+ * sr_inverse_plan: pure host arithmetic.  chunk_elems: the consecutive elements one lane inverts together (it depends on the ring and
+ * on has_num); launches: 1, or 0 for n == 0; work_elems: the workspace the _dev call wants, 0 on every ring today -- d_work may then be
+ * NULL -- and kept so that the call has the shape of its siblings.
+ * SR_E_INVALID, each with its own message and before any device work: a null context (first), a null d_out or d_den, d_out
+ * overlapping d_den or d_num without being that very pointer, a workspace below the plan, an element count too large, and for the plan
+ * an unknown ring id or a log2_degree out of range.
+ * The host-pointer form goes through the chunked staging pipeline of the element-wise calls (SR_HOST_CHUNK_MB). */
+int sr_inverse_plan(int ring, int log2_degree, size_t n, int has_num, size_t *work_elems, int *launches, size_t *chunk_elems);
+int sr_inverse_batch_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_num /* may be NULL */, const uint64_t *d_den, size_t n,
+                         uint64_t *d_work, size_t work_elems, void *stream);
+int sr_inverse_batch(sr_ctx *ctx, uint64_t *out, const uint64_t *num /* may be NULL */, const uint64_t *den, size_t n);
+int sr_inverse_zero_count(sr_ctx *ctx, unsigned long long *out, void *stream);
 /* Norms of a coefficient slice on the device: WithLinfNorm::linf_norm / WithL2Norm::l2_norm_squared over [Fq]
  * (crates/ring/src/traits.rs:6-36; per element balanced_decomposition/convertible_ring.rs:49-66; the signed representative of
  * fq_convertible.rs:20-34 and stark_prime/decomposition.rs:40-52).

@@ -15,6 +15,7 @@ Layout:
   grand_product.py      ProductTree: every layer of a table's binary product tree, the circuit of the layered grand-product argument
   frac_tree.py          FractionTree: every layer of a sum of fractions p/q, the circuit of the layered logUp (lookup, range) argument
   lincomb.py            linear combinations of up to 16 tables with ring-element coefficients, up to 4 outputs from one pass
+  inverse.py            batch inversion num / den slot by slot (Montgomery's trick per lane), zero slots counted
   index_columns.py      integer columns (u64 per row, or a progression) beside the tables of a linear combination; multiplicities
   lookup.py             PermutationCheck and LookupCheck: leaves (lincomb), trees and layer claims end to end on the device
   symmetric.py          SymmetricMatrix of crates/linear_algebra, packed: Gram matrices and the G^T M G recomposition
@@ -40,9 +41,10 @@ from .wsumcheck import vpoly_wround_evals_dev, vpoly_wround_fold_evals_dev  # no
 from .range_check import RangePolynomial, range_wround_evals, range_wround_evals_dev, range_wround_plan  # noqa: F401
 from .frac_tree import FractionTree, frac_tree_dev, frac_tree_plan  # noqa: F401  (the host-pointer form: frac_tree.frac_tree)
 from .lincomb import lincomb_dev, lincomb_plan  # noqa: F401  (the host-pointer form: lincomb.lincomb)
+from .inverse import inverse_dev, inverse_plan, inverse_zero_count  # noqa: F401  (the host-pointer form: inverse.inverse)
 from .index_columns import (IndexColumn, from_u64_dev, identity_permutation, identity_permutation_mles, index_count,  # noqa: F401
                             index_count_dev, lincomb_index, lincomb_index_dev, lincomb_index_plan)
-from .lookup import (LookupCheck, PermutationCheck, fingerprint, fingerprint_indexed, permutation_leaves,  # noqa: F401
+from .lookup import (LookupCheck, LookupHelperColumns, PermutationCheck, fingerprint, fingerprint_indexed, permutation_leaves,  # noqa: F401
                      permutation_leaves_indexed)
 from .symmetric import SymmetricMatrixNTT, recompose_left_right_symmetric_matrix  # noqa: F401
 from .sparse import SparseMatrixNTT  # noqa: F401

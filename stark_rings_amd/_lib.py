@@ -62,6 +62,11 @@ SYMBOLS = {
                                     _c.c_size_t]),
     "sr_index_count_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p]),
     "sr_index_count": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t, _c.c_size_t]),
+    "sr_inverse_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
+                                   _c.POINTER(_c.c_size_t)]),
+    "sr_inverse_batch_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_inverse_batch": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, u64p, _c.c_size_t]),
+    "sr_inverse_zero_count": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_ulonglong), _c.c_void_p]),
     "sr_mle_round_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
     "sr_mle_round_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_void_p,
                                           _c.c_size_t, _c.c_void_p]),

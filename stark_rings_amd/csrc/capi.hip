@@ -42,6 +42,7 @@
 #include "frac_tree.hpp"
 #include "lincomb.hpp"
 #include "lincomb_index.hpp"
+#include "inverse.hpp"
 #include "range_check.hpp"
 
 namespace {
@@ -2194,6 +2195,38 @@ int check_frac_tree(sr_ctx *c, const void *p_layers, const void *q_layers, const
     if (p_leaves && ranges_overlap(q_layers, out, p_leaves, in)) return fail(SR_E_INVALID, "frac_tree: d_q_layers overlaps d_p_leaves");
     return SR_OK;
 }
+// ---- batch inversion (csrc/inverse.hpp): one launch under K_POINTWISE, nothing allocated, no context scratch ------------------------
+// out[e] = num[e] / den[e] slot by slot (num == nullptr: one()); zero slots come back zero and are counted in d_counter[5]
+int dev_inverse(sr_ctx *c, uint64_t *out, const uint64_t *num, const uint64_t *den, size_t n, hipStream_t st) {
+    if (n == 0) return SR_OK;
+    const bool aligned = ((((uintptr_t)out | (uintptr_t)num | (uintptr_t)den)) & 15u) == 0;
+    const sr::smle::One one = smle_one(c);
+    unsigned long long *zeros = c->d_counter + 5;
+    ProfScope prof(c, st, K_POINTWISE);
+    hipError_t e;
+    switch (c->ring) {
+        case SR_RING_GOLDILOCKS_POW2: e = sr::inverse::launch<sr::Goldilocks>({}, out, num, den, one, n, c->k, aligned, zeros, st); break;
+        case SR_RING_BABYBEAR_POW2: e = sr::inverse::launch<sr::BabyBear>({}, out, num, den, one, n, c->k, aligned, zeros, st); break;
+        case SR_RING_STARK_POW2: e = sr::inverse::launch<sr::Stark>({}, out, num, den, one, n, c->k, aligned, zeros, st); break;
+        case SR_RING_GOLDILOCKS_24: e = sr::inverse::launch<sr::SlotG24>(c->small, out, num, den, one, n, 0, aligned, zeros, st); break;
+        case SR_RING_BABYBEAR_72: e = sr::inverse::launch<sr::SlotB72>(c->small, out, num, den, one, n, 0, aligned, zeros, st); break;
+        default: e = sr::inverse::launch<sr::SlotFrog>(c->frog, out, num, den, one, n, 0, aligned, zeros, st); break;
+    }
+    if (e != hipSuccess) return fail(SR_E_HIP, std::string("inverse launch: ") + hipGetErrorString(e));
+    return SR_OK;
+}
+// the argument checks the two forms of sr_inverse_batch share
+int check_inverse(sr_ctx *c, const void *out, const void *num, const void *den, size_t n) {
+    if (!c) return fail(SR_E_INVALID, "null context");
+    if (!out) return fail(SR_E_INVALID, "inverse: null output buffer");
+    if (!den) return fail(SR_E_INVALID, "inverse: null denominators");
+    if (int rc = check_count(c, n)) return rc;
+    const size_t bytes = n * (size_t)c->degree * c->limbs * 8;
+    if (out != den && ranges_overlap(out, bytes, den, bytes)) return fail(SR_E_INVALID, "inverse: d_out overlaps d_den (in place needs d_out == d_den)");
+    if (num && out != num && ranges_overlap(out, bytes, num, bytes))
+        return fail(SR_E_INVALID, "inverse: d_out overlaps d_num (in place needs d_out == d_num)");
+    return SR_OK;
+}
 // ---- linear combinations (csrc/lincomb.hpp): every launch under K_POINTWISE, nothing allocated, no context scratch -------------------
 // The launches of sr::lincomb::plan: outputs m0 .. m0 + outputs_per_launch - 1 each, every launch over all the tables.
 int dev_lincomb(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
@@ -2820,11 +2853,12 @@ int sr_ctx_create_ex(int ring, int log2_degree, int device, const sr_plan *plan,
     };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(SR_E_HIP, "hipStreamCreate failed"));
     if (hipStreamCreateWithFlags(&c->out_stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(SR_E_HIP, "hipStreamCreate failed"));
-    // five words: [0] scratch counter of count_noncanonical, [1] out-of-range column indices seen by spmv and out-of-range positions
+    // six words: [0] scratch counter of count_noncanonical, [1] out-of-range column indices seen by spmv and out-of-range positions
     // seen by the gather, [2] coefficients that needed more digits than padding_size in a decomposition, [3] wire coefficients >= p /
-    // misaligned wire offsets, [4] structural entries of a sparse product none of whose products was non-zero ([1]..[4] sticky until read)
-    if (hipMalloc(&c->d_counter, 5 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_ALLOC, "hipMalloc counter failed"));
-    if (hipMemset(c->d_counter, 0, 5 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_HIP, "hipMemset counter failed"));
+    // misaligned wire offsets, [4] structural entries of a sparse product none of whose products was non-zero, [5] zero slots met by the batch inversion
+    // ([1]..[5] sticky until read)
+    if (hipMalloc(&c->d_counter, 6 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_ALLOC, "hipMalloc counter failed"));
+    if (hipMemset(c->d_counter, 0, 6 * sizeof(unsigned long long)) != hipSuccess) return bail(fail(SR_E_HIP, "hipMemset counter failed"));
     if (is_pow2_ring(ring)) {
         const int k = log2_degree;
         c->k = k;
@@ -3100,6 +3134,39 @@ int sr_lincomb_index_dev(sr_ctx *c, uint64_t *const *outs, int n_outputs, const 
 int sr_lincomb_index(sr_ctx *c, uint64_t *const *outs, int n_outputs, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
                      const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n) {
     return lincomb_host(kLincombIndex, c, outs, n_outputs, tables, n_evals, n_tables, columns, n_index, coef, uses, n);
+}
+int sr_inverse_plan(int ring, int log2_degree, size_t n, int has_num, size_t *work_elems, int *launches, size_t *chunk_elems) {
+    if (int rc = check_plan_ring(ring, log2_degree)) return rc;
+    if (!work_elems || !launches || !chunk_elems) return fail(SR_E_INVALID, "inverse_plan: null result pointer");
+    if (n > (size_t)1 << 46) return fail(SR_E_INVALID, "inverse_plan: element count too large");
+    sr::inverse::Plan p;
+    if (!sr::inverse::plan(ring, n, has_num != 0, &p)) return fail(SR_E_INVALID, "inverse_plan: no plan for these arguments");
+    *work_elems = p.work_elems;
+    *launches = p.launches;
+    *chunk_elems = p.chunk_elems;
+    return SR_OK;
+}
+int sr_inverse_batch_dev(sr_ctx *c, uint64_t *out, const uint64_t *num, const uint64_t *den, size_t n, uint64_t *work, size_t work_elems,
+                         void *stream) {
+    if (int rc = check_inverse(c, out, num, den, n)) return rc;
+    sr::inverse::Plan p;
+    if (!sr::inverse::plan(c->ring, n, num != nullptr, &p)) return fail(SR_E_INVALID, "inverse: no plan for these arguments");
+    if (p.work_elems && (!work || work_elems < p.work_elems)) return fail(SR_E_INVALID, "inverse: d_work is smaller than sr_inverse_plan asks for");
+    const Call call(c, stream);
+    return dev_inverse(c, out, num, den, n, call.st);
+}
+int sr_inverse_batch(sr_ctx *c, uint64_t *out, const uint64_t *num, const uint64_t *den, size_t n) {
+    if (int rc = check_inverse(c, out, num, den, n)) return rc;
+    const Call call(c);
+    // in place on the staged denominators; a staging chunk is a whole number of elements, and a lane's chunk never crosses it
+    return host_pipeline(c, out, den, num, n, [&](uint64_t *s0, uint64_t *s1, size_t m, hipStream_t st) {
+        return dev_inverse(c, s0, num ? s1 : nullptr, s0, m, st);
+    });
+}
+int sr_inverse_zero_count(sr_ctx *c, unsigned long long *out, void *stream) {
+    if (int rc = check(c, {out})) return rc;
+    const Call call(c, stream);
+    return read_counter(c, 5, out, call.st);
 }
 int sr_index_count_dev(sr_ctx *c, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins, void *stream) {
     if (int rc = check_index_count(c, counts, idx, n, n_bins)) return rc;

@@ -145,6 +145,29 @@ class FractionTree:
             return self.p_leaves, self.q_leaves
         return self._tables(self._num_vars)
 
+    def root_value(self, stream=None):
+        """P / Q: the value of the sum of all fractions as one ring element (a new tensor), slot by slot (sr_inverse_batch_dev on the
+        root).  Raises RingError when Q has a zero slot -- some denominator was no unit of the ring.  Q is copied to the host and its
+        slots are tested there before the device call, so the call meets no zero and a count of inverse_zero_count the caller has not
+        read yet stays as it is.  Blocks on `stream`."""
+        import torch
+
+        from .inverse import inverse_dev
+
+        ring = self.ring
+        p, q = self.root()
+        if stream is not None:
+            stream.synchronize()
+        words = q.cpu().numpy().view(np.uint64)
+        slot = ring.limbs if ring.ring <= STARK_POW2 else {3: 3, 4: 9, 5: 4}[ring.ring]   # words of a slot: Fq, Fq3, Fq9, Fq4
+        if not words.reshape(-1, slot).any(axis=1).all():
+            raise RingError("FractionTree.root_value: Q has a zero slot, the sum of the fractions has no value")
+        out = torch.empty_like(q)
+        if stream is not None:
+            out.record_stream(stream)
+        inverse_dev(ring, out, q, p, 1, stream=stream)
+        return out
+
     def halves(self, k):
         """(p_lo, p_hi, q_lo, q_hi): the lower and upper halves of layer k - 1 as MLEs in num_vars - k variables, with
         P_k = p_lo q_hi + p_hi q_lo and Q_k = q_lo q_hi element by element.  Trailing order only."""

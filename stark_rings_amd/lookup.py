@@ -185,3 +185,93 @@ class LookupCheck:
         """FractionTree.layer_claim of one side: side 0 / "witness" or 1 / "table" """
         tree = self.witness if side in (0, "witness") else self.table
         return tree.layer_claim(k, z, lam, stream)
+
+
+class LookupHelperColumns:
+    """logUp in its helper-column form: instead of two fraction trees (one sum-check per layer and side) the prover holds the inverse
+    columns h_w = 1 / witness_q and h_t = multiplicities / table_q themselves (two sr_inverse_batch_dev calls), shows
+    sum_b eq(z, b) (h q - num)(b) = 0 with ONE zero-check per side (zero_claim, EqSumCheck) and compares sum h_w with sum h_t.
+
+    Unlike LookupCheck.holds -- a polynomial identity in beta that needs no inverse and excludes no challenge -- this form DOES exclude
+    the challenges that hit a denominator: a zero slot of witness_q or table_q has no inverse, its helper slot is zero, and holds() is
+    false whatever the sums say (zero_slots counts them).
+
+    The zero slots are read from the context's counter (sr_inverse_zero_count), which the constructor reads twice: once before its two
+    calls, so that zero_slots and holds() speak of this lookup alone, and once after them.  The first read clears what earlier inverse
+    calls on the same context left unread; that number is not lost but kept in zero_slots_before for the caller who still wanted it.
+
+    Both sides must be stored in full, n_w == 2^num_vars_w and n_t == 2^num_vars_t: a truncated side is refused.  The fraction trees
+    count a missing row as the fraction 0 / 1, with q = one().  A caller with fewer rows writes the padding out and passes the full
+    form.  On the table side q = one() and m = zero() give h = 0: the claim h q - m holds there and the sum is unchanged.  On the
+    witness side q = one() gives h = 1 and the claim h q - 1 holds there, but every padded row adds one() to sum h_w, which the fraction
+    tree does not count: the caller subtracts the number of padded rows from sum h_w, or pads the witness with copies of a row that is
+    in the table and counts them in the multiplicities, after which holds() is the check as it stands."""
+
+    def __init__(self, ring, witness_q, table_q, multiplicities, num_vars_w, num_vars_t, n_w=None, n_t=None, stream=None):
+        import torch
+
+        from .inverse import inverse_dev, inverse_zero_count
+        from .mle import DenseMultilinearExtension
+
+        w = ring.words_per_elem
+        rows_w = ring._batch_of(witness_q.numel()) if n_w is None else int(n_w)
+        rows_t = ring._batch_of(table_q.numel()) if n_t is None else int(n_t)
+        if rows_w != 1 << num_vars_w or rows_t != 1 << num_vars_t:
+            raise RingError("LookupHelperColumns: a truncated side is refused: store all 2^num_vars rows (pad q with one(), the "
+                            "multiplicities with zero())")
+        if witness_q.numel() < rows_w * w or table_q.numel() < rows_t * w or multiplicities.numel() < rows_t * w:
+            raise RingError("LookupHelperColumns: a column holds fewer rows than its side")
+        self.ring, self.stream = ring, stream
+        self.num_vars_w, self.num_vars_t = int(num_vars_w), int(num_vars_t)
+        self.witness_q, self.table_q = witness_q[:rows_w * w], table_q[:rows_t * w]
+        self.multiplicities = multiplicities[:rows_t * w]
+        self.h_w, self.h_t = torch.empty_like(self.witness_q), torch.empty_like(self.table_q)
+        one = _one(ring, witness_q)
+        self.minus_one = one.clone()
+        ring.neg_dev(self.minus_one, stream)
+        self.ones = one.repeat(rows_w)      # the numerators of the witness side, as a table: the claim h q - 1 needs it as an MLE
+        if stream is not None:
+            for t in (self.h_w, self.h_t, self.minus_one, self.ones):
+                t.record_stream(stream)
+        # a count an earlier call on this context left unread is not this lookup's: it is taken out first and kept for the caller
+        self.zero_slots_before = inverse_zero_count(ring, stream)
+        inverse_dev(ring, self.h_w, self.witness_q, None, rows_w, stream=stream)
+        inverse_dev(ring, self.h_t, self.table_q, self.multiplicities, rows_t, stream=stream)
+        self.zero_slots = inverse_zero_count(ring, stream)   # the zero slots of witness_q and table_q
+        self._mle = lambda t, nv: DenseMultilinearExtension(ring, nv, t)
+
+    @classmethod
+    def from_indices(cls, ring, witness_q, table_q, indices, num_vars_w, num_vars_t, n_w=None, n_t=None, stream=None):
+        """As LookupCheck.from_indices: the multiplicities are counted on the device from indices[i], the table row of witness row i."""
+        rows_t = ring._batch_of(table_q.numel()) if n_t is None else int(n_t)
+        counts = index_count_dev(ring, indices, rows_t, stream=stream)
+        mult = from_u64_dev(ring, counts, rows_t, stream=stream)
+        return cls(ring, witness_q, table_q, mult, num_vars_w, num_vars_t, n_w, n_t, stream)
+
+    def sums(self):
+        """(sum_i h_w[i], sum_j h_t[j]): one ring element each (sr_sum_batch_dev)"""
+        import torch
+
+        w = self.ring.words_per_elem
+        a, b = torch.empty_like(self.h_w[:w]), torch.empty_like(self.h_w[:w])
+        self.ring.sum_dev(a, self.h_w, self.stream)
+        self.ring.sum_dev(b, self.h_t, self.stream)
+        return a, b
+
+    def holds(self):
+        """the two sums agree and no denominator had a zero slot (compared on the host; synchronises)"""
+        a, b = self.sums()
+        return _same(a, b) and self.zero_slots == 0
+
+    def zero_claim(self, side):
+        """The VirtualPolynomial h q - 1 (side 0 / "witness") or h q - m (side 1 / "table"): it vanishes on the whole cube exactly when
+        h is the inverse column, so EqSumCheck(zero_claim(side), z) with a random z proves it with a claimed sum of zero."""
+        from .mle import VirtualPolynomial
+
+        if side in (0, "witness"):
+            nv, h, q, num = self.num_vars_w, self.h_w, self.witness_q, self.ones
+        else:
+            nv, h, q, num = self.num_vars_t, self.h_t, self.table_q, self.multiplicities
+        g = VirtualPolynomial(self.ring, nv)
+        g.add_mle_list([self._mle(h, nv), self._mle(q, nv)]).add_mle_list([self._mle(num, nv)], self.minus_one)
+        return g

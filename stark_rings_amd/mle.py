@@ -98,6 +98,31 @@ class DenseMultilinearExtension:
         self.ring.mul_elem_add_dev(self.evaluations, other.evaluations, r, stream)
         return self
 
+    def _quotient(self, num, stream):
+        import torch
+
+        from .inverse import inverse_dev
+
+        out = torch.empty_like(self.evaluations)
+        if stream is not None:
+            out.record_stream(stream)
+        if len(self):
+            inverse_dev(self.ring, out, self.evaluations, num.evaluations if num is not None else None, len(self), stream=stream)
+        return DenseMultilinearExtension(self.ring, self._num_vars, out)
+
+    def inverse(self, stream=None):
+        """The table of slot-wise inverses 1 / self[b] as a new MLE over the stored evaluations (sr_inverse_batch_dev:
+        ark_ff::batch_inversion on every slot).  A zero slot gives zero and is counted: ring.inverse_zero_count() == 0 afterwards says
+        that every stored evaluation was a unit.  The implicit zero tail of a truncated table stays implicit (zeros are left in place)."""
+        return self._quotient(None, stream)
+
+    def divide(self, other, stream=None):
+        """The table of slot-wise quotients self[b] / other[b] as a new MLE; zero slots of `other` give zero and are counted.  Both
+        operands store the same number of evaluations."""
+        if other.ring is not self.ring or other.num_vars != self._num_vars or len(other) != len(self):
+            raise RingError("divide: the operands differ in ring, num_vars or stored length")
+        return other._quotient(self, stream)
+
     @staticmethod
     def linear_combination(mles, coeffs, const=None, out=None, stream=None):
         """sum_k coeffs[k] * mles[k] (+ const) as one MLE from 1 .. 16 in one pass over their tables (sr_lincomb_dev): the composition

@@ -1475,6 +1475,25 @@ class CyclotomicRing:
         self._check(self._lib.sr_spgemm_dead_count(self._ctx, ctypes.byref(n), self._stream(stream)))
         return int(n.value)
 
+    # ---- batch inversion (inverse.py holds the calls; the device form is inverse.inverse_dev(ring, ...), as lincomb_dev is) ----
+    def inverse_plan(self, n, has_num=False):
+        """sr_inverse_plan for this ring: (work_elems, launches, chunk_elems)."""
+        from .inverse import inverse_plan
+
+        return inverse_plan(self, n, has_num)
+
+    def inverse(self, den, num=None):
+        """Host buffers: sr_inverse_batch (see inverse_dev); returns the quotients as a new array."""
+        from .inverse import inverse
+
+        return inverse(self, den, num)
+
+    def inverse_zero_count(self, stream=None):
+        """sr_inverse_zero_count: the zero slots the inverse calls met since the last read; clears the count."""
+        from .inverse import inverse_zero_count
+
+        return inverse_zero_count(self, stream)
+
     def rot_dev(self, out, a, stream=None):
         po, n = self._dev(out)
         pa, m = self._dev(a)
