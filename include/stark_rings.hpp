@@ -43,7 +43,9 @@
 //                                                                      and the next message in one pass), fixed_variables,
 //                                                                      round_evals_weighted / fold_round_evals_weighted (sr_vpoly_wround_*:
 //                                                                      a per-pair weight, the eq factor without a table); class EqSumCheck:
-//                                                                      a whole sum-check of eq(z, .) g, message / next / final
+//                                                                      a whole sum-check of eq(z, .) g, message / next / final;
+//                                                                      class IndexMultilinearExtension: an IndexColumn as a factor,
+//                                                                      read as u64 by the weighted rounds (sr_vpoly_iwround_*), to_dense
 //   the range (norm) check of a lattice  (LatticeFold's norm check)     class RangePolynomial: sum_i mu_i prod_{|j| < B} (f_i - j) over 1 .. 8
 //     folding scheme                                                   MLEs, each read once (sr_range_wround_evals); RangeSumCheck: the
 //                                                                      whole check; CyclotomicConfig::range_wround_plan / _evals_dev / _evals
@@ -249,6 +251,32 @@ public:
         check(sr_vpoly_wround_fold_evals_dev(raw(), d_out, d_out_tables, n_evals_out, d_weights, d_tables, n_evals, n_tables, terms, n_terms,
                                              d_coeffs, num_vars, d_r, order, d_work, work_elems, stream),
               "vpoly_wround_fold_evals_dev");
+    }
+    // the same rounds with integer columns as factors (include/stark_rings_hip.h: sr_vpoly_iwround_plan, sr_vpoly_iwround_evals_dev,
+    // sr_vpoly_iwround_fold_evals_dev): slots 0 .. n_tables - 1 of a term are the tables, the next n_index the columns; fold: the plan
+    // of the fused call; d_out_tables and n_evals_out hold n_tables + n_index entries
+    std::pair<size_t, int> vpoly_iwround_plan(int log2_degree, size_t num_vars, int n_tables, int n_index, int n_terms, int degree, int order,
+                                              bool fold) const {
+        size_t work = 0;
+        int launches = 0;
+        check(sr_vpoly_iwround_plan((int)ring_, log2_degree, num_vars, n_tables, n_index, n_terms, degree, order, fold ? 1 : 0, &work, &launches),
+              "vpoly_iwround_plan");
+        return {work, launches};
+    }
+    void vpoly_iwround_evals_dev(uint64_t *d_out, const uint64_t *d_weights, const uint64_t *const *d_tables, const size_t *n_evals, int n_tables,
+                                 const sr_index_column *columns, int n_index, const sr_vpoly_term *terms, int n_terms, const uint64_t *d_coeffs,
+                                 size_t num_vars, int order, uint64_t *d_work, size_t work_elems, void *stream) const {
+        check(sr_vpoly_iwround_evals_dev(raw(), d_out, d_weights, d_tables, n_evals, n_tables, columns, n_index, terms, n_terms, d_coeffs, num_vars,
+                                         order, d_work, work_elems, stream),
+              "vpoly_iwround_evals_dev");
+    }
+    void vpoly_iwround_fold_evals_dev(uint64_t *d_out, uint64_t *const *d_out_tables, size_t *n_evals_out, const uint64_t *d_weights,
+                                      const uint64_t *const *d_tables, const size_t *n_evals, int n_tables, const sr_index_column *columns,
+                                      int n_index, const sr_vpoly_term *terms, int n_terms, const uint64_t *d_coeffs, size_t num_vars,
+                                      const uint64_t *d_r, int order, uint64_t *d_work, size_t work_elems, void *stream) const {
+        check(sr_vpoly_iwround_fold_evals_dev(raw(), d_out, d_out_tables, n_evals_out, d_weights, d_tables, n_evals, n_tables, columns, n_index,
+                                              terms, n_terms, d_coeffs, num_vars, d_r, order, d_work, work_elems, stream),
+              "vpoly_iwround_fold_evals_dev");
     }
     // range-check (norm-check) rounds (include/stark_rings_hip.h: sr_range_wround_plan, sr_range_wround_evals_dev, sr_range_wround_evals):
     // {work_elems, launches} of the plan, the device call and the host-pointer form (2 bound elements into `out`)
@@ -979,11 +1007,50 @@ private:
     std::vector<uint64_t> p_leaves_, q_leaves_, p_layers_, q_layers_;
 };
 
+// A multilinear extension in num_vars variables whose evaluations are an IndexColumn: evaluation e is R::from(col[e]); a stored column's
+// evaluations beyond its values are zero.  A factor of a VirtualPolynomial: the weighted sum-check rounds read it as one u64 per row
+// (sr_vpoly_iwround_evals / sr_vpoly_iwround_fold_evals), everything else expands it with to_dense() first.
+class IndexMultilinearExtension {
+public:
+    IndexMultilinearExtension(CyclotomicConfig cfg, size_t num_vars, IndexColumn column) : cfg_(std::move(cfg)), nv_(num_vars), col_(std::move(column)) {
+        if (nv_ >= 48) throw std::length_error("IndexMultilinearExtension: num_vars must be below 48");
+        const uint64_t full = (uint64_t)1 << nv_;
+        if (col_.is_progression) {
+            if (!col_.values.empty()) throw std::length_error("IndexMultilinearExtension: a progression stores no values");
+            if (col_.start > UINT64_MAX - (full - 1)) throw std::length_error("IndexMultilinearExtension: a progression wraps past 2^64 - 1");
+        } else {
+            if (col_.start != 0) throw std::length_error("IndexMultilinearExtension: a stored column with a non-zero start");
+            if (col_.values.size() > full) throw std::length_error("IndexMultilinearExtension: more values than 2^num_vars");
+        }
+    }
+    size_t num_vars() const { return nv_; }
+    size_t len() const { return col_.is_progression ? (size_t)1 << nv_ : col_.values.size(); }  // stored evaluations
+    const IndexColumn &column() const { return col_; }
+    const CyclotomicConfig &config() const { return cfg_; }
+    // the DenseMultilinearExtension of the same evaluations: from_u64 over the stored part, D words per integer
+    DenseMultilinearExtension to_dense() const {
+        if (len() == 0) return DenseMultilinearExtension(cfg_, nv_, std::vector<uint64_t>());
+        const uint64_t dummy = 0;
+        std::vector<uint64_t> one(cfg_.words_per_elem());  // the eq table of no variables is the single element one()
+        CyclotomicConfig::check(sr_eq_table(cfg_.raw(), one.data(), &dummy, 0), "sr_eq_table");
+        return DenseMultilinearExtension(cfg_, nv_, from_u64(cfg_, col_, len(), one));
+    }
+
+private:
+    CyclotomicConfig cfg_;
+    size_t nv_;
+    IndexColumn col_;
+};
+
 // A sum of products of dense MLEs with ring coefficients, g = sum_k c_k prod_s f_{k,s}, after HyperPlonk's VirtualPolynomial (the code
 // crates/poly's polynomials/multilinear_polynomial.rs was adapted from): the object a sum-check is run on -- eq (a b - c),
 // sum_i alpha_i eq prod_j (...).  The MLEs are referred to, not copied, and must outlive the polynomial; an MLE that is in several
 // products is one table slot and is read once per round (sr_vpoly_round_evals).  At most SR_VPOLY_MAX_TABLES distinct MLEs,
 // SR_VPOLY_MAX_TERMS products, SR_VPOLY_MAX_FACTORS factors per product; throws std::length_error beyond, leaving the polynomial as it was.
+// A factor may be an IndexMultilinearExtension, a column of integers that stands for the table R::from(col[e]): round_evals_weighted
+// and fold_round_evals_weighted read such a slot as u64 (sr_vpoly_iwround_*), and the polynomial fold_round_evals_weighted returns
+// holds dense tables only.  round_evals, sum, fold_round_evals and fixed_variables have no such kernels: they expand every column slot
+// with to_dense() first -- the slow path, D words per integer.
 class VirtualPolynomial {
 public:
     VirtualPolynomial(CyclotomicConfig cfg, size_t num_vars) : cfg_(std::move(cfg)), nv_(num_vars) {}
@@ -994,31 +1061,41 @@ public:
         for (const sr_vpoly_term &t : terms_) d = t.n_factors > d ? t.n_factors : d;
         return (size_t)d;
     }
-    const std::vector<const DenseMultilinearExtension *> &tables() const { return tables_; }  // the table slots, in order of first use
+    // the table slots, in order of first use; a slot that holds a column is nullptr here and set in columns()
+    const std::vector<const DenseMultilinearExtension *> &tables() const { return tables_; }
+    const std::vector<const IndexMultilinearExtension *> &columns() const { return columns_; }
+    bool has_columns() const {
+        for (const IndexMultilinearExtension *c : columns_)
+            if (c) return true;
+        return false;
+    }
     const std::vector<sr_vpoly_term> &terms() const { return terms_; }
     // g += coeff * prod(mles): 1 .. 4 MLEs (one may appear twice), coeff one ring element or nullptr for one()
     void add_mle_list(const std::vector<const DenseMultilinearExtension *> &mles, const RqNTTVec *coeff = nullptr) {
-        if (mles.empty() || mles.size() > SR_VPOLY_MAX_FACTORS) throw std::length_error("VirtualPolynomial: a product has 1 .. 4 factors");
+        add_product(mles, {}, coeff);
+    }
+    // g += coeff * prod(mles) * prod(columns): add_mle_list with factors of both kinds, 1 .. 4 together.  Its own name, not one more
+    // overload: a braced list of pointers, or {}, would otherwise have to choose between two vector types and a null coefficient.
+    void add_product(const std::vector<const DenseMultilinearExtension *> &mles, const std::vector<const IndexMultilinearExtension *> &columns,
+                     const RqNTTVec *coeff = nullptr) {
+        if (mles.size() + columns.size() < 1 || mles.size() + columns.size() > SR_VPOLY_MAX_FACTORS)
+            throw std::length_error("VirtualPolynomial: a product has 1 .. 4 factors");
         if (terms_.size() >= SR_VPOLY_MAX_TERMS) throw std::length_error("VirtualPolynomial: more than 8 products");
         if (coeff && coeff->len() != 1) throw std::length_error("VirtualPolynomial: the coefficient is not one ring element");
         std::vector<const DenseMultilinearExtension *> slots = tables_;
+        std::vector<const IndexMultilinearExtension *> cslots = columns_;
         sr_vpoly_term t{};
-        for (const DenseMultilinearExtension *m : mles) t.table[t.n_factors++] = slot_of(slots, m);
+        for (const DenseMultilinearExtension *m : mles) t.table[t.n_factors++] = slot_of(slots, cslots, m, nullptr);
+        for (const IndexMultilinearExtension *c : columns) t.table[t.n_factors++] = slot_of(slots, cslots, nullptr, c);
         tables_ = std::move(slots);
+        columns_ = std::move(cslots);
         terms_.push_back(t);
         has_coeff_.push_back(coeff != nullptr);
         coeffs_.push_back(coeff ? coeff->words() : std::vector<uint64_t>());
     }
     // g *= mle: the MLE becomes one more factor of every product
-    void mul_by_mle(const DenseMultilinearExtension *mle) {
-        if (terms_.empty()) throw std::length_error("VirtualPolynomial: mul_by_mle on an empty polynomial");
-        for (const sr_vpoly_term &t : terms_)
-            if (t.n_factors >= SR_VPOLY_MAX_FACTORS) throw std::length_error("VirtualPolynomial: a product has 1 .. 4 factors");
-        std::vector<const DenseMultilinearExtension *> slots = tables_;
-        const int slot = slot_of(slots, mle);
-        tables_ = std::move(slots);
-        for (sr_vpoly_term &t : terms_) t.table[t.n_factors++] = slot;
-    }
+    void mul_by_mle(const DenseMultilinearExtension *mle) { mul_by(mle, nullptr); }
+    void mul_by_mle(const IndexMultilinearExtension *mle) { mul_by(nullptr, mle); }
     // The prover's message of one sum-check round over g: the degree() + 1 elements p(t) = sum_b g(t, b), t = 0 .. degree(), the variable
     // being the one fix_variables (SR_MLE_LEADING) or fix_last_variables (SR_MLE_TRAILING) fixes next.
     RqNTTVec round_evals(int order = SR_MLE_LEADING) const {
@@ -1035,6 +1112,7 @@ public:
     std::pair<RqNTTVec, VirtualPolynomial> fold_round_evals(const RqNTTVec &r, int order = SR_MLE_LEADING) const {
         if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("fold_round_evals: unknown order");
         if (terms_.empty()) throw std::length_error("VirtualPolynomial: no product has been added");
+        if (has_columns()) return dense().fold_round_evals(r, order);
         if (r.len() != 1) throw std::length_error("fold_round_evals: r is not one ring element");
         if (nv_ < 2) throw std::length_error("fold_round_evals: num_vars >= 2");
         const size_t w = cfg_.words_per_elem();
@@ -1068,6 +1146,7 @@ public:
     VirtualPolynomial fixed_variables(const RqNTTVec &point, int order = SR_MLE_LEADING) const {
         if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("fixed_variables: unknown order");
         if (point.len() > nv_) throw std::length_error("too many partial points");
+        if (has_columns()) return dense().fixed_variables(point, order);
         std::vector<DenseMultilinearExtension> g;
         for (const DenseMultilinearExtension *t : tables_) g.push_back(order == SR_MLE_LEADING ? t->fixed_variables(point) : t->fix_last_variables(point));
         return over(std::move(g), nv_ - point.len());
@@ -1079,6 +1158,7 @@ public:
         if (order != SR_MLE_LEADING && order != SR_MLE_TRAILING) throw std::invalid_argument("round_evals_weighted: unknown order");
         if (terms_.empty()) throw std::length_error("VirtualPolynomial: no product has been added");
         if (nv_ < 1 || weights.len() != (size_t)1 << (nv_ - 1)) throw std::length_error("round_evals_weighted: one weight per pair");
+        if (has_columns()) return indexed(weights, nullptr, order).first;
         std::vector<const uint64_t *> ptrs;
         std::vector<size_t> sizes;
         for (const DenseMultilinearExtension *t : tables_) {
@@ -1100,6 +1180,7 @@ public:
         if (r.len() != 1) throw std::length_error("fold_round_evals_weighted: r is not one ring element");
         if (nv_ < 2) throw std::length_error("fold_round_evals_weighted: num_vars >= 2");
         if (next_weights.len() != (size_t)1 << (nv_ - 2)) throw std::length_error("fold_round_evals_weighted: one weight per pair of the folded tables");
+        if (has_columns()) return indexed(next_weights, &r, order);
         const size_t w = cfg_.words_per_elem();
         std::vector<const uint64_t *> ptrs;
         std::vector<size_t> sizes;
@@ -1154,16 +1235,98 @@ private:
         }
         return coeffs;
     }
-    int slot_of(std::vector<const DenseMultilinearExtension *> &slots, const DenseMultilinearExtension *m) const {
-        if (m->config().raw() != cfg_.raw() || m->num_vars() != nv_) throw std::length_error("VirtualPolynomial: the MLEs differ in ring or num_vars");
+    // the slot of a dense MLE (m) or of a column (c): the two vectors run in parallel, one of the two entries of a slot is set
+    int slot_of(std::vector<const DenseMultilinearExtension *> &slots, std::vector<const IndexMultilinearExtension *> &cslots,
+                const DenseMultilinearExtension *m, const IndexMultilinearExtension *c) const {
+        if ((m && (m->config().raw() != cfg_.raw() || m->num_vars() != nv_)) || (c && (c->config().raw() != cfg_.raw() || c->num_vars() != nv_)))
+            throw std::length_error("VirtualPolynomial: the MLEs differ in ring or num_vars");
+        cslots.resize(slots.size(), nullptr);
         for (size_t j = 0; j < slots.size(); j++)
-            if (slots[j] == m) return (int)j;
+            if (slots[j] == m && cslots[j] == c) return (int)j;
         if (slots.size() >= SR_VPOLY_MAX_TABLES) throw std::length_error("VirtualPolynomial: more than 8 distinct tables");
         slots.push_back(m);
+        cslots.push_back(c);
         return (int)slots.size() - 1;
+    }
+    void mul_by(const DenseMultilinearExtension *m, const IndexMultilinearExtension *c) {
+        if (terms_.empty()) throw std::length_error("VirtualPolynomial: mul_by_mle on an empty polynomial");
+        for (const sr_vpoly_term &t : terms_)
+            if (t.n_factors >= SR_VPOLY_MAX_FACTORS) throw std::length_error("VirtualPolynomial: a product has 1 .. 4 factors");
+        std::vector<const DenseMultilinearExtension *> slots = tables_;
+        std::vector<const IndexMultilinearExtension *> cslots = columns_;
+        const int slot = slot_of(slots, cslots, m, c);
+        tables_ = std::move(slots);
+        columns_ = std::move(cslots);
+        for (sr_vpoly_term &t : terms_) t.table[t.n_factors++] = slot;
+    }
+    const IndexMultilinearExtension *column_at(size_t j) const { return j < columns_.size() ? columns_[j] : nullptr; }
+    // the same polynomial with every column slot expanded to a ring table
+    VirtualPolynomial dense() const {
+        std::vector<DenseMultilinearExtension> g;
+        for (size_t j = 0; j < tables_.size(); j++) g.push_back(column_at(j) ? column_at(j)->to_dense() : *tables_[j]);
+        return over(std::move(g), nv_);
+    }
+    // sr_vpoly_iwround_evals (r == nullptr) or sr_vpoly_iwround_fold_evals: the dense slots first, then the column slots, the terms
+    // renumbered; the folded slots come back in the polynomial's own slot order
+    std::pair<RqNTTVec, VirtualPolynomial> indexed(const RqNTTVec &weights, const RqNTTVec *r, int order) const {
+        const size_t w = cfg_.words_per_elem(), n = tables_.size();
+        const uint64_t dummy = 0;
+        std::vector<size_t> slot_of_operand;
+        for (size_t j = 0; j < n; j++)
+            if (!column_at(j)) slot_of_operand.push_back(j);
+        const size_t K = slot_of_operand.size();
+        for (size_t j = 0; j < n; j++)
+            if (column_at(j)) slot_of_operand.push_back(j);
+        std::vector<int> operand_of_slot(n);
+        for (size_t i = 0; i < n; i++) operand_of_slot[slot_of_operand[i]] = (int)i;
+        std::vector<sr_vpoly_term> terms = terms_;
+        for (sr_vpoly_term &t : terms)
+            for (int s = 0; s < t.n_factors; s++) t.table[s] = operand_of_slot[t.table[s]];
+        std::vector<const uint64_t *> ptrs;
+        std::vector<size_t> sizes;
+        std::vector<sr_index_column> cols;
+        std::vector<std::vector<uint64_t>> folded;
+        for (size_t i = 0; i < n; i++) {
+            const size_t j = slot_of_operand[i];
+            if (i < K) {
+                ptrs.push_back(tables_[j]->words().empty() ? nullptr : tables_[j]->words().data());
+                sizes.push_back(tables_[j]->len());
+            } else {
+                const IndexColumn &c = column_at(j)->column();
+                if (c.is_progression) cols.push_back(sr_index_column{nullptr, 0, c.start});
+                else cols.push_back(sr_index_column{c.values.empty() ? &dummy : c.values.data(), c.values.size(), 0});
+            }
+            const size_t stored = i < K ? tables_[j]->len() : column_at(j)->len();
+            if (r) folded.emplace_back(stored * w);  // never shorter than the folded slot
+        }
+        const std::vector<uint64_t> coeffs = coeff_words();
+        std::vector<uint64_t> out(w * (degree() + 1));
+        if (!r) {
+            CyclotomicConfig::check(sr_vpoly_iwround_evals(cfg_.raw(), out.data(), weights.words().data(), ptrs.data(), sizes.data(), (int)K, cols.data(),
+                                                           (int)(n - K), terms.data(), (int)terms.size(), coeffs.empty() ? nullptr : coeffs.data(),
+                                                           nv_, order),
+                                    "sr_vpoly_iwround_evals");
+            return {RqNTTVec(cfg_, std::move(out)), VirtualPolynomial(cfg_, nv_)};
+        }
+        std::vector<uint64_t *> optrs;
+        uint64_t sink = 0;
+        for (auto &f : folded) optrs.push_back(f.empty() ? &sink : f.data());
+        std::vector<size_t> n_out(n);
+        CyclotomicConfig::check(sr_vpoly_iwround_fold_evals(cfg_.raw(), out.data(), optrs.data(), n_out.data(), weights.words().data(), ptrs.data(),
+                                                            sizes.data(), (int)K, cols.data(), (int)(n - K), terms.data(), (int)terms.size(),
+                                                            coeffs.empty() ? nullptr : coeffs.data(), nv_, r->words().data(), order),
+                                "sr_vpoly_iwround_fold_evals");
+        std::vector<DenseMultilinearExtension> g;
+        for (size_t j = 0; j < n; j++) {
+            const size_t i = (size_t)operand_of_slot[j];
+            folded[i].resize(n_out[i] * w);
+            g.emplace_back(cfg_, nv_ - 1, std::move(folded[i]));
+        }
+        return {RqNTTVec(cfg_, std::move(out)), over(std::move(g), nv_ - 1)};
     }
     RqNTTVec call(int mode) const {
         if (terms_.empty()) throw std::length_error("VirtualPolynomial: no product has been added");
+        if (has_columns()) return dense().call(mode);
         const size_t w = cfg_.words_per_elem();
         std::vector<const uint64_t *> ptrs;
         std::vector<size_t> sizes;
@@ -1181,6 +1344,7 @@ private:
     CyclotomicConfig cfg_;
     size_t nv_;
     std::vector<const DenseMultilinearExtension *> tables_;
+    std::vector<const IndexMultilinearExtension *> columns_;  // parallel to tables_ (shorter: no column behind); one of the two is set per slot
     std::vector<sr_vpoly_term> terms_;
     std::vector<bool> has_coeff_;
     std::vector<std::vector<uint64_t>> coeffs_;

@@ -650,6 +650,44 @@ int sr_lincomb_index(sr_ctx *ctx, uint64_t *const *outs, int n_outputs, const ui
                      const sr_index_column *columns, int n_index, const uint64_t *coef, const uint32_t *uses, size_t n);
 int sr_index_count_dev(sr_ctx *ctx, uint64_t *d_counts, const uint64_t *d_idx, size_t n, size_t n_bins, void *stream);
 int sr_index_count(sr_ctx *ctx, uint64_t *counts, const uint64_t *idx, size_t n, size_t n_bins);
+/* Integer columns in weighted sum-check rounds (csrc/sumcheck_index.hpp): a factor that is really a column of integers -- the selectors
+ * of a Plonkish gate, a 0/1 mask, a multiplicity column out of sr_index_count_dev, sigma, id -- is read as one uint64_t per row (or not
+ * at all: a progression) by the first message and the first fold, and never expanded to a ring table.
+ *   slots   terms[k].table[s] in 0 .. K - 1 are the ring tables, K .. K + J - 1 the columns, in the order of the arrays;
+ *           0 <= K, 0 <= J <= 8, 1 <= K + J <= SR_VPOLY_MAX_TABLES; K == 0 is a claim over columns only
+ * With E_j the table R::from(col_j[e]), e < n_evals_j, as sr_lincomb_index_dev writes it (a progression: n_evals_j = 2^num_vars),
+ * sr_vpoly_iwround_evals_dev writes in d_out exactly what sr_vpoly_wround_evals_dev writes over T_0 .. T_{K-1}, E_0 .. E_{J-1}, and
+ * sr_vpoly_iwround_fold_evals_dev writes in d_out, d_out_tables[0 .. K+J-1] and n_evals_out[0 .. K+J-1] exactly what
+ * sr_vpoly_wround_fold_evals_dev writes over those tables -- every word.  A folded column slot is a ring table of (n_evals_j + 1) / 2
+ * (leading) or min(n_evals_j, 2^(num_vars-1)) (trailing) elements with a buffer of its own; nothing beyond that length is touched, a
+ * stored value beyond n_evals_j counts as 0 and is never read, values >= p are reduced.  After the first fold every slot is a ring
+ * table and the weighted calls carry on.  With n_index == 0 the calls ARE the weighted calls.
+ * d_weights is required; order is SR_MLE_LEADING or SR_MLE_TRAILING; 1 <= num_vars (fused: 2) < 48.  The promises of the weighted
+ * calls hold: nothing allocated, no context scratch, every workspace word written before it is read, one chain of launches on one
+ * stream (capturable on a fresh context), canonical in gives canonical out, every ring id; terms, d_tables, d_out_tables, n_evals and
+ * columns are host arrays consumed at call time; a trailing-order fold may run in place for table slots.
+ * SR_E_INVALID, each with its own message and before any device work: every refusal of the weighted calls; n_index outside 0 .. 8;
+ * K + J outside 1 .. 8; null columns with n_index > 0; a column no term uses; n_evals_j > 2^num_vars; values != NULL with start != 0;
+ * a progression with start + 2^num_vars - 1 > 2^64 - 1; a column's array overlapping d_out, d_work or a folded table.  Column arrays
+ * may overlap each other and may be the same pointer in two slots.
+ * sr_vpoly_iwround_plan (fold: 0 the message, 1 the fused call) is pure host arithmetic with the records of sr_vpoly_wround[_fold]_plan
+ * and the points per launch of the weighted calls at K + J slots.  The host-pointer forms stage their operands as
+ * sr_vpoly_wround_evals does. */
+int sr_vpoly_iwround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_index, int n_terms, int degree, int order, int fold,
+                          size_t *work_elems, int *launches);
+int sr_vpoly_iwround_evals_dev(sr_ctx *ctx, uint64_t *d_out, const uint64_t *d_weights, const uint64_t *const *d_tables, const size_t *n_evals,
+                               int n_tables, const sr_index_column *columns, int n_index, const sr_vpoly_term *terms, int n_terms,
+                               const uint64_t *d_coeffs, size_t num_vars, int order, uint64_t *d_work, size_t work_elems, void *stream);
+int sr_vpoly_iwround_evals(sr_ctx *ctx, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
+                           int n_tables, const sr_index_column *columns, int n_index, const sr_vpoly_term *terms, int n_terms,
+                           const uint64_t *coeffs, size_t num_vars, int order);
+int sr_vpoly_iwround_fold_evals_dev(sr_ctx *ctx, uint64_t *d_out, uint64_t *const *d_out_tables, size_t *n_evals_out, const uint64_t *d_weights,
+                                    const uint64_t *const *d_tables, const size_t *n_evals, int n_tables, const sr_index_column *columns,
+                                    int n_index, const sr_vpoly_term *terms, int n_terms, const uint64_t *d_coeffs, size_t num_vars,
+                                    const uint64_t *d_r, int order, uint64_t *d_work, size_t work_elems, void *stream);
+int sr_vpoly_iwround_fold_evals(sr_ctx *ctx, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
+                                const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_index_column *columns, int n_index,
+                                const sr_vpoly_term *terms, int n_terms, const uint64_t *coeffs, size_t num_vars, const uint64_t *r, int order);
 /* Batch inversion (csrc/inverse.hpp): out[e] = num[e] * den[e]^-1 for e < n, slot by slot on tables in CRT / NTT form -- Field::inverse
  * / ark_ff::batch_inversion(&mut [F]) on every slot: the base field of a power-of-two ring, the Fq3 / Fq9 / Fq4 slots of goldilocks24 /
  * babybear72 / frog16.  d_num == NULL: every numerator is one().  `*` is the slot product (sr_pointwise_mul_batch), so for a ring

@@ -9,7 +9,8 @@ Layout:
   mle.py                DenseMultilinearExtension and SparseMultilinearExtension of crates/poly over device-resident values,
                         with the round message of a sum-check over a product, or a sum of products (VirtualPolynomial), of dense MLEs,
                         and EqSumCheck: a whole sum-check of eq(z, .) g with eq as per-pair weights, not a table
-  wsumcheck.py          the device-pointer forms of the weighted sum-check rounds (sr_vpoly_wround_evals_dev, sr_vpoly_wround_fold_evals_dev)
+  wsumcheck.py          the device-pointer forms of the weighted sum-check rounds (sr_vpoly_wround_evals_dev, sr_vpoly_wround_fold_evals_dev),
+                        and the same rounds with integer columns as factors (sr_vpoly_iwround_*)
   range_check.py        range-check (norm-check) rounds: sum_i mu_i prod_j (f_i - j) over |j| < B from one read of each table, and
                         RangePolynomial, the claim EqSumCheck runs a whole norm check on
   grand_product.py      ProductTree: every layer of a table's binary product tree, the circuit of the layered grand-product argument
@@ -37,12 +38,13 @@ from .rings import (  # noqa: F401
 )
 from .mle import DenseMultilinearExtension, EqSumCheck, SparseMultilinearExtension, VirtualPolynomial  # noqa: F401
 from .grand_product import ProductTree  # noqa: F401
-from .wsumcheck import vpoly_wround_evals_dev, vpoly_wround_fold_evals_dev  # noqa: F401
+from .wsumcheck import (vpoly_iwround_evals_dev, vpoly_iwround_fold_evals_dev, vpoly_iwround_plan, vpoly_wround_evals_dev,  # noqa: F401
+                        vpoly_wround_fold_evals_dev)
 from .range_check import RangePolynomial, range_wround_evals, range_wround_evals_dev, range_wround_plan  # noqa: F401
 from .frac_tree import FractionTree, frac_tree_dev, frac_tree_plan  # noqa: F401  (the host-pointer form: frac_tree.frac_tree)
 from .lincomb import lincomb_dev, lincomb_plan  # noqa: F401  (the host-pointer form: lincomb.lincomb)
 from .inverse import inverse_dev, inverse_plan, inverse_zero_count  # noqa: F401  (the host-pointer form: inverse.inverse)
-from .index_columns import (IndexColumn, from_u64_dev, identity_permutation, identity_permutation_mles, index_count,  # noqa: F401
+from .index_columns import (IndexColumn, IndexMultilinearExtension, from_u64_dev, identity_permutation, identity_permutation_mles, index_count,  # noqa: F401
                             index_count_dev, lincomb_index, lincomb_index_dev, lincomb_index_plan)
 from .lookup import (LookupCheck, LookupHelperColumns, PermutationCheck, fingerprint, fingerprint_indexed, permutation_leaves,  # noqa: F401
                      permutation_leaves_indexed)

@@ -108,6 +108,17 @@ SYMBOLS = {
                                                   _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sr_vpoly_wround_fold_evals": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int,
                                               _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, u64p, _c.c_int]),
+    "sr_vpoly_iwround_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                         _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int)]),
+    "sr_vpoly_iwround_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int,
+                                              _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_vpoly_iwround_evals": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                          _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int]),
+    "sr_vpoly_iwround_fold_evals_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                   _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                   _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sr_vpoly_iwround_fold_evals": (_c.c_int, [_c.c_void_p, u64p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                               _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, u64p, _c.c_int]),
     "sr_eq_table_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sr_eq_table": (_c.c_int, [_c.c_void_p, u64p, u64p, _c.c_size_t]),
     "sr_smle_fix_pattern": (_c.c_int, [u64p, _c.c_size_t, _c.c_size_t, _c.c_size_t, u64p, u64p, _c.POINTER(_c.c_size_t)]),

@@ -44,6 +44,7 @@
 #include "lincomb_index.hpp"
 #include "inverse.hpp"
 #include "range_check.hpp"
+#include "sumcheck_index.hpp"
 
 namespace {
 
@@ -1613,14 +1614,19 @@ struct RoundFamily {
     bool terms, fold;       // a sum of products (n_terms, degree); a fold as well (an order, no SR_MLE_ROUND_SUM, two variables)
     bool weighted = false;  // a per-pair weight (csrc/sumcheck_weighted.hpp): an order, no SR_MLE_ROUND_SUM
     bool range = false;     // a bound in place of terms and one coefficient per table (csrc/range_check.hpp); d_coeffs may alias a table
+    bool index = false;     // the last n_index slots are integer columns (csrc/sumcheck_index.hpp)
     // log2 of the weights' element count: one per pair of the tables the message is over (of a fold: the folded ones)
     size_t weight_log2(size_t num_vars) const { return num_vars - (fold ? 2 : 1); }
 };
 const RoundFamily kMleRound{"mle_round", SR_MLE_ROUND_MAX_TABLES, false, false}, kVpolyRound{"vpoly_round", SR_VPOLY_MAX_TABLES, true, false},
     kMleRoundFold{"mle_round_fold", SR_MLE_ROUND_MAX_TABLES, false, true}, kVpolyRoundFold{"vpoly_round_fold", SR_VPOLY_MAX_TABLES, true, true},
     kVpolyWround{"vpoly_wround", SR_VPOLY_MAX_TABLES, true, false, true}, kVpolyWroundFold{"vpoly_wround_fold", SR_VPOLY_MAX_TABLES, true, true, true},
-    kRangeWround{"range_wround", SR_RANGE_MAX_TABLES, false, false, true, true};
+    kRangeWround{"range_wround", SR_RANGE_MAX_TABLES, false, false, true, true},
+    kVpolyIwround{"vpoly_iwround", SR_VPOLY_MAX_TABLES, true, false, true, false, true},
+    kVpolyIwroundFold{"vpoly_iwround_fold", SR_VPOLY_MAX_TABLES, true, true, true, false, true};
 // Every operand of a round call.  The first seven exist in every family; an operand that a family does not have stays null (0).
+// With integer columns (f.index) a slot is a table or a column: tables, n_evals and n_tables speak of all slots, the last n_index of
+// which are the columns -- there tables[s] is null and n_evals[s] the column's stored length (a progression: 2^num_vars).
 struct RoundCall {
     const RoundFamily &f;
     uint64_t *out;
@@ -1639,8 +1645,11 @@ struct RoundCall {
     const uint64_t *coef = nullptr;         // n_coef() elements, or null for one() everywhere
     uint64_t *work = nullptr;               // the *_evals_dev forms: the caller's workspace
     size_t work_elems = 0;
+    const sr_index_column *columns = nullptr;  // integer columns: slots n_tables - n_index .. n_tables - 1
+    int n_index = 0;
     sr::sumcheck::Plan plan{};              // check_round sets it
     int n_coef() const { return f.range ? n_tables : n_terms; }
+    int first_column() const { return n_tables - n_index; }
 };
 extern "C++" {
 template <class T> struct FamilyType {
@@ -1719,19 +1728,37 @@ int dev_round(sr_ctx *c, const RoundCall &a, hipStream_t st) {
             return sr::vpoly_fold::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, tb, fo, a.r, nt, tm, a.n_terms, a.coef, a.num_vars,
                                                                       a.n_evals_out, k, aligned, a.work, st);
         });
-    if (!f.range && !f.fold)
+    if (!f.range && !f.index && !f.fold)
         return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
             return sr::wsumcheck::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, nt, tm, a.n_terms, a.coef, a.num_vars, k,
                                                                      aligned, a.work, st);
         });
-    if (!f.range)
+    if (!f.range && !f.index)
         return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
             return sr::wsumcheck::launch_fold<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, fo, a.r, nt, tm, a.n_terms, a.coef,
                                                                           a.num_vars, a.n_evals_out, k, aligned, a.work, st);
         });
+    if (f.range)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::range::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, nt, a.bound, a.coef, a.num_vars, k, aligned,
+                                                                 a.work, st);
+        });
+    // integer columns: the index arrays are 8-byte accesses and take no part in `aligned`
+    sr::isumcheck::ColumnArgs ca{};
+    ca.n = a.n_index;
+    for (int j = 0; j < a.n_index; j++) {
+        ca.values[j] = a.columns[j].values;
+        ca.start[j] = a.columns[j].start;
+    }
+    const int first = a.first_column();
+    if (!f.fold)
+        return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
+            return sr::isumcheck::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, first, ca, tm, a.n_terms, a.coef, a.num_vars,
+                                                                     k, aligned, a.work, st);
+        });
     return round_dispatch(c, st, f, [&](auto t, const auto &kc) {
-        return sr::range::launch<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, nt, a.bound, a.coef, a.num_vars, k, aligned, a.work,
-                                                             st);
+        return sr::isumcheck::launch_fold<typename decltype(t)::type>(kc, p, a.mode, a.out, a.weights, tb, fo, a.r, first, ca, tm, a.n_terms, a.coef,
+                                                                      a.num_vars, a.n_evals_out, k, aligned, a.work, st);
     });
 }
 // a refusal of family f: the message is assembled here, on the failing path only
@@ -1787,7 +1814,8 @@ size_t round_fold_n_out(size_t n, size_t num_vars, int order) {
 int check_round_aliasing(const sr_ctx *c, const RoundCall &a) {
     const RoundFamily &f = a.f;
     const size_t w = (size_t)c->degree * c->limbs * 8;
-    enum Kind { WRITTEN, FOLDED, READ, TABLE, WEIGHTS };  // a refusal names its two operands in this order
+    // a refusal names its two operands in this order; a column's array may overlap whatever the call only reads
+    enum Kind { WRITTEN, FOLDED, READ, TABLE, WEIGHTS, COLUMN };
     struct {
         const void *p;
         size_t bytes;
@@ -1802,8 +1830,10 @@ int check_round_aliasing(const sr_ctx *c, const RoundCall &a) {
     ops[n++] = {a.coef, a.coef ? a.n_coef() * w : 0, "d_coeffs", READ, 0};
     for (int j = 0; f.fold && j < a.n_tables; j++)
         ops[n++] = {a.out_tables[j], round_fold_n_out(a.n_evals[j], a.num_vars, a.mode) * w, "a folded table", FOLDED, j};
-    for (int j = 0; j < a.n_tables; j++) ops[n++] = {a.tables[j], a.n_evals[j] * w, "a table", TABLE, j};
+    for (int j = 0; j < a.first_column(); j++) ops[n++] = {a.tables[j], a.n_evals[j] * w, "a table", TABLE, j};
     ops[n++] = {a.weights, a.weights ? w << f.weight_log2(a.num_vars) : 0, "d_weights", WEIGHTS, 0};
+    for (int j = 0; j < a.n_index; j++)
+        ops[n++] = {a.columns[j].values, a.columns[j].values ? a.columns[j].n_evals * 8 : 0, "a column", COLUMN, a.first_column() + j};
     for (int x = 0; x < n; x++)
         for (int y = x + 1; y < n; y++) {
             const auto &p = ops[x], &q = ops[y];
@@ -1847,12 +1877,15 @@ int check_round(sr_ctx *c, RoundCall &a, bool dev) {
                 used |= 1u << t.table[s];
             }
         }
-        if (used != (1u << a.n_tables) - 1) return refuse(f, "a table that no term uses");
+        if ((used | ~((1u << a.first_column()) - 1)) != ~0u) return refuse(f, "a table that no term uses");
+        if (used != (1u << a.n_tables) - 1) return refuse(f, "a column that no term uses");
     }
     if (int rc = round_plan_for(f, c->ring, c->k, a.num_vars, a.n_tables, a.n_terms, degree, a.bound, a.mode, &a.plan)) return rc;
     for (int j = 0; j < a.n_tables; j++) {
         if (a.n_evals[j] > (size_t)1 << a.num_vars) return refuse(f, "n_evals exceeds 2^num_vars");
-        if (a.n_evals[j] && (!a.tables[j] || (f.fold && !a.out_tables[j]))) return refuse(f, "null pointer (a table)");
+        const bool column = j >= a.first_column();  // its values are a progression's when null
+        if (a.n_evals[j] && column && f.fold && !a.out_tables[j]) return refuse(f, "null pointer (the folded table of a column)");
+        if (a.n_evals[j] && ((!column && !a.tables[j]) || (f.fold && !a.out_tables[j]))) return refuse(f, "null pointer (a table)");
         if (int rc = check_count(c, a.n_evals[j])) return rc;
     }
     if (!dev) return SR_OK;
@@ -2488,7 +2521,15 @@ int round_host(sr_ctx *c, RoundCall &a) {
     for (int j = 0; j < nf; j++) n_out[j] = round_fold_n_out(a.n_evals[j], a.num_vars, a.mode);
     const uint64_t *const rest[3] = {a.r, a.coef, a.weights};
     const size_t rest_bytes[3] = {a.r ? w : 0, a.coef ? a.n_coef() * w : 0, a.weights ? w << f.weight_log2(a.num_vars) : 0};
-    const TableSlot in(a.n_evals, nt, w), folded(n_out, nf, w), aux(rest_bytes, 3, 1);
+    // a slot's host source and its bytes: a table's elements, a stored column's integers, nothing for a progression
+    const uint64_t *src[SR_VPOLY_MAX_TABLES];
+    size_t src_bytes[SR_VPOLY_MAX_TABLES];
+    for (int j = 0; j < nt; j++) {
+        const sr_index_column *col = j >= a.first_column() ? a.columns + (j - a.first_column()) : nullptr;
+        src[j] = col ? col->values : a.tables[j];
+        src_bytes[j] = col ? (col->values ? col->n_evals * 8 : 0) : a.n_evals[j] * w;
+    }
+    const TableSlot in(src_bytes, nt, 1), folded(n_out, nf, w), aux(rest_bytes, 3, 1);
     return staged(c, {{nullptr, nullptr, in.total}, {nullptr, a.out, a.plan.np_total * w}, {nullptr, nullptr, a.plan.work_elems * w},
                       {nullptr, nullptr, folded.total}, {nullptr, nullptr, aux.total}},
                   [&](void *const *d) -> int {
@@ -2496,9 +2537,15 @@ int round_host(sr_ctx *c, RoundCall &a) {
                       in.at(d[0], nt, dt);
                       folded.at(d[3], nf, df);
                       aux.at(d[4], 3, ds);
-                      if (int rc = upload_tables(c, dt, a.tables, a.n_evals, nt, w)) return rc;
+                      if (int rc = upload_tables(c, dt, src, src_bytes, nt, 1)) return rc;
                       if (int rc = upload_tables(c, ds, rest, rest_bytes, 3, 1)) return rc;
                       RoundCall dev = a;
+                      sr_index_column dc[SR_LINCOMB_MAX_INDEX_COLUMNS];
+                      for (int j = 0; j < a.n_index; j++) {
+                          dc[j] = a.columns[j];
+                          if (dc[j].values) dc[j].values = dt[a.first_column() + j];
+                      }
+                      dev.columns = a.n_index ? dc : nullptr;
                       dev.out = (uint64_t *)d[1], dev.work = (uint64_t *)d[2], dev.tables = dt, dev.out_tables = nf ? df : nullptr;
                       dev.r = a.r ? ds[0] : nullptr, dev.coef = a.coef ? ds[1] : nullptr, dev.weights = a.weights ? ds[2] : nullptr;
                       if (int rc = dev_round(c, dev, c->stream)) return rc;
@@ -2507,6 +2554,53 @@ int round_host(sr_ctx *c, RoundCall &a) {
                               HIP_TRY(hipMemcpyAsync(a.out_tables[j], df[j], a.n_evals_out[j] * w, hipMemcpyDeviceToHost, c->stream));
                       return SR_OK;
                   });
+}
+// The weighted calls with integer columns.  Without columns they ARE the weighted calls (family kVpolyWround / kVpolyWroundFold);
+// otherwise the slots of the call -- the tables, then the columns -- are laid out for RoundCall here, after the checks that only the
+// columns have.
+const RoundFamily &iwround_family(bool fold) { return fold ? kVpolyIwroundFold : kVpolyIwround; }
+int check_iwround_counts(const RoundFamily &f, int n_tables, int n_index) {
+    if (n_index < 0 || n_index > SR_LINCOMB_MAX_INDEX_COLUMNS) return refuse(f, "n_index must be 0 .. 8");
+    if (n_index == 0) return SR_OK;  // the weighted call checks its own n_tables
+    if (n_tables < 0 || n_tables + n_index > SR_VPOLY_MAX_TABLES) return refuse(f, "n_tables + n_index must be 1 .. 8");
+    return SR_OK;
+}
+int iwround_call(bool fold, bool dev, sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
+                 const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_index_column *columns, int n_index,
+                 const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, const uint64_t *r, int order, uint64_t *work,
+                 size_t work_elems, void *stream) {
+    const RoundFamily &f = iwround_family(fold);
+    if (int rc = check_iwround_counts(f, n_tables, n_index)) return rc;
+    const uint64_t *slot_tables[SR_VPOLY_MAX_TABLES];
+    size_t slot_evals[SR_VPOLY_MAX_TABLES];
+    if (n_index) {
+        if (!columns) return refuse(f, "null pointer (columns)");
+        if (n_tables && (!tables || !n_evals)) return refuse(f, "null pointer");
+        if (num_vars >= 48) return refuse(f, "num_vars must be below 48");
+        const size_t full = (size_t)1 << num_vars;
+        for (int j = 0; j < n_tables; j++) {
+            slot_tables[j] = tables[j];
+            slot_evals[j] = n_evals[j];
+        }
+        for (int j = 0; j < n_index; j++) {
+            const sr_index_column &col = columns[j];
+            if (col.values) {
+                if (col.start != 0) return refuse(f, "a stored column with a non-zero start");
+                if (col.n_evals > full) return refuse(f, "a column's n_evals exceeds 2^num_vars");
+            } else if (col.start > UINT64_MAX - (uint64_t)(full - 1)) {
+                return refuse(f, "a progression wraps past 2^64 - 1");
+            }
+            slot_tables[n_tables + j] = nullptr;
+            slot_evals[n_tables + j] = col.values ? col.n_evals : full;
+        }
+    }
+    RoundCall a{n_index ? f : (fold ? kVpolyWroundFold : kVpolyWround), out, n_index ? slot_tables : tables, n_index ? slot_evals : n_evals,
+                n_tables + n_index, num_vars, order};
+    a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
+    a.weights = weights, a.terms = terms, a.n_terms = n_terms, a.coef = coef;
+    a.work = work, a.work_elems = work_elems;
+    a.columns = n_index ? columns : nullptr, a.n_index = n_index;
+    return dev ? round_dev(c, a, stream) : round_host(c, a);
 }
 // The host-pointer form of sr_lincomb and sr_lincomb_index.  HOST_0: the stored parts of the tables, one behind the other on 16-byte
 // boundaries; HOST_1: the outputs; HOST_2: the coefficients; HOST_3: the stored parts of the index arrays, copied as they are
@@ -3290,6 +3384,41 @@ int sr_vpoly_wround_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_ta
     a.out_tables = out_tables, a.n_evals_out = n_evals_out, a.r = r;
     a.weights = weights, a.terms = terms, a.n_terms = n_terms, a.coef = coef;
     return round_host(c, a);
+}
+int sr_vpoly_iwround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int n_index, int n_terms, int degree, int order, int fold,
+                          size_t *work_elems, int *launches) {
+    if (fold != 0 && fold != 1) return refuse(kVpolyIwround, "fold must be 0 or 1");
+    const RoundFamily &f = iwround_family(fold);
+    if (int rc = check_iwround_counts(f, n_tables, n_index)) return rc;
+    if (n_index == 0)
+        return round_plan_entry(fold ? kVpolyWroundFold : kVpolyWround, ring, log2_degree, num_vars, n_tables, n_terms, degree, 0, order, work_elems,
+                                launches);
+    return round_plan_entry(f, ring, log2_degree, num_vars, n_tables + n_index, n_terms, degree, 0, order, work_elems, launches);
+}
+int sr_vpoly_iwround_evals_dev(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals,
+                               int n_tables, const sr_index_column *columns, int n_index, const sr_vpoly_term *terms, int n_terms,
+                               const uint64_t *coef, size_t num_vars, int order, uint64_t *work, size_t work_elems, void *stream) {
+    return iwround_call(false, true, c, out, nullptr, nullptr, weights, tables, n_evals, n_tables, columns, n_index, terms, n_terms, coef, num_vars,
+                        nullptr, order, work, work_elems, stream);
+}
+int sr_vpoly_iwround_evals(sr_ctx *c, uint64_t *out, const uint64_t *weights, const uint64_t *const *tables, const size_t *n_evals, int n_tables,
+                           const sr_index_column *columns, int n_index, const sr_vpoly_term *terms, int n_terms, const uint64_t *coef,
+                           size_t num_vars, int order) {
+    return iwround_call(false, false, c, out, nullptr, nullptr, weights, tables, n_evals, n_tables, columns, n_index, terms, n_terms, coef, num_vars,
+                        nullptr, order, nullptr, 0, nullptr);
+}
+int sr_vpoly_iwround_fold_evals_dev(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
+                                    const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_index_column *columns, int n_index,
+                                    const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, const uint64_t *r, int order,
+                                    uint64_t *work, size_t work_elems, void *stream) {
+    return iwround_call(true, true, c, out, out_tables, n_evals_out, weights, tables, n_evals, n_tables, columns, n_index, terms, n_terms, coef,
+                        num_vars, r, order, work, work_elems, stream);
+}
+int sr_vpoly_iwround_fold_evals(sr_ctx *c, uint64_t *out, uint64_t *const *out_tables, size_t *n_evals_out, const uint64_t *weights,
+                                const uint64_t *const *tables, const size_t *n_evals, int n_tables, const sr_index_column *columns, int n_index,
+                                const sr_vpoly_term *terms, int n_terms, const uint64_t *coef, size_t num_vars, const uint64_t *r, int order) {
+    return iwround_call(true, false, c, out, out_tables, n_evals_out, weights, tables, n_evals, n_tables, columns, n_index, terms, n_terms, coef,
+                        num_vars, r, order, nullptr, 0, nullptr);
 }
 int sr_range_wround_plan(int ring, int log2_degree, size_t num_vars, int n_tables, int bound, int order, size_t *work_elems, int *launches) {
     return round_plan_entry(kRangeWround, ring, log2_degree, num_vars, n_tables, 0, 0, bound, order, work_elems, launches);

@@ -42,6 +42,9 @@
 //                   sumcheck_vpoly_fold.hpp), frog16 1 / 1 (188 / 237)
 // babybear72 over 8 slots needs the weight out of the registers (weight_in_lds below).  The remaining points of a fused call come from
 // the weighted round kernels over the FOLDED tables, into the same records with the same t0 / np_total convention.
+//
+// sumcheck_index.hpp holds copies of the four kernels below with a loader that also takes integer columns: a change to the flush, the
+// meeting of the lane-groups or the store sequence here has to be made there as well.
 #pragma once
 #include "sumcheck_vpoly_fold.hpp"
 

@@ -216,6 +216,57 @@ def identity_permutation_mles(ring, num_vars, num_chunks, like):
             for i in range(int(num_chunks))]
 
 
+class IndexMultilinearExtension:
+    """A multilinear extension in num_vars variables whose evaluations are an IndexColumn: evaluation e is R::from(col[e]), a stored
+    column's beyond n_evals are zero.  A factor of a VirtualPolynomial (mle.py): the weighted sum-check rounds read it as one u64 per
+    row (sr_vpoly_iwround_*), everything else expands it with to_dense() first.  A stored column's values are a CUDA tensor of
+    8-byte integers."""
+
+    def __init__(self, ring, num_vars, column):
+        self.ring, self._num_vars = ring, int(num_vars)
+        if not 0 <= self._num_vars < 48:
+            raise RingError("IndexMultilinearExtension: num_vars must be below 48")
+        self.column = col = _column(column)
+        full = 1 << self._num_vars
+        if col.is_progression:
+            if col.start + (full - 1) >= 1 << 64:
+                raise RingError("IndexMultilinearExtension: a progression wraps past 2^64 - 1")
+        else:
+            if isinstance(col.values, np.ndarray) or not (col.values.is_cuda and col.values.is_contiguous() and col.values.element_size() == 8):
+                raise RingError("IndexMultilinearExtension: the values are a contiguous CUDA tensor of 8-byte integers")
+            if col.n_evals > full:
+                raise RingError("IndexMultilinearExtension: n_evals exceeds 2^num_vars")
+
+    @property
+    def num_vars(self):
+        return self._num_vars
+
+    def __len__(self):
+        """the stored evaluations: n_evals, or 2^num_vars of a progression"""
+        return (1 << self._num_vars) if self.column.is_progression else self.column.n_evals
+
+    def key(self):
+        """what tells two columns apart as slots of a VirtualPolynomial"""
+        c = self.column
+        if c.is_progression:
+            return ("progression", c.start)
+        return ("column", c.values.data_ptr(), c.n_evals) if c.n_evals else ("empty", id(self))
+
+    def to_dense(self, stream=None):
+        """The DenseMultilinearExtension of the same evaluations: from_u64_dev over the stored part, D words per integer."""
+        import torch
+
+        from .mle import DenseMultilinearExtension
+
+        n = len(self)
+        out = torch.empty(n * self.ring.words_per_elem, dtype=torch.int64, device=torch.device("cuda", self.ring.device))
+        if stream is not None:
+            out.record_stream(stream)
+        if n:
+            from_u64_dev(self.ring, self.column, n, out=out, stream=stream)
+        return DenseMultilinearExtension(self.ring, self._num_vars, out)
+
+
 def index_count_dev(ring, idx, n_bins, out=None, stream=None):
     """sr_index_count_dev: counts[t] = #{ i : idx[i] == t } for t < n_bins as an int64 CUDA tensor (`out`, or a new one).  idx: a CUDA
     tensor of 8-byte integers read as u64.  An index >= n_bins is skipped and counted (ring.spmv_bad_index_count)."""

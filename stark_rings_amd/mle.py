@@ -249,7 +249,12 @@ class VirtualPolynomial:
     """A sum of products of dense MLEs with ring coefficients, g = sum_k c_k prod_s f_{k,s}, after HyperPlonk's VirtualPolynomial
     (the code crates/poly's polynomials/multilinear_polynomial.rs was adapted from): the object a sum-check is run on -- eq (a b - c),
     sum_i alpha_i eq prod_j (...).  The tables stay where they are; a table that is in several products is held, and read, once
-    (sr_vpoly_round_evals_dev).  At most 8 distinct tables, 8 products, 4 factors per product."""
+    (sr_vpoly_round_evals_dev).  At most 8 distinct tables, 8 products, 4 factors per product.
+
+    A factor may be an IndexMultilinearExtension (index_columns.py): a column of integers that stands for the table R::from(col[e]).
+    round_evals_weighted and fold_round_evals_weighted read such a slot as u64 (sr_vpoly_iwround_*), and the polynomial that
+    fold_round_evals_weighted returns holds dense tables only.  round_evals, sum, fold_round_evals and fixed_variables have no such
+    kernels: they expand every column slot with to_dense() first -- the slow path, D words per integer."""
 
     MAX_TABLES, MAX_TERMS, MAX_FACTORS = 8, 8, 4
 
@@ -270,10 +275,43 @@ class VirtualPolynomial:
         """the largest number of factors of a product: a round message has degree + 1 elements"""
         return max([len(t) for t in self.terms] or [0])
 
+    @staticmethod
+    def _is_column(mle):
+        from .index_columns import IndexMultilinearExtension
+
+        return isinstance(mle, IndexMultilinearExtension)
+
+    @classmethod
+    def _key(cls, mle):
+        """what deduplicates a slot: a table's device pointer; a column's array and stored length, or a progression's start"""
+        if cls._is_column(mle):
+            return mle.key()
+        return mle.evaluations.data_ptr() if len(mle) else ("empty", id(mle))
+
+    def _has_columns(self):
+        return any(self._is_column(t) for t in self.tables)
+
+    def _like(self):
+        """(dtype, device) of what the polynomial allocates"""
+        import torch
+
+        for want in (True, False):
+            for t in self.tables:
+                if not self._is_column(t) and (len(t) or not want):
+                    return t.evaluations.dtype, t.evaluations.device
+        for t in self.tables:
+            if t.column.values is not None:
+                return torch.int64, t.column.values.device
+        return torch.int64, torch.device("cuda", self.ring.device)
+
+    def _dense(self, stream):
+        """the same polynomial with every column slot expanded to a ring table (IndexMultilinearExtension.to_dense)"""
+        return self._over([t.to_dense(stream) if self._is_column(t) else t for t in self.tables], self._num_vars)
+
     def _slot_of(self, mle, new):
         if mle.ring is not self.ring or mle.num_vars != self._num_vars:
             raise RingError("VirtualPolynomial: every MLE must have the polynomial's ring and num_vars")
-        key = mle.evaluations.data_ptr() if len(mle) else ("empty", id(mle))
+        key = self._key(mle)
         if key in self._slot:
             return self._slot[key]
         if key in new:
@@ -290,7 +328,7 @@ class VirtualPolynomial:
 
     def add_mle_list(self, mles, coeff=None):
         """g += coeff * prod(mles): 1 .. 4 MLEs (one may appear twice), coeff one ring element (a tensor) or None for one().
-        Tables are deduplicated by device pointer into table slots."""
+        Tables are deduplicated by device pointer into table slots.  An MLE may be an IndexMultilinearExtension."""
         mles = list(mles)
         if not 1 <= len(mles) <= self.MAX_FACTORS:
             raise RingError("VirtualPolynomial: a product has 1 .. %d factors" % self.MAX_FACTORS)
@@ -306,7 +344,7 @@ class VirtualPolynomial:
         return self
 
     def mul_by_mle(self, mle):
-        """g *= mle: the MLE becomes one more factor of every product."""
+        """g *= mle: the MLE (dense or an IndexMultilinearExtension) becomes one more factor of every product."""
         if not self.terms:
             raise RingError("VirtualPolynomial: mul_by_mle on an empty polynomial")
         if any(len(t) >= self.MAX_FACTORS for t in self.terms):
@@ -338,6 +376,8 @@ class VirtualPolynomial:
 
         if not self.terms:
             raise RingError("VirtualPolynomial: no product has been added")
+        if self._has_columns():
+            return self._dense(stream)._call(mode, stream)
         ring, nv = self.ring, self._num_vars
         like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
         w = ring.words_per_elem
@@ -370,7 +410,7 @@ class VirtualPolynomial:
         g.tables = list(tables)
         g.terms = [list(t) for t in self.terms]
         g.coeffs = list(self.coeffs)
-        g._slot = {(t.evaluations.data_ptr() if len(t) else ("empty", id(t))): j for j, t in enumerate(g.tables)}
+        g._slot = {self._key(t): j for j, t in enumerate(g.tables)}
         return g
 
     def fold_round_evals(self, r, order=MLE_LEADING, stream=None):
@@ -388,6 +428,8 @@ class VirtualPolynomial:
         ring, nv = self.ring, self._num_vars
         if nv < 2:
             raise RingError("fold_round_evals: num_vars >= 2 (the last round folds with fixed_variables)")
+        if self._has_columns():
+            return self._dense(stream).fold_round_evals(r, order, stream)
         like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
         w = ring.words_per_elem
         out = torch.empty((self.degree + 1) * w, dtype=like.dtype, device=like.device)
@@ -416,6 +458,8 @@ class VirtualPolynomial:
         if not self.terms:
             raise RingError("VirtualPolynomial: no product has been added")
         ring, nv = self.ring, self._num_vars
+        if self._has_columns():
+            return self._round_evals_indexed(weights, order, stream)
         like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
         w = ring.words_per_elem
         out = torch.empty((self.degree + 1) * w, dtype=like.dtype, device=like.device)
@@ -428,6 +472,60 @@ class VirtualPolynomial:
                     t.record_stream(stream)
         ring._vpoly_wround_evals_dev(out, weights, [t.evaluations for t in self.tables], self.terms, coeffs, nv, order, work, stream)
         return out
+
+    def _indexed_operands(self):
+        """the operands of sr_vpoly_iwround_*: (tables, columns, terms, order) -- the dense slots first, then the column slots, the terms
+        renumbered; order[i]: the polynomial's slot of operand slot i"""
+        order = [j for j, t in enumerate(self.tables) if not self._is_column(t)] + [j for j, t in enumerate(self.tables) if self._is_column(t)]
+        where = {j: i for i, j in enumerate(order)}
+        tables = [self.tables[j].evaluations for j in order if not self._is_column(self.tables[j])]
+        columns = [self.tables[j].column for j in order if self._is_column(self.tables[j])]
+        return tables, columns, [[where[j] for j in t] for t in self.terms], order
+
+    def _round_evals_indexed(self, weights, order, stream):
+        import torch
+
+        from . import wsumcheck
+
+        ring, nv, w = self.ring, self._num_vars, self.ring.words_per_elem
+        dtype, device = self._like()
+        like = torch.empty(0, dtype=dtype, device=device)
+        tables, columns, terms, _ = self._indexed_operands()
+        out = torch.empty((self.degree + 1) * w, dtype=dtype, device=device)
+        need = wsumcheck.vpoly_iwround_plan(ring, nv, len(tables), len(columns), len(terms), self.degree, order)[0]
+        work = torch.empty(need * w, dtype=dtype, device=device) if need else None
+        coeffs = self._coeff_tensor(like, stream)
+        if stream is not None:
+            for t in (work, coeffs):
+                if t is not None:
+                    t.record_stream(stream)
+        wsumcheck.vpoly_iwround_evals_dev(ring, out, weights, tables, columns, terms, coeffs, nv, order, work, stream)
+        return out
+
+    def _fold_round_evals_indexed(self, r, next_weights, order, stream):
+        import torch
+
+        from . import wsumcheck
+
+        ring, nv, w = self.ring, self._num_vars, self.ring.words_per_elem
+        dtype, device = self._like()
+        like = torch.empty(0, dtype=dtype, device=device)
+        tables, columns, terms, slots = self._indexed_operands()
+        out = torch.empty((self.degree + 1) * w, dtype=dtype, device=device)
+        sizes = [(len(self.tables[j]) + 1) // 2 if order == MLE_LEADING else min(len(self.tables[j]), 1 << (nv - 1)) for j in slots]
+        folded = [torch.empty(n * w, dtype=dtype, device=device) for n in sizes]
+        need = wsumcheck.vpoly_iwround_plan(ring, nv, len(tables), len(columns), len(terms), self.degree, order, fold=True)[0]
+        work = torch.empty(need * w, dtype=dtype, device=device) if need else None
+        coeffs = self._coeff_tensor(like, stream)
+        if stream is not None:
+            for t in folded + [work, coeffs]:
+                if t is not None:
+                    t.record_stream(stream)
+        wsumcheck.vpoly_iwround_fold_evals_dev(ring, out, folded, next_weights, tables, columns, terms, coeffs, nv, r, order, work, stream)
+        dense = [None] * len(slots)
+        for i, j in enumerate(slots):
+            dense[j] = DenseMultilinearExtension(ring, nv - 1, folded[i])
+        return out, self._over(dense, nv - 1)
 
     def fold_round_evals_weighted(self, r, next_weights, order=MLE_LEADING, stream=None):
         """fold_round_evals with a per-pair weight on the message (sr_vpoly_wround_fold_evals_dev): every table slot folded at `r`,
@@ -442,6 +540,8 @@ class VirtualPolynomial:
         ring, nv = self.ring, self._num_vars
         if nv < 2:
             raise RingError("fold_round_evals_weighted: num_vars >= 2 (the last round folds with fixed_variables)")
+        if self._has_columns():
+            return self._fold_round_evals_indexed(r, next_weights, order, stream)
         like = next((t.evaluations for t in self.tables if len(t)), self.tables[0].evaluations)
         w = ring.words_per_elem
         out = torch.empty((self.degree + 1) * w, dtype=like.dtype, device=like.device)
@@ -467,6 +567,8 @@ class VirtualPolynomial:
         n_fixed = self.ring._batch_of(point.numel())
         if n_fixed > self._num_vars:
             raise RingError("fixed_variables: the point has more entries than the polynomial has variables")
+        if self._has_columns():
+            return self._dense(stream).fixed_variables(point, order, stream)
         fold = (lambda t: t.fixed_variables(point, stream)) if order == MLE_LEADING else (lambda t: t.fix_last_variables(point, stream))
         return self._over([fold(t) for t in self.tables], self._num_vars - n_fixed)
 
